@@ -3,10 +3,17 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1 without a launcher: re-executes itself under
                                                           torch.distributed.run, one rank per GPU, backend nccl = RCCL)
+    python bench.py ... --full                           the headline run plus everything below that is not the headline figure:
+                                                          roofline / per-kernel timers, cpu_baseline, driver-clocked variants,
+                                                          bucket probe and exposed communication (N>1)
+    python bench.py ... --dump-outputs DIR               after the timed steps: what the last timed step handed its caller,
+                                                          as float32 DIR/<name>.npy (see dump_outputs)
 
 One "step" = policy forward + backward, reference forward, DPO loss, gradient all-reduce (N>1), clip + AdamW, on a
 synthetic batch already resident in HBM: per rank 4 pairs, 336x336 image, 1024 text tokens each (BASELINE.json
 configs[1]; S = 1599 decoder positions), random N(0,0.02) bf16 weights, policy != reference.  Prints ONE JSON line.
+A plain run (no --full) sets up, warms up, times the K steps and prints the line: metric / value / unit / higher_is_better /
+dtype / ms_per_step / config; `roofline`, `cpu_baseline`, `variants` and the multi-rank `comm` measurements come with --full.
 
 roofline: the dominant kernel is the 8-phase 256x256x64 bf16 MFMA GEMM (gemm256p_kernel, all three layouts: 486 launches
 and ~79 % of the step); `achieved` = its algorithmic FLOPs (2*M*N*K per launch) / its summed launch durations, measured
@@ -266,7 +273,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--text_len", type=int, default=1024)
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer decoder layers (line is then marked INVALID)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--no_side_stream", action="store_true")
     ap.add_argument("--ref_pipeline", action="store_true", help="A/B: reference forward of the next batch issued under the update (slower at N=1, see DESIGN.md)")
     ap.add_argument("--precomputed_ref", action="store_true", help="stream precomputed reference log-probs (SURVEY 8f rank 1)")
@@ -280,9 +287,14 @@ def main():
     ap.add_argument("--fresh_batches", action="store_true", help="SURVEY 8f-3: every step takes a NEW batch from the input pipeline (JPEG files -> PIL decode + CLIP preprocess in the collator, "
                     "background prefetch, pinned H2D copy, un-memoised concatenated_inputs) instead of rotating four resident ones; reports the host ms per batch")
     ap.add_argument("--lr", type=float, default=2e-8, help="learning rate of the timed steps (kernel arithmetic does not depend on it)")
-    ap.add_argument("--no_variants", action="store_true", help="default command at 1 GPU only: skip the driver-clocked variants behind the timed region "
+    ap.add_argument("--no_variants", action="store_true", help="--full at 1 GPU only: skip the driver-clocked variants behind the timed region "
                     "(precomputed reference log-probs in-process, LoRA as a child process of this script)")
     ap.add_argument("--variant_steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline + per-kernel timers inside the timed "
+                    "region, cpu_baseline, the driver-clocked variants (trimmed by --no_cpu_baseline / --no_variants), the bucket probe and exposed "
+                    "communication (N>1)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as float32 DIR/<name>.npy (dump_outputs)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -312,7 +324,7 @@ def variant_child(flags, a, full_ms):
     """one variant of the default command as a child process (same script, same box, right behind the timed region of the parent):
     {"ms_per_step", "pairs_per_s", "ratio_to_full", "steps", "seconds"} or {"error"}"""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), *flags, "--steps", str(a.variant_steps), "--warmup", "2", "--no_cpu_baseline", "--no_variants",
+    cmd = [sys.executable, os.path.abspath(__file__), *flags, "--steps", str(a.variant_steps), "--warmup", "2", "--full", "--no_cpu_baseline", "--no_variants",
            "--pairs", str(a.pairs), "--text_len", str(a.text_len)]
     t0 = time.time()
     try:
@@ -325,6 +337,83 @@ def variant_child(flags, a, full_ms):
         return {"error": f"{type(e).__name__}: {e}"[:300], "seconds": round(time.time() - t0, 1)}
 
 
+DUMP_SAMPLE = 1 << 20          # elements drawn from each flat parameter-sized buffer by --dump-outputs (4 MB each as float32)
+
+
+def dump_outputs(path, loss, tr, eng):
+    """--dump-outputs DIR: what the last timed step handed its caller, one float32 DIR/<name>.npy per array (28 MB in all):
+    loss (the value training_step returned), metric_* (the DPO metrics it stored: rewards, margins, log-probs, logits), grad_norm
+    (the optimizer's [norm, clip coefficient, sum g^2]) and a fixed seeded sample of DUMP_SAMPLE positions of the trained flat buffers
+    - weights (bf16 working copy), master (fp32), adam_m, adam_v, grads (bf16 gradients of the last step) - with the positions
+    themselves in sample_index (float64, exact).  The same arguments give the same inputs, so two builds compare array for array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if eng.master.is_cuda:
+        torch.cuda.synchronize()
+    out = {"loss": loss.detach().float().reshape(1), "grad_norm": eng.norm_out.float()}
+    for k, v in tr._stored_metrics["train"].items():
+        out["metric_" + k.replace("/", "_")] = torch.as_tensor(v[-1], dtype=torch.float32).reshape(1)
+    lora = eng.lora is not None
+    flat = {"weights": eng.lora_flat if lora else eng.policy.flat, "master": eng.master, "adam_m": eng.m, "adam_v": eng.v,
+            "grads": eng.lora_grads if lora else eng.grads}
+    n = min(t.numel() for t in flat.values())
+    g = torch.Generator().manual_seed(20240607)
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g).sort().values
+    idx_dev = idx.to(eng.master.device)
+    for name, t in flat.items():
+        out[name] = t.reshape(-1).index_select(0, idx_dev).float()
+    out["sample_index"] = idx.double()
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def roofline(a, prof, dt, cfg, eng, S_dec, step_frac):
+    """--full: the line's `roofline` entry from the in-library HIP-event timers of the timed region (module docstring)"""
+    # HBM traffic of the dominant kernel: PMC passes cannot run inside the timed region; the committed rocprofv3 --pmc
+    # result (tools/pmc_traffic.sh -> profiles/rNN_pmc_hbm_traffic.json, newest first) is quoted ONLY when it was taken with the library
+    # built from the GEMM sources this run uses (build_hip.kernel_digest() recorded in the file) - a stale file is refused
+    import build_hip as _bh
+    lib_digest = _bh.kernel_digest()[:16]       # gemm256p.hip + gemm.h + common.h + flags
+    traffic = None
+    traffic_file = None
+    for tag in ("r06", "r05", "r04"):      # the newest counter file taken with THIS library's GEMM sources
+        tf = os.path.join(ROOT, "profiles", f"{tag}_pmc_hbm_traffic.json")
+        if not os.path.exists(tf):
+            continue
+        tj = json.load(open(tf))
+        if tj.get("source_digest") == lib_digest:
+            traffic = round(tj["gemm_hbm_bytes_per_launch"])
+            traffic_file = f"profiles/{tag}_pmc_hbm_traffic.json"
+            break
+        traffic_file = f"profiles/{tag}_pmc_hbm_traffic.json REFUSED: taken with source digest {tj.get('source_digest')}, this library is {lib_digest}"
+    # roofline of the DOMINANT kernel: the 8-phase 256x256 GEMM alone (its launches are timed under their own id; the
+    # gemm_nt/nn/tn entries of per_kernel are whole vlr_gemm_bf16 calls incl. peeled rows and split-K reduces)
+    g_n, g_ms, g_flop = prof["gemm256p"]
+    all_ms = sum(prof[k][1] for k in ("gemm_nt", "gemm_nn", "gemm_tn"))
+    g_bytes = 0.0   # algorithmic elements moved (A + B + C once) summed over the decoder GEMMs of the timed steps
+    H_, I_, M_ = cfg["hidden"], cfg["inter"], 2 * a.pairs * S_dec
+    per_shape = cfg["layers"] * a.steps * ((1 if a.precomputed_ref else 2) + 2)   # fwd (policy [+ ref]) + dgrad + wgrad
+    Nqkv_ = eng.Nqkv
+    for m_, n_, k_ in ((M_, Nqkv_, H_), (M_, H_, eng.Nq), (M_, 2 * I_, H_), (M_, H_, I_)):
+        g_bytes += per_shape * (m_ * k_ + n_ * k_ + m_ * n_)
+    if eng.resid_f32:     # o_proj / down_proj forward launches read the fp32 residual and write the fp32 stream (8 bytes per element instead of a 2-byte store)
+        g_bytes += 2 * cfg["layers"] * a.steps * (1 if a.precomputed_ref else 2) * (M_ * H_ * 3)       # in 2-byte elements: + 6 bytes per element
+    # every entry with its own fraction of the nominal bf16 MFMA peak (attention included: the kernels furthest below it)
+    per_kernel = {k: {"launches": n, "ms": round(ms, 2), "tflops": round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 else 0.0,
+                      "frac": round(fl / (ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if ms > 0 else 0.0}
+                  for k, (n, ms, fl) in prof.items()}
+    achieved = g_flop / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
+    return {"bound": "mfma", "kernel": "gemm256p_kernel<A_KS,B_KS> (8-phase 256x256x64 bf16 GEMM: NT/NN/TN)", "achieved": round(achieved, 1),
+            "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+            "traffic": traffic, "traffic_source": traffic_file, "traffic_unit": "bytes/launch leaving L2 (2*FETCH_SIZE+WRITE_SIZE, rocprofv3 --pmc, OFFLINE pass of tools/pmc_traffic.sh with the same binary - counters cannot be collected inside the timed region; A+B of a decoder GEMM fit the 256 MB Infinity Cache, so most of the re-reads never reach HBM)",
+            "algorithmic_bytes_per_launch": round(2.0 * g_bytes / max(1, g_n)), "launches": g_n, "avg_launch_ms": round(g_ms / max(1, g_n), 4), "event_sampling": f"one launch in {max(1, a.prof_sample)} bracketed by HIP events (pseudo-random per kernel id); launches and FLOPs exact, ms = sampled mean x launches", "per_kernel": per_kernel,
+            "profile_file": PROFILE_FILE, "gemm_source_digest": lib_digest,
+            "kernel_share_of_step": round(g_ms * 1e-3 / dt, 3), "all_gemm_share_of_step": round(all_ms * 1e-3 / dt, 3),
+            "share_note": "kernel_share = the 256x256 kernel's launches alone; all_gemm_share = every vlr_gemm_* call by layout (fused launches, peeled rows and split-K reduces included), so all_gemm_share >= kernel_share",
+            "step_frac": step_frac,
+            "step_frac_note": "algorithmic TFLOP per pair of SURVEY.md 8d (lm-head counted on all S positions; the kernel evaluates it on the response rows only, ~1.3 % fewer executed FLOPs) / nominal 2516.6 TF/s; this chip sustains 1828 TF/s on random bf16 operands in a register-only MFMA loop (profiles/r02_gemm_ceiling_mfma_only_and_ablation.txt)"}
+
+
 def run(a):
     from vlrlhf import _hip
     from vlrlhf.models.Llava import LlavaDPOTrainer, LlavaForRL
@@ -332,7 +421,7 @@ def run(a):
     from vlrlhf.utils.synthetic import LLAVA_1_5_7B, init_random_model, synthetic_batch
     from types import SimpleNamespace
 
-    rccl_log = rccl_debug_setup() if int(os.environ.get("WORLD_SIZE", "1")) > 1 else None
+    rccl_log = rccl_debug_setup() if a.full and int(os.environ.get("WORLD_SIZE", "1")) > 1 else None
     rank, local, world = init_distributed_from_env()
     assert world == max(1, a.gpus), f"--gpus {a.gpus} but WORLD_SIZE={world}"
     torch.cuda.set_device(local)
@@ -385,6 +474,7 @@ def run(a):
             transport_fallback = str(e)[:300]
             os.environ["VLR_COMM"] = "torch"
             reducer = eng.make_reducer()
+    if world > 1 and a.full:
         # one 0.4 GB bucket (a decoder layer's gradients) on communicators of their own: RCCL's default channel count against the bound
         # that matches the CU reservation, and against half of it (would 8 CUs do?)
         n_bucket = 4 * cfg["hidden"] * cfg["hidden"] + 3 * cfg["hidden"] * cfg["inter"]
@@ -478,13 +568,14 @@ def run(a):
     for _ in range(a.warmup - 1):
         loss = step()
     barrier()
-    _hip.lib_profile_start(a.prof_sample)
+    if a.full:
+        _hip.lib_profile_start(a.prof_sample)
     t0 = time.time()
     for _ in range(a.steps):
         loss = step()
     barrier()
     dt = time.time() - t0
-    prof = _hip.lib_profile_stop()
+    prof = _hip.lib_profile_stop() if a.full else None
     tmax = torch.tensor([dt], device="cuda")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -494,10 +585,12 @@ def run(a):
     import math
     assert math.isfinite(loss_first) and math.isfinite(loss_last), (loss_first, loss_last)
     assert torch.isfinite(eng.norm_out).all(), "non-finite gradient norm in the timed region"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, tr, eng)
     # exposed communication: the same steps with the gradient exchange switched off (ranks diverge afterwards - timing only); no bucket is
     # issued, so no CUs are given up either: the difference is everything the exchange costs (its exposed part + the bucket-window reservation)
     exposed_ms = None
-    if reducer is not None:
+    if reducer is not None and a.full:
         reducer.enabled = False
         step()
         barrier()
@@ -510,40 +603,7 @@ def run(a):
         dist.all_reduce(t2, op=dist.ReduceOp.MAX)
         exposed_ms = round((dt / a.steps - float(t2)) * 1e3, 2)
         reducer.enabled = True
-    # HBM traffic of the dominant kernel: PMC passes cannot run inside the timed region; the committed rocprofv3 --pmc
-    # result (tools/pmc_traffic.sh -> profiles/rNN_pmc_hbm_traffic.json, newest first) is quoted ONLY when it was taken with the library
-    # built from the GEMM sources this run uses (build_hip.kernel_digest() recorded in the file) - a stale file is refused
-    import build_hip as _bh
-    lib_digest = _bh.kernel_digest()[:16]       # gemm256p.hip + gemm.h + common.h + flags
-    traffic = None
-    traffic_file = None
-    for tag in ("r06", "r05", "r04"):      # the newest counter file taken with THIS library's GEMM sources
-        tf = os.path.join(ROOT, "profiles", f"{tag}_pmc_hbm_traffic.json")
-        if not os.path.exists(tf):
-            continue
-        tj = json.load(open(tf))
-        if tj.get("source_digest") == lib_digest:
-            traffic = round(tj["gemm_hbm_bytes_per_launch"])
-            traffic_file = f"profiles/{tag}_pmc_hbm_traffic.json"
-            break
-        traffic_file = f"profiles/{tag}_pmc_hbm_traffic.json REFUSED: taken with source digest {tj.get('source_digest')}, this library is {lib_digest}"
-    # roofline of the DOMINANT kernel: the 8-phase 256x256 GEMM alone (its launches are timed under their own id; the
-    # gemm_nt/nn/tn entries of per_kernel are whole vlr_gemm_bf16 calls incl. peeled rows and split-K reduces)
-    g_n, g_ms, g_flop = prof["gemm256p"]
-    all_ms = sum(prof[k][1] for k in ("gemm_nt", "gemm_nn", "gemm_tn"))
-    g_bytes = 0.0   # algorithmic elements moved (A + B + C once) summed over the decoder GEMMs of the timed steps
     S_dec = int(tr.model._last_ctx["S"])            # decoder length of the last policy pass (1599 at configs[1])
-    H_, I_, M_ = cfg["hidden"], cfg["inter"], 2 * a.pairs * S_dec
-    per_shape = cfg["layers"] * a.steps * ((1 if a.precomputed_ref else 2) + 2)   # fwd (policy [+ ref]) + dgrad + wgrad
-    Nqkv_ = eng.Nqkv
-    for m_, n_, k_ in ((M_, Nqkv_, H_), (M_, H_, eng.Nq), (M_, 2 * I_, H_), (M_, H_, I_)):
-        g_bytes += per_shape * (m_ * k_ + n_ * k_ + m_ * n_)
-    if eng.resid_f32:     # o_proj / down_proj forward launches read the fp32 residual and write the fp32 stream (8 bytes per element instead of a 2-byte store)
-        g_bytes += 2 * cfg["layers"] * a.steps * (1 if a.precomputed_ref else 2) * (M_ * H_ * 3)       # in 2-byte elements: + 6 bytes per element
-    # every entry with its own fraction of the nominal bf16 MFMA peak (attention included: the kernels furthest below it)
-    per_kernel = {k: {"launches": n, "ms": round(ms, 2), "tflops": round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 else 0.0,
-                      "frac": round(fl / (ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if ms > 0 else 0.0}
-                  for k, (n, ms, fl) in prof.items()}
     pairs_per_s = world * a.pairs * a.steps / dt
     per_pair = TFLOP_PER_PAIR["ref_precomputed" if a.precomputed_ref else "ref_in_step"]
     if nxt:
@@ -552,7 +612,6 @@ def run(a):
     if qwen:
         per_pair = tflop_per_pair_qwen(cfg, S_dec, not a.precomputed_ref, a.lora)
     if rank == 0:
-        achieved = g_flop / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
         line = {
             "metric": "preference-pairs/sec (chosen+rejected) LLaVA-1.5-7B DPO step", "value": round(pairs_per_s, 4),
             "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -583,16 +642,9 @@ def run(a):
                      "comm_cus_scope": reducer.reserve_scope if reducer is not None else None,      # "backward": the CUs are given up only while buckets are in flight (compute_cus above = outside that window)
                      "rccl_max_min_nchannels": list(reducer.rccl_channels) if reducer is not None else None,     # NCCL_MAX_NCHANNELS := comm_cus for torch's communicator (parallel.rccl_channel_env); MIN only if the user set it
                      "exposed_ms_per_step": exposed_ms, "bytes_per_step": 2 * (eng.lora_layout.numel if a.lora else eng.layout.numel)},
-            "roofline": {"bound": "mfma", "kernel": "gemm256p_kernel<A_KS,B_KS> (8-phase 256x256x64 bf16 GEMM: NT/NN/TN)", "achieved": round(achieved, 1),
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         "traffic": traffic, "traffic_source": traffic_file, "traffic_unit": "bytes/launch leaving L2 (2*FETCH_SIZE+WRITE_SIZE, rocprofv3 --pmc, OFFLINE pass of tools/pmc_traffic.sh with the same binary - counters cannot be collected inside the timed region; A+B of a decoder GEMM fit the 256 MB Infinity Cache, so most of the re-reads never reach HBM)",
-                         "algorithmic_bytes_per_launch": round(2.0 * g_bytes / max(1, g_n)), "launches": g_n, "avg_launch_ms": round(g_ms / max(1, g_n), 4), "event_sampling": f"one launch in {max(1, a.prof_sample)} bracketed by HIP events (pseudo-random per kernel id); launches and FLOPs exact, ms = sampled mean x launches", "per_kernel": per_kernel,
-                         "profile_file": PROFILE_FILE, "gemm_source_digest": lib_digest,
-                         "kernel_share_of_step": round(g_ms * 1e-3 / dt, 3), "all_gemm_share_of_step": round(all_ms * 1e-3 / dt, 3),
-                         "share_note": "kernel_share = the 256x256 kernel's launches alone; all_gemm_share = every vlr_gemm_* call by layout (fused launches, peeled rows and split-K reduces included), so all_gemm_share >= kernel_share",
-                         "step_frac": round(pairs_per_s / world * per_pair / PEAK_BF16_TFLOPS, 4),
-                         "step_frac_note": "algorithmic TFLOP per pair of SURVEY.md 8d (lm-head counted on all S positions; the kernel evaluates it on the response rows only, ~1.3 % fewer executed FLOPs) / nominal 2516.6 TF/s; this chip sustains 1828 TF/s on random bf16 operands in a register-only MFMA loop (profiles/r02_gemm_ceiling_mfma_only_and_ablation.txt)"},
         }
+        if a.full:
+            line["roofline"] = roofline(a, prof, dt, cfg, eng, S_dec, round(pairs_per_s / world * per_pair / PEAK_BF16_TFLOPS, 4))
         if a.layers:
             line["INVALID"] = "reduced layer count (debug run)"
         if nxt:
@@ -613,7 +665,8 @@ def run(a):
                                           + ", frozen ViT + projector; PLoRA on the fused C layer calls (vlr_decoder_layer_*_lora_ex)" + ("; peft LoRA stacked on it on the two-adapter passes (vlr_decoder_layer_*_lora2)" if a.lora else ""))
             line["config"]["variant"] = "internlm_xc2" + ("+lora" if a.lora else "") + " (not the headline configuration)"
             line["config"]["tflop_per_pair"] = round(per_pair_i, 2)
-            line["roofline"]["step_frac"] = None if a.lora else round(pairs_per_s / world * per_pair_i / PEAK_BF16_TFLOPS, 4)
+            if a.full:
+                line["roofline"]["step_frac"] = None if a.lora else round(pairs_per_s / world * per_pair_i / PEAK_BF16_TFLOPS, 4)
         elif qwen:
             line["metric"] = "preference-pairs/sec (chosen+rejected) Qwen-VL-Chat DPO step"
             line["config"]["workload"] = (f"variant on BASELINE.json configs[2]: Qwen-VL-Chat DPO bf16, 448x448 image (1024 patches -> 256 resampler "
@@ -623,16 +676,18 @@ def run(a):
                                              "full fine-tune of the language model + resampler (attn_pool), reference forward inside the step, frozen ViT trunk"))
             line["config"]["variant"] = "qwen_vl" + ("+lora" if a.lora else "") + " (not the headline configuration)"
             line["config"]["tflop_per_pair"] = round(per_pair, 2)
-            line["roofline"]["step_frac"] = round(pairs_per_s / world * per_pair / PEAK_BF16_TFLOPS, 4)
+            if a.full:
+                line["roofline"]["step_frac"] = round(pairs_per_s / world * per_pair / PEAK_BF16_TFLOPS, 4)
         elif a.lora:
             line["config"]["workload"] = line["config"]["workload"].replace(
                 "full fine-tune of LLM+projector", "LoRA r=128 alpha=256 dropout=0.05 on the 7 decoder linears (scripts/ddpo_llava.sh), frozen base")
             line["config"]["variant"] = "lora (not the headline configuration)"
-            line["roofline"]["step_frac"] = None
-        if not a.no_cpu_baseline and world == 1:
+            if a.full:
+                line["roofline"]["step_frac"] = None
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["_cpu_baseline"] = True
         plain = world == 1 and a.model == "llava" and not (a.lora or a.precomputed_ref or a.layers or a.gradient_checkpointing or a.fresh_batches or a.ref_pipeline)
-        if plain and not a.no_variants:
+        if plain and a.full and not a.no_variants:
             # SURVEY 8f row 1 on the driver's clock, in-process: the same engine and batches, the reference log-probs stored on the batches
             # (what trl's precompute_ref_log_probs leaves on the dataset rows) - the trainer then runs no reference forward
             for b_ in batches:

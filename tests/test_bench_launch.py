@@ -64,3 +64,38 @@ def test_relaunch_passes_arguments_and_exit_code(tmp_path):
     script.write_text("import os, sys\nassert os.environ['WORLD_SIZE'] == '2' and os.environ['MASTER_ADDR'] == '127.0.0.1'\n"
                       "assert sys.argv[1:] == ['--x', '7']\nsys.exit(0 if os.environ['LOCAL_RANK'] in '01' else 3)\n")
     assert relaunch_under_torchrun(str(script), ["--x", "7"], 2) == 0
+
+
+def test_dump_outputs_cpu(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): float32 / float64 .npy files only, a fixed seeded sample of the flat buffers (the same
+    positions every run), within 64 MB, and the last step's loss and metrics"""
+    sys.path[:0] = [ROOT]
+    import importlib
+    import numpy as np
+    import torch
+    from collections import defaultdict
+    from types import SimpleNamespace
+    bench = importlib.import_module("bench")
+    n = (1 << 20) + 12345
+    g = torch.Generator().manual_seed(0)
+    eng = SimpleNamespace(lora=None, policy=SimpleNamespace(flat=torch.randn(n, generator=g).bfloat16()), master=torch.randn(n, generator=g),
+                          m=torch.randn(n, generator=g), v=torch.rand(n, generator=g), grads=torch.randn(n, generator=g).bfloat16(),
+                          norm_out=torch.tensor([3.0, 0.25, 9.0]))
+    tr = SimpleNamespace(_stored_metrics=defaultdict(lambda: defaultdict(list)))
+    for step in range(3):
+        tr._stored_metrics["train"]["rewards/chosen"].append(torch.tensor(float(step)))
+        tr._stored_metrics["train"]["logps/rejected"].append(torch.tensor(-10.0 - step))
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.6931), tr, eng)
+        outs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert set(a) == {"loss", "grad_norm", "metric_rewards_chosen", "metric_logps_rejected", "weights", "master", "adam_m", "adam_v", "grads",
+                      "sample_index"}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["sample_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and idx.min() >= 0 and idx.max() < n
+    assert np.array_equal(a["master"], eng.master.numpy()[idx]) and np.array_equal(a["weights"], eng.policy.flat.float().numpy()[idx])
+    assert a["metric_rewards_chosen"][0] == 2.0 and a["metric_logps_rejected"][0] == -12.0 and abs(a["loss"][0] - 0.6931) < 1e-6
