@@ -470,6 +470,63 @@ typedef struct { void* xn; void* qkv; void* attn; void* h; } vlr_vit_ws;   /* [M
 int vlr_vit_layer_fwd(const vlr_vit_cfg* cfg, const vlr_vit_layer_weights* w, const vlr_vit_ws* ws, void* x_inout,
                       int n_img, int T, vlr_stream_t stream);
 
+/* ---- decoding with a KV cache (replaces transformers LlamaAttention / LlamaMLP with a DynamicCache during GenerationMixin.generate:
+ *      one new token per sequence per step, the K / V of every earlier token kept per layer; reference call site
+ *      base/trainer.py:310-360 `model.generate`).  Every kernel below is bound by HBM bandwidth: the weights are read once per step.
+ *
+ * vlr_gemv_bf16 - skinny GEMM Y [M][N] = X [M][K] . W [N][K]^T for 1 <= M <= 16 (what vlr_gemm_bf16 layout 0 computes; its 128- and
+ *   256-row tiles would do 8-256x the work at M = 4).  X, W bf16, fp32 accumulation, K % 8 == 0, any N; X and W 16-byte aligned, W dense
+ *   (row stride K).  Split-K partials go to `workspace` (vlr_gemv_workspace_bytes(M, N, K) bytes) and are summed in a fixed order: no
+ *   atomics, bit-reproducible.  Epilogue by `mode`:
+ *     VLR_GEMV_BF16     Y bf16 [M][ldy] = acc + bias[n] + residual bf16 [M][ldr] (bias / residual NULL = none; Y == residual allowed)
+ *     VLR_GEMV_F32      Y fp32 [M][ldy] = acc + bias[n]                                      (lm-head logits)
+ *     VLR_GEMV_F32RES   Y fp32 [M][ldy] = acc + residual fp32 [M][ldr]; Y == residual allowed (o_proj / down_proj on vlr_llama_cfg.resid_f32)
+ *     VLR_GEMV_QKV_ROPE Y bf16 = acc + bias, then rotate-half RoPE at pos[m] on the first rope_cols columns - the arithmetic of
+ *                       vlr_gemm_qkv_rope_bias (rotation of the fp32 accumulators, one rounding)
+ *     VLR_GEMV_SWIGLU   N = 2 I (gate | up rows of W): Y bf16 [M][I] = silu(gate) * up - the epilogue of vlr_gemm_swiglu; gate | up is
+ *                       not stored
+ *   pos / cos_t / sin_t / rope_cols / head_dim / max_pos are read by VLR_GEMV_QKV_ROPE only. */
+enum { VLR_GEMV_BF16 = 0, VLR_GEMV_F32 = 1, VLR_GEMV_F32RES = 2, VLR_GEMV_QKV_ROPE = 3, VLR_GEMV_SWIGLU = 4 };
+long vlr_gemv_workspace_bytes(int M, int N, int K);
+int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual, int ldr,
+                  const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
+                  void* workspace, vlr_stream_t stream);
+/* vlr_kv_cache_write - the K / V column blocks k, v of a fused [batch*S][ld] q|k|v buffer (post-RoPE) -> cache columns slot0 ..
+ *   slot0 + S - 1 of k_cache, v_cache [batch][kv_heads][cap][head_dim] bf16: an exact copy.  Serves the prefill (S = merged length,
+ *   slot0 = 0) and every decode step (S = 1, slot0 = filled length).  Replaces DynamicCache.update's torch.cat. */
+int vlr_kv_cache_write(const void* k, const void* v, int ld, void* k_cache, void* v_cache, int batch, int S, int kv_heads,
+                       int head_dim, int cap, int slot0, vlr_stream_t stream);
+/* vlr_attn_decode_gqa - attention of ONE new query row per sequence against its cache: q [batch][ldq] (head h at columns h*head_dim,
+ *   post-RoPE), key_mask [batch][cap] int32 (0 = padded key), the first `len` cache columns (the new token's own included); o bf16
+ *   [batch][ldo], head h at h*head_dim.  fp32 softmax with `scale`: the last row of vlr_attn_fwd_gqa (causal) on the same keys.
+ *   Split-KV: a workgroup owns (sequence, kv head, key chunk) and the heads / kv_heads query heads of that group (1, 2, 4 or 8); the
+ *   partials go to `workspace` (vlr_attn_decode_workspace_bytes(batch, heads, cap) bytes) and a second kernel folds them in chunk
+ *   order.  head_dim 128 only (VLR_ERR_ARG otherwise); 1 <= len <= cap. */
+long vlr_attn_decode_workspace_bytes(int batch, int heads, int cap);
+int vlr_attn_decode_gqa(const void* q, int ldq, const void* k_cache, const void* v_cache, const int* key_mask, void* o, int ldo,
+                        void* workspace, int batch, int heads, int kv_heads, int head_dim, int cap, int len, float scale,
+                        vlr_stream_t stream);
+/* vlr_decoder_layer_decode - one decoder layer (vlr_decoder_layer_fwd_ex's arithmetic) for one new token per sequence:
+ *   RMSNorm -> q|k|v + bias + RoPE (vlr_gemv_bf16) -> cache write at column len -> decode attention over len + 1 columns -> o_proj +
+ *   residual -> RMSNorm -> gate|up SwiGLU -> down_proj + residual.  x_inout [batch][hidden] is the residual stream (fp32 when
+ *   cfg->resid_f32, else bf16), updated in place; pos [batch] the new rows' positions; key_mask [batch][cap] must already mark column
+ *   len of every row (the new token).  kv_heads and bqkv are honoured; head_dim 128; len < cap.  Batches above 16 rows run the skinny
+ *   GEMMs in 16-row groups.  Scratch: */
+typedef struct {
+    void* xn;          /* bf16 [batch][hidden] */
+    float* rstd;       /* [batch] */
+    void* qkv;         /* bf16 [batch][Nq + 2 Nkv] */
+    void* attn;        /* bf16 [batch][Nq] */
+    void* act;         /* bf16 [batch][inter] */
+    void* gemv_ws;     /* >= gemv_ws_bytes: the largest vlr_gemv_workspace_bytes(min(batch, 16), N, K) of the layer's four projections */
+    long gemv_ws_bytes;
+    void* attn_ws;     /* >= attn_ws_bytes: vlr_attn_decode_workspace_bytes(batch, heads, cap) */
+    long attn_ws_bytes;
+} vlr_decode_ws;
+int vlr_decoder_layer_decode(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_decode_ws* ws, void* x_inout,
+                             const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len,
+                             vlr_stream_t stream);
+
 /* ---- data-parallel gradient exchange on RCCL over xGMI (replaces accelerate MULTI_GPU / torch DDP's NCCL all-reduce:
  *      /root/reference accelerate_config/ddp.yaml:1-14; the reference itself never calls a collective).  One process per
  *      GPU, one communicator per process.  RCCL is dlopen'ed at run time (the copy already mapped into the process,

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libvlr_hip.so")
-SOURCES = ["api.cpp", "layers.cpp", "comm.cpp", "gemm.hip", "gemm128p.hip", "lora_dx.hip", "lora_rows.hip", "gemm256p.hip", "attention.hip", "elementwise.hip", "dpo_ops.hip"]
+SOURCES = ["api.cpp", "layers.cpp", "comm.cpp", "gemm.hip", "gemm128p.hip", "lora_dx.hip", "lora_rows.hip", "gemm256p.hip", "attention.hip", "elementwise.hip", "dpo_ops.hip", "decode.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-I/opt/rocm/include"]
 
 
@@ -102,6 +102,25 @@ def check_attn_fwd3_isa(asm_path):
         raise RuntimeError(f"attention.hip: the ISA audit found {seen} attn_fwd3_kernel instantiations (expected 2) - update check_attn_fwd3_isa")
 
 
+def check_gemv_isa(asm_path):
+    """decode.hip: the skinny GEMM is as fast as the weight bytes it keeps in flight - every k chunk issues its 20 16-byte loads (4 X + 16 W
+    fragments) before the first wait on them.  A vector-memory wait between those loads (hipcc serialising a conditional load) would cut
+    the bytes in flight per lane by up to 20x.  Raises when the loads in front of the gemv_kernel's first vmcnt wait are fewer than 20."""
+    import re
+    text = open(asm_path).read()
+    m = re.search(r"^(_Z11gemv_kernel\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M)
+    if not m:
+        raise RuntimeError("decode.hip: the ISA audit found no gemv_kernel - update check_gemv_isa")
+    loads = 0
+    for line in m.group(2).split("\n"):
+        if "global_load_dwordx4" in line:
+            loads += 1
+        elif "s_waitcnt" in line and "vmcnt" in line and loads:
+            break
+    if loads < 20:
+        raise RuntimeError(f"decode.hip: gemv_kernel waits after {loads} of its 20 fragment loads per k chunk")
+
+
 def build(force=False, verbose=True, defines=(), tag=""):
     """defines / tag: a diagnostics variant of the library (e.g. defines=("VLR_GEMM_TRACE",), tag="_trace" -> libvlr_hip_trace.so with
     its own object directory), loaded through VLR_LIB; the product build is the one with neither."""
@@ -120,8 +139,8 @@ def build(force=False, verbose=True, defines=(), tag=""):
         cmd = [hipcc] + FLAGS + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if src.endswith(".hip"):
             cmd.append("-Rpass-analysis=kernel-resource-usage")
-        if src in ("gemm256p.hip", "attention.hip"):
-            cmd.append("-save-temps")          # keeps the gfx950 assembly (in OBJ) for check_kloop_isa / check_attn_fwd3_isa
+        if src in ("gemm256p.hip", "attention.hip", "decode.hip"):
+            cmd.append("-save-temps")          # keeps the gfx950 assembly (in OBJ) for check_kloop_isa / check_attn_fwd3_isa / check_gemv_isa
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=OBJ)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr[-4000:]}")
@@ -135,6 +154,8 @@ def build(force=False, verbose=True, defines=(), tag=""):
             check_kloop_isa(os.path.join(OBJ, "gemm256p-hip-amdgcn-amd-amdhsa-gfx950.s"))
         if src == "attention.hip":
             check_attn_fwd3_isa(os.path.join(OBJ, "attention-hip-amdgcn-amd-amdhsa-gfx950.s"))
+        if src == "decode.hip":
+            check_gemv_isa(os.path.join(OBJ, "decode-hip-amdgcn-amd-amdhsa-gfx950.s"))
         return obj
 
     with ThreadPoolExecutor(max_workers=6) as ex:

@@ -1,0 +1,397 @@
+// KV-cache decoding: one new token per sequence against a per-layer K/V cache (transformers LlamaAttention with a DynamicCache
+// during `generate`).  Every kernel here is bound by HBM bandwidth, not by the matrix pipe:
+//
+//   gemv_kernel          Y [M][N] = X [M][K] . W [N][K]^T for M <= 16 - the weight matrix is streamed ONCE.  One MFMA
+//                        (v_mfma_f32_16x16x32_bf16) per 16 x 16 x 32 block with M padded to 16: a lane's W operand is one 16-byte
+//                        load, the X operand one more that four n tiles share, so the whole inner loop is 16-byte loads and four
+//                        MFMAs per k step.  VALU dot products would need M x 8 FMAs plus the bf16 unpacking per W load - at
+//                        M = 16 that is as long as the load itself; the padded MFMA costs nothing the loads do not already hide.
+//                        A workgroup (4 waves) owns 64 output columns and one K slice; its waves take 128-k chunks in turn and
+//                        meet in LDS in a fixed order.  K slices (split-K, enough workgroups to cover the chip at N = 4096) write
+//                        fp32 partials; gemv_epilogue_kernel sums them in slice order and applies the epilogue: no atomics, the
+//                        result is bit-reproducible.
+//   kv_cache_write_kernel  post-RoPE K / V column blocks of the fused qkv rows -> cache columns slot0 .. slot0 + S - 1 (exact copy)
+//   attn_decode_kernel   flash-decoding: a workgroup owns (sequence, kv head, key chunk) and all heads / kv_heads query heads of the
+//                        group, so a grouped K/V chunk is read once; partials (max, sum, fp32 accumulator) go to a workspace and
+//                        attn_decode_combine_kernel folds them in chunk order.
+#include "../../include/vlr.h"
+#include "common.h"
+
+constexpr int GV_COLS = 64;          // output columns per workgroup (4 MFMA n tiles of 16)
+constexpr int GV_CHUNK = 128;        // k per chunk: 4 MFMA k steps of 32, all loads issued before the MFMAs
+constexpr int GV_TARGET_WGS = 1024;  // split K until about this many workgroups are in flight (256 CUs)
+
+__device__ __forceinline__ bf16x8 load8(const bf16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
+
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
+                                                   float* __restrict__ part, int M, int N, int K, int cps) {
+    __shared__ float red[4][16][GV_COLS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * GV_COLS, split = blockIdx.y;
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
+    const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
+    const bool mok = r < M;
+    const bf16_t* xrow = X + (size_t)(mok ? r : 0) * ldx;
+    const bf16_t* wrow[4];
+    bool nok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int n = n0 + t * 16 + r;
+        nok[t] = n < N;
+        wrow[t] = W + (size_t)(nok[t] ? n : 0) * K;
+    }
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+    // lane (r, g) holds A[m = r][k = 8 g + j] (X) and B[k = 8 g + j][n = r] (a row of W) of every 32-k step
+    for (int c = c0 + wv; c < c1; c += 4) {
+        bf16x8 a[4], b[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = c * GV_CHUNK + u * 32 + g * 8;
+            const bool kok = k < K;                        // K % 8 == 0: a lane's 8 k are all in or all out
+            a[u] = (mok && kok) ? load8(xrow + k) : zero;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) b[u][t] = (nok[t] && kok) ? load8(wrow[t] + k) : zero;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[u][t], acc[t], 0, 0, 0);
+    }
+    // D map: lane holds D[m = 4 g + i][n = r] of each n tile
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[wv][4 * g + i][t * 16 + r] = acc[t][i];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int idx = threadIdx.x + 256 * e, m = idx / GV_COLS, n = idx % GV_COLS;
+        if (m < M && n0 + n < N)
+            part[((size_t)split * M + m) * N + n0 + n] = ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n];
+    }
+}
+
+struct GemvEpi {
+    int mode;
+    const float* part;
+    int S, M, N;
+    void* Y;
+    int ldy;
+    const bf16_t* bias;
+    const void* res;
+    int ldr;
+    const int* pos;
+    const float* cos_t;
+    const float* sin_t;
+    int rope_cols, hd, max_pos;
+};
+
+__device__ __forceinline__ float gv_acc(const GemvEpi& p, int m, int n) {
+    float s = 0.f;
+    for (int k = 0; k < p.S; ++k) s += p.part[((size_t)k * p.M + m) * p.N + n];     // split order: fixed
+    return s;
+}
+
+// one thread = one output element (one rotated pair under RoPE): consecutive threads read consecutive partials, and M x N threads fill
+// the chip even at M = 1 (an 8-column-per-thread form ran on 8 workgroups at M = 4, N = 4096 and took ~15 us per call)
+__global__ __launch_bounds__(256) void gemv_epilogue_kernel(GemvEpi p, int units) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= p.M * units) return;
+    const int m = gid / units, u = gid % units;
+    if (p.mode == VLR_GEMV_SWIGLU) {                          // N = 2 I: gate columns [0, I), up columns [I, 2 I)
+        const int I = p.N / 2;
+        const float gt = gv_acc(p, m, u), up = gv_acc(p, m, I + u);
+        ((bf16_t*)p.Y)[(size_t)m * p.ldy + u] = f32_to_bf16(gt * fast_sigmoid(gt) * up);
+        return;
+    }
+    if (p.mode == VLR_GEMV_QKV_ROPE) {
+        const int half = p.hd / 2;
+        bf16_t* y = (bf16_t*)p.Y + (size_t)m * p.ldy;
+        if (u < p.rope_cols / 2) {                            // frequency f of one rotated head: columns c1 and c1 + hd / 2
+            const int head = u / half, f = u % half;
+            const int c1 = head * p.hd + f, c2 = c1 + half;
+            int ps = p.pos[m];
+            ps = ps < 0 ? 0 : (ps >= p.max_pos ? p.max_pos - 1 : ps);
+            float x1 = gv_acc(p, m, c1), x2 = gv_acc(p, m, c2);
+            if (p.bias) { x1 += bf16_to_f32(p.bias[c1]); x2 += bf16_to_f32(p.bias[c2]); }
+            const float cs = p.cos_t[(size_t)ps * half + f], sn = p.sin_t[(size_t)ps * half + f];
+            y[c1] = f32_to_bf16(x1 * cs - x2 * sn);
+            y[c2] = f32_to_bf16(x2 * cs + x1 * sn);
+            return;
+        }
+        const int c = p.rope_cols + u - p.rope_cols / 2;
+        y[c] = f32_to_bf16(gv_acc(p, m, c) + (p.bias ? bf16_to_f32(p.bias[c]) : 0.f));
+        return;
+    }
+    float v = gv_acc(p, m, u) + (p.bias ? bf16_to_f32(p.bias[u]) : 0.f);
+    if (p.mode == VLR_GEMV_BF16) {
+        if (p.res) v += bf16_to_f32(((const bf16_t*)p.res)[(size_t)m * p.ldr + u]);
+        ((bf16_t*)p.Y)[(size_t)m * p.ldy + u] = f32_to_bf16(v);
+    } else {                                                  // fp32 out (VLR_GEMV_F32), + fp32 residual (VLR_GEMV_F32RES, in place allowed)
+        if (p.mode == VLR_GEMV_F32RES && p.res) v += ((const float*)p.res)[(size_t)m * p.ldr + u];
+        ((float*)p.Y)[(size_t)m * p.ldy + u] = v;
+    }
+}
+
+// split count: enough workgroups for the chip, every split at least one chunk per wave where K allows
+static int gemv_splits(int N, int K) {
+    const int nb = (N + GV_COLS - 1) / GV_COLS, nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
+    int s = (GV_TARGET_WGS + nb - 1) / nb;
+    const int smax = (nchunks + 3) / 4;
+    s = s < 1 ? 1 : (s > smax ? smax : s);
+    const int cps = (nchunks + s - 1) / s;
+    return (nchunks + cps - 1) / cps;                         // no empty split
+}
+
+__global__ __launch_bounds__(256) void kv_cache_write_kernel(const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ld,
+                                                             bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int S, int kvh, int hd,
+                                                             int cap, int slot0, long per) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * per) return;
+    const bool isv = i >= per;
+    if (isv) i -= per;
+    const int v8 = hd / 8;
+    const int e8 = (int)(i % v8);
+    long rest = i / v8;
+    const int h = (int)(rest % kvh);
+    rest /= kvh;
+    const int s = (int)(rest % S);
+    const long b = rest / S;
+    const bf16_t* src = (isv ? v : k) + (size_t)(b * S + s) * ld + (size_t)h * hd + e8 * 8;
+    bf16_t* dst = (isv ? vc : kc) + (((size_t)b * kvh + h) * cap + slot0 + s) * hd + e8 * 8;
+    *reinterpret_cast<u32x4*>(dst) = *reinterpret_cast<const u32x4*>(src);
+}
+
+constexpr int AD_HD = 128;
+constexpr int AD_REC = 132;          // floats per (sequence, head, chunk) partial: max, sum, 2 pad, accumulator [128]
+constexpr int AD_CMAX = 256, AD_CMIN = 64;
+constexpr int AD_TARGET_WGS = 1024;
+
+static int attn_decode_chunk(int B, int kvh, int len) {
+    int C = AD_CMAX;
+    while (C > AD_CMIN && (long)B * kvh * ((len + C - 1) / C) < AD_TARGET_WGS) C /= 2;
+    return C;
+}
+
+// grid (chunk, kv head, sequence), 256 threads.  Scores in the log2 domain (scale * log2 e folded into q . k).
+template <int G>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ kc,
+                                                          const bf16_t* __restrict__ vc, const int* __restrict__ key_mask,
+                                                          float* __restrict__ ws, int kvh, int cap, int len, int C, int nchunks,
+                                                          float sl2) {
+    __shared__ float sc[G][AD_CMAX];
+    __shared__ float red[4][G][AD_HD];
+    const int c = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, d0 = (lane & 15) * 8;
+    const int j0 = c * C;
+    const bf16_t* kbase = kc + ((size_t)b * kvh + hk) * cap * AD_HD;
+    const bf16_t* vbase = vc + ((size_t)b * kvh + hk) * cap * AD_HD;
+    const int* km = key_mask + (size_t)b * cap;
+    float qf[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g) unpack8(*reinterpret_cast<const u32x4*>(q + (size_t)b * ldq + (size_t)(hk * G + g) * AD_HD + d0), qf[g]);
+    // ---- scores: 16 lanes per key (8 dims each), 4 keys per wave-instruction, 4 keys in flight per lane
+    for (int i0 = wv * 4 + (lane >> 4); i0 < C; i0 += 64) {
+        u32x4 kr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + i0 + 16 * u;
+            kr[u] = j < len ? *reinterpret_cast<const u32x4*>(kbase + (size_t)j * AD_HD + d0) : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float kf[8];
+            unpack8(kr[u], kf);
+            const int i = i0 + 16 * u, j = j0 + i;
+            const bool valid = j < len && km[j] != 0;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                float s = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += qf[g][e] * kf[e];
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                if ((lane & 15) == 0) sc[g][i] = valid ? s * sl2 : -INFINITY;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- chunk softmax statistics: wave g % 4 owns query head g
+    float* rec = ws + (((size_t)b * kvh + hk) * nchunks + c) * G * AD_REC;
+    for (int g = wv; g < G; g += 4) {
+        float mx = -INFINITY;
+        for (int i = lane; i < C; i += 64) mx = fmaxf(mx, sc[g][i]);
+        mx = wave_max(mx);
+        float l = 0.f;
+        for (int i = lane; i < C; i += 64) {
+            const float pr = mx == -INFINITY ? 0.f : exp2f(sc[g][i] - mx);
+            sc[g][i] = pr;
+            l += pr;
+        }
+        l = wave_sum(l);
+        if (lane == 0) { rec[g * AD_REC] = mx; rec[g * AD_REC + 1] = l; }
+    }
+    __syncthreads();
+    // ---- P V: 16 lanes per key (8 dims each), 16 key groups; keys whose probabilities are all zero are skipped (masked, or beyond len)
+    float o[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+    const int kg = threadIdx.x >> 4;
+    for (int i0 = kg; i0 < C; i0 += 64) {
+        u32x4 vr[4];
+        bool use[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + 16 * u;
+            bool any = false;
+#pragma unroll
+            for (int g = 0; g < G; ++g) any |= sc[g][i] != 0.f;
+            use[u] = any && j0 + i < len;
+            vr[u] = use[u] ? *reinterpret_cast<const u32x4*>(vbase + (size_t)(j0 + i) * AD_HD + d0) : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (!use[u]) continue;
+            float vf[8];
+            unpack8(vr[u], vf);
+            const int i = i0 + 16 * u;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float pr = sc[g][i];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[g][e] += pr * vf[e];
+            }
+        }
+    }
+    // the 4 key groups of a wave (lane bits 4, 5), then the 4 waves through LDS in wave order
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float x = o[g][e];
+            x += __shfl_xor(x, 16);
+            x += __shfl_xor(x, 32);
+            o[g][e] = x;
+        }
+    if (lane < 16)
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[wv][g][d0 + e] = o[g][e];
+    __syncthreads();
+    for (int t = threadIdx.x; t < G * AD_HD; t += 256) {
+        const int g = t / AD_HD, d = t % AD_HD;
+        rec[g * AD_REC + 4 + d] = ((red[0][g][d] + red[1][g][d]) + red[2][g][d]) + red[3][g][d];
+    }
+}
+
+// grid (heads, batch), 128 threads = one per feature; chunks folded in order
+__global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* __restrict__ ws, bf16_t* __restrict__ o, int ldo, int heads,
+                                                                  int kvh, int nchunks) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    const int G = heads / kvh, hk = h / G, g = h % G;
+    const float* base = ws + ((size_t)b * kvh + hk) * nchunks * G * AD_REC + (size_t)g * AD_REC;
+    float mx = -INFINITY;
+    for (int c = 0; c < nchunks; ++c) mx = fmaxf(mx, base[(size_t)c * G * AD_REC]);
+    float l = 0.f, acc = 0.f;
+    if (mx != -INFINITY)
+        for (int c = 0; c < nchunks; ++c) {
+            const float* rc = base + (size_t)c * G * AD_REC;
+            const float m = rc[0];
+            if (m == -INFINITY) continue;
+            const float w = exp2f(m - mx);
+            l += w * rc[1];
+            acc += w * rc[4 + d];
+        }
+    o[(size_t)b * ldo + (size_t)h * AD_HD + d] = f32_to_bf16(l > 0.f ? acc / l : 0.f);
+}
+
+extern "C" long vlr_gemv_workspace_bytes(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 8) return 0;
+    return (long)gemv_splits(N, K) * (M > 16 ? 16 : M) * N * 4;
+}
+
+extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
+                             int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
+                             int M, int N, int K, void* workspace, vlr_stream_t st) {
+    VLR_REQUIRE(mode >= VLR_GEMV_BF16 && mode <= VLR_GEMV_SWIGLU, "vlr_gemv_bf16: unknown mode %d", mode);
+    VLR_REQUIRE(X && W && Y && workspace, "vlr_gemv_bf16: null argument");
+    VLR_REQUIRE(M >= 1 && M <= 16, "vlr_gemv_bf16: M = %d rows, the skinny GEMM takes 1 <= M <= 16", M);
+    VLR_REQUIRE(K >= 8 && K % 8 == 0, "vlr_gemv_bf16: K = %d must be a positive multiple of 8", K);
+    VLR_REQUIRE(N >= 1 && ldx >= K && ldx % 8 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0,
+                "vlr_gemv_bf16: N %d, ldx %d (>= K, multiple of 8) and 16-byte aligned X / W required", N, ldx);
+    const int ncols = mode == VLR_GEMV_SWIGLU ? N / 2 : N;
+    VLR_REQUIRE(ldy >= ncols, "vlr_gemv_bf16: ldy %d < output columns %d", ldy, ncols);
+    VLR_REQUIRE(mode != VLR_GEMV_SWIGLU || N % 2 == 0, "vlr_gemv_bf16: gate|up needs an even N (got %d)", N);
+    VLR_REQUIRE(mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32RES || !residual, "vlr_gemv_bf16: mode %d takes no residual", mode);
+    VLR_REQUIRE(!residual || ldr >= N, "vlr_gemv_bf16: ldr %d < N %d", ldr, N);
+    VLR_REQUIRE(!bias || mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32 || mode == VLR_GEMV_QKV_ROPE, "vlr_gemv_bf16: mode %d takes no bias", mode);
+    if (mode == VLR_GEMV_QKV_ROPE)
+        VLR_REQUIRE(pos && cos_t && sin_t && head_dim >= 16 && head_dim % 16 == 0 && rope_cols % head_dim == 0 && rope_cols >= 0 &&
+                        rope_cols <= N && max_pos > 0,
+                    "vlr_gemv_bf16: RoPE needs pos / cos / sin tables, head_dim %d (multiple of 16), rope_cols %d (multiple of head_dim, <= N %d)",
+                    head_dim, rope_cols, N);
+    const int S = gemv_splits(N, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    hipLaunchKernelGGL(gemv_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
+                       (float*)workspace, M, N, K, cps);
+    GemvEpi p{mode, (const float*)workspace, S, M, N, Y, ldy, (const bf16_t*)bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
+              head_dim, max_pos};
+    const int units = mode == VLR_GEMV_SWIGLU ? N / 2 : (mode == VLR_GEMV_QKV_ROPE ? N - rope_cols / 2 : N);
+    hipLaunchKernelGGL(gemv_epilogue_kernel, dim3((M * units + 255) / 256), dim3(256), 0, st, p, units);
+    return vlr_check_launch("vlr_gemv_bf16");
+}
+
+extern "C" int vlr_kv_cache_write(const void* k, const void* v, int ld, void* k_cache, void* v_cache, int batch, int S, int kv_heads,
+                                  int head_dim, int cap, int slot0, vlr_stream_t st) {
+    VLR_REQUIRE(k && v && k_cache && v_cache, "vlr_kv_cache_write: null argument");
+    VLR_REQUIRE(batch >= 1 && S >= 1 && kv_heads >= 1 && head_dim >= 8 && head_dim % 8 == 0 && ld % 8 == 0 && ld >= kv_heads * head_dim,
+                "vlr_kv_cache_write: bad shape (batch %d, S %d, kv_heads %d, head_dim %d, ld %d)", batch, S, kv_heads, head_dim, ld);
+    VLR_REQUIRE(slot0 >= 0 && slot0 + S <= cap, "vlr_kv_cache_write: columns %d .. %d outside the cache capacity %d", slot0, slot0 + S - 1, cap);
+    VLR_REQUIRE((((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0,
+                "vlr_kv_cache_write: pointers must be 16-byte aligned");
+    const long per = (long)batch * S * kv_heads * (head_dim / 8);
+    hipLaunchKernelGGL(kv_cache_write_kernel, dim3((unsigned)((2 * per + 255) / 256)), dim3(256), 0, st, (const bf16_t*)k,
+                       (const bf16_t*)v, ld, (bf16_t*)k_cache, (bf16_t*)v_cache, S, kv_heads, head_dim, cap, slot0, per);
+    return vlr_check_launch("vlr_kv_cache_write");
+}
+
+extern "C" long vlr_attn_decode_workspace_bytes(int batch, int heads, int cap) {
+    if (batch < 1 || heads < 1 || cap < 1) return 0;
+    return (long)batch * heads * ((cap + AD_CMIN - 1) / AD_CMIN) * AD_REC * 4;
+}
+
+extern "C" int vlr_attn_decode_gqa(const void* q, int ldq, const void* k_cache, const void* v_cache, const int* key_mask, void* o, int ldo,
+                                   void* workspace, int batch, int heads, int kv_heads, int head_dim, int cap, int len, float scale,
+                                   vlr_stream_t st) {
+    VLR_REQUIRE(q && k_cache && v_cache && key_mask && o && workspace, "vlr_attn_decode_gqa: null argument");
+    VLR_REQUIRE(head_dim == AD_HD, "vlr_attn_decode_gqa: head_dim %d unsupported (the decode kernel takes head_dim 128)", head_dim);
+    VLR_REQUIRE(batch >= 1 && kv_heads >= 1 && heads % kv_heads == 0, "vlr_attn_decode_gqa: heads %d is not a multiple of kv_heads %d",
+                heads, kv_heads);
+    const int G = heads / kv_heads;
+    VLR_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "vlr_attn_decode_gqa: heads / kv_heads = %d (1, 2, 4 or 8 supported)", G);
+    VLR_REQUIRE(len >= 1 && len <= cap, "vlr_attn_decode_gqa: len %d outside 1 .. cap %d", len, cap);
+    VLR_REQUIRE(ldq % 8 == 0 && ldq >= heads * head_dim && ldo >= heads * head_dim, "vlr_attn_decode_gqa: ldq %d / ldo %d too small or ldq not a multiple of 8", ldq, ldo);
+    const int C = attn_decode_chunk(batch, kv_heads, len), nchunks = (len + C - 1) / C;
+    const float sl2 = scale * 1.4426950408889634f;
+    const dim3 grid(nchunks, kv_heads, batch);
+#define AD_LAUNCH(GG)                                                                                                               \
+    hipLaunchKernelGGL(attn_decode_kernel<GG>, grid, dim3(256), 0, st, (const bf16_t*)q, ldq, (const bf16_t*)k_cache,             \
+                       (const bf16_t*)v_cache, key_mask, (float*)workspace, kv_heads, cap, len, C, nchunks, sl2)
+    switch (G) {
+        case 1: AD_LAUNCH(1); break;
+        case 2: AD_LAUNCH(2); break;
+        case 4: AD_LAUNCH(4); break;
+        default: AD_LAUNCH(8); break;
+    }
+#undef AD_LAUNCH
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(heads, batch), dim3(AD_HD), 0, st, (const float*)workspace, (bf16_t*)o, ldo, heads,
+                       kv_heads, nchunks);
+    return vlr_check_launch("vlr_attn_decode_gqa");
+}

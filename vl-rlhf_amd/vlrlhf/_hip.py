@@ -46,6 +46,11 @@ class LoraBcomb(C.Structure):      # vlr_lora_bcomb: the groups' [B_lora | B_plo
     _fields_ = [(n, P) for n in ("qkv", "o", "gu", "down")]
 
 
+class DecodeWs(C.Structure):      # vlr_decode_ws: scratch of vlr_decoder_layer_decode (one new token per sequence)
+    _fields_ = [("xn", P), ("rstd", P), ("qkv", P), ("attn", P), ("act", P), ("gemv_ws", P), ("gemv_ws_bytes", L), ("attn_ws", P),
+                ("attn_ws_bytes", L)]
+
+
 class VitCfg(C.Structure):
     _fields_ = [("hidden", I), ("mlp", I), ("heads", I), ("head_dim", I), ("ln_eps", F), ("act", I), ("head_dim_pad", I), ("attn_scale", F)]
 
@@ -147,7 +152,13 @@ _SIGS = {
     "vlr_layers_join": [P],
     "vlr_allreduce_bucket": [P, P, L, I, P],
     "vlr_comm_probe": [P, P, L, I, P],
+    # decoding with a KV cache (include/vlr.h "decoding")
+    "vlr_gemv_bf16": [I, P, I, P, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P],
+    "vlr_kv_cache_write": [P, P, I, P, P, I, I, I, I, I, I, P],
+    "vlr_attn_decode_gqa": [P, I, P, P, P, P, I, P, I, I, I, I, I, I, F, P],
+    "vlr_decoder_layer_decode": [P, P, P, P, P, P, P, P, I, I, I, P],
 }
+GEMV_BF16, GEMV_F32, GEMV_F32RES, GEMV_QKV_ROPE, GEMV_SWIGLU = range(5)      # vlr_gemv_bf16 modes
 _INT_HELPERS = {
     "vlr_rmsnorm_bwd_workspace_bytes": [I],
     "vlr_layernorm_bwd_workspace_bytes": [I],
@@ -172,6 +183,9 @@ _INT_HELPERS = {
 }
 
 
+_LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes"]      # (int, int, int) -> long
+
+
 class VlrError(RuntimeError):
     pass
 
@@ -194,6 +208,12 @@ def lib():
         l.vlr_lora_mask_bytes.argtypes = [I, I, I]
         l.vlr_dropout_bits_kt_bytes.restype = C.c_long
         l.vlr_dropout_bits_kt_bytes.argtypes = [I, I]
+        for name in _LONG_HELPERS:
+            if os.environ.get("VLR_LIB") and not hasattr(l, name):
+                continue
+            fn = getattr(l, name)
+            fn.restype = C.c_long
+            fn.argtypes = [I, I, I]
         for name, sig in _SIGS.items():
             if os.environ.get("VLR_LIB") and not hasattr(l, name):      # A/B against an older build of the library: newer entries may be absent
                 continue
@@ -211,7 +231,7 @@ def lib():
 
 
 def exported_symbols():
-    return list(_SIGS) + list(_INT_HELPERS) + ["vlr_last_error", "vlr_comm_library", "vlr_lmhead_workspace_bytes", "vlr_lora_mask_bytes", "vlr_dropout_bits_kt_bytes"]
+    return list(_SIGS) + list(_INT_HELPERS) + ["vlr_last_error", "vlr_comm_library", "vlr_lmhead_workspace_bytes", "vlr_lora_mask_bytes", "vlr_dropout_bits_kt_bytes"] + _LONG_HELPERS
 
 
 def ptr(t):

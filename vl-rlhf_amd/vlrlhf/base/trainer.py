@@ -853,8 +853,9 @@ class VLDPOTrainer:
     def get_batch_samples(self, model, batch):
         """reference base/trainer.py:310-360: sample a continuation of every prompt from the policy and from the reference (the batch's
         `reference_output`, else the reference model, else the policy with its adapters disabled), pad to max_length, decode.
-        Evaluation-time only (`generate_during_eval`; the reference CLI never switches it on): `model.generate` re-runs the HIP forward
-        per token, no KV cache."""
+        Evaluation-time only (`generate_during_eval`; the reference CLI never switches it on): `model.generate` decodes with its KV cache
+        where the model has one (LLaVA-1.5 / LLaVA-Next: one prefill, then one decode step per token) and re-runs the HIP forward per
+        token otherwise."""
         others = dict(batch.get("img_input_dict", {}))
         kw = dict(input_ids=batch["prompt_input_ids"], attention_mask=batch["prompt_attention_mask"], max_length=self.max_length,
                   do_sample=True, pad_token_id=self.tokenizer.pad_token_id, **others)

@@ -316,11 +316,71 @@ class VisionWeights:
                 "ln1_w", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2"))))
 
 
+class KVCache:
+    """Per-layer K / V cache of `generate` with use_cache (transformers DynamicCache): k, v [L][B][kv_heads][cap][head_dim] bf16 (post-RoPE,
+    written by the prefill - LlavaHipEngine.forward_hidden(kv_cache=...) - and one column per decode step), key_mask [B][cap] int32
+    (0 = padded key, the merge's convention), `len` = filled columns (the same for every row), `pos` [B] int32 = each row's NEXT position.
+
+    Positions follow the merge (cumsum(mask) - 1 on the attended rows), so a new token's position is the number of attended columns of
+    its row.  The buffers are allocated by `reserve(S)` once the prompt's merged length S is known: capacity = S + `new_tokens`."""
+
+    def __init__(self, layers, batch, kv_heads, head_dim, new_tokens, device="cuda"):
+        self.L, self.B, self.kv_heads, self.head_dim = int(layers), int(batch), int(kv_heads), int(head_dim)
+        self.new_tokens = int(new_tokens)
+        self.device = torch.device(device)
+        self.cap = 0
+        self.len = 0
+        self.k = self.v = self.key_mask = self.pos = None
+
+    @staticmethod
+    def capacity(prompt_len, new_tokens):
+        """columns the cache needs: the merged prompt plus one per new token"""
+        return int(prompt_len) + int(new_tokens)
+
+    @staticmethod
+    def next_positions(key_mask, length=None):
+        """[B] int32: position of the token each row appends next = attended columns among the first `length`"""
+        m = key_mask if length is None else key_mask[:, :length]
+        return (m != 0).sum(1).to(torch.int32)
+
+    def reserve(self, prompt_len, alloc=True):
+        self.cap = self.capacity(prompt_len, self.new_tokens)
+        self.len = 0
+        self.key_mask = torch.zeros(self.B, self.cap, dtype=torch.int32, device=self.device)
+        self.pos = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        if alloc:
+            shape = (self.L, self.B, self.kv_heads, self.cap, self.head_dim)
+            self.k = torch.empty(shape, dtype=BF16, device=self.device)
+            self.v = torch.empty(shape, dtype=BF16, device=self.device)
+        return self.cap
+
+    def start(self, mask):
+        """the prefill filled columns [0, S) with the merged rows of attention mask `mask` [B][S]"""
+        S = mask.shape[1]
+        if S > self.cap:
+            raise ValueError(f"KV cache: prompt of {S} merged rows exceeds the capacity {self.cap}")
+        self.key_mask[:, :S] = mask.to(device=self.key_mask.device, dtype=torch.int32)
+        self.len = S
+        self.pos = self.next_positions(self.key_mask, S)
+
+    def open_column(self):
+        """marks column `len` (the token of the coming decode step) as attended in every row; -> that column"""
+        if self.len >= self.cap:
+            raise ValueError(f"KV cache full: {self.len} of {self.cap} columns filled")
+        self.key_mask[:, self.len] = 1
+        return self.len
+
+    def advance(self):
+        self.len += 1
+        self.pos += 1
+
+
 class LlavaHipEngine:
     custom_layers = False          # True: the subclass composes the decoder layer itself (_layer_forward / _hidden_backward_custom)
     supports_resid_f32 = True      # False: the subclass adds to the residual stream with bf16 primitives
     supports_ckpt = True           # False: the subclass's backward cannot re-run a layer's forward (gradient checkpointing is ignored)
     proj_out_f32 = True            # with the fp32 stream the projector writes fp32 rows for the merge (VLR_PROJ_F32=0: bf16)
+    supports_kv_cache = True       # generate(use_cache=True): prefill into a KVCache + decode_step (vlr_decoder_layer_decode)
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
         if not torch.cuda.is_available():
@@ -743,9 +803,10 @@ class LlavaHipEngine:
                     proj_z=z, proj_h=h, n_rows=n_rows, n_feat=n_feat, pack=pack)
 
     def forward_hidden(self, ws: WeightSet, input_ids, attention_mask, labels, pixel_values, image_dup=1, save=False,
-                       tag="ref", image_sizes=None):
+                       tag="ref", image_sizes=None, kv_cache: Optional[KVCache] = None):
         """embed -> ViT -> projector -> merge -> decoder -> final RMSNorm.  Returns a context dict with the final
-        hidden states [Bn*S, H] and the merged labels / mask / positions."""
+        hidden states [Bn*S, H] and the merged labels / mask / positions.  kv_cache (generate's prefill, no-grad, engines with
+        supports_kv_cache): each layer's post-RoPE K / V rows are copied into it right after the layer ran."""
         c = self.cfg
         if ws is self.policy:
             self.wait_optimizer()
@@ -759,6 +820,10 @@ class LlavaHipEngine:
         e["grad_pass"] = bool(save)  # this pass will be back-propagated (training-mode dropout applies; a checkpointed forward included)
         S, M = e["S"], e["M"]
         src, mask, pos, mlabels, img_map, inv = e["src"], e["mask"], e["pos"], e["labels"], e["img_map"], e["inv"]
+        if kv_cache is not None:
+            if save or not self.supports_kv_cache:
+                raise ValueError("forward_hidden: kv_cache needs a no-grad pass of an engine with supports_kv_cache")
+            kv_cache.reserve(S)
         feats, vit_feat, z, h, n_rows, n_feat, pack = e["feats"], e["vit_feat"], e["proj_z"], e["proj_h"], e["n_rows"], e["n_feat"], e["pack"]
         if self.resid_f32:                 # fp32 stream: embedding rows widened exactly, the projector's output rows unrounded (fp32 feats)
             x0 = self._buf((tag, "x0f", Bn, S), (M, self.H), torch.float32)
@@ -781,16 +846,77 @@ class LlavaHipEngine:
                 a = self._layer_acts(tag if save else tag + "/scratch", l if save else (l % 2), Bn, S)   # scratch per pass tag (side stream)
             # checkpointing: this pass keeps x_out only - what the backward reads is written by the recompute (hidden_backward)
             self._layer_fwd_call(ws, l, a, x, e, Bn, S, save and not ckpt, use_lora, lora_seed)
+            if kv_cache is not None:      # (the scratch activation sets alternate per layer: the K / V columns are taken now)
+                qkv = a["qkv"]
+                _hip.call("vlr_kv_cache_write", qkv[:, self.Nq:], qkv[:, self.Nq + self.Nkv:], self.Nqkv, kv_cache.k[l], kv_cache.v[l],
+                          Bn, S, self.nkv, self.hd, kv_cache.cap, 0)
             acts.append(a)
             x = a["x_out"]
         hidden = torch.empty(M, self.H, dtype=BF16, device=self.dev)
         rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
         self._norm_fwd(x, ws.v["norm"], hidden, rstd_f, M)
+        if kv_cache is not None:
+            kv_cache.start(mask.view(Bn, S))
         return dict(ws=ws, Bn=Bn, T=T, S=S, M=M, ids=ids, src=src, inv=inv, mask=mask, labels=mlabels, pos=pos,
                     img_map=img_map.bool(), hidden=hidden, rstd_f=rstd_f, x_last=x, x0=x0, acts=acts if save else None,
                     vit_feat=vit_feat, feats=feats, proj_z=z, proj_h=h, image_dup=image_dup, n_rows=n_rows, n_feat=n_feat,
                     pack=pack, tag=tag, lora_seed=lora_seed, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
                     embed=dict(pos=e["pos"], mask=e["mask"], extra=e.get("extra"), tag=tag, img_map=e["img_map"], plora_seed=e.get("plora_seed"), grad_pass=bool(save)))
+
+    # ------------------------------------------------------------------------------------------------ decoding
+    def new_kv_cache(self, batch, new_tokens) -> KVCache:
+        """an empty cache for `batch` sequences and `new_tokens` decode columns; the prefill (forward_hidden(kv_cache=...)) sizes it"""
+        return KVCache(self.L, batch, self.nkv, self.hd, new_tokens, self.dev)
+
+    def _gemv_rows(self, mode, X, W, Y, M, N, K, ws):
+        for m0 in range(0, M, 16):
+            mr = min(16, M - m0)
+            _hip.call("vlr_gemv_bf16", mode, X[m0:m0 + mr], X.shape[1], W, Y[m0:m0 + mr], Y.shape[1], None, None, 0, None, None, None,
+                      0, self.hd, self.max_pos, mr, N, K, ws)
+
+    def _decode_ws(self, B, cap):
+        key = ("decode_ws", B, cap)
+        d = self._ws.get(key)
+        if d is None:
+            self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
+            mb = min(B, 16)
+            gb = max(int(_hip.lib().vlr_gemv_workspace_bytes(mb, n, k)) for n, k in
+                     ((self.Nqkv, self.H), (self.H, self.Nq), (2 * self.I, self.H), (self.H, self.I), (self.V, self.H)))
+            ab = int(_hip.lib().vlr_attn_decode_workspace_bytes(B, self.nh, cap))
+            d = dict(xn=torch.empty(B, self.H, dtype=BF16, device=self.dev), rstd=torch.empty(B, dtype=torch.float32, device=self.dev),
+                     qkv=torch.empty(B, self.Nqkv, dtype=BF16, device=self.dev), attn=torch.empty(B, self.Nq, dtype=BF16, device=self.dev),
+                     act=torch.empty(B, self.I, dtype=BF16, device=self.dev), gemv=torch.empty(gb, dtype=torch.uint8, device=self.dev),
+                     attn_ws=torch.empty(ab, dtype=torch.uint8, device=self.dev), x=torch.empty(B, self.H, dtype=self.RDT, device=self.dev),
+                     xe=torch.empty(B, self.H, dtype=BF16, device=self.dev), hidden=torch.empty(B, self.H, dtype=BF16, device=self.dev))
+            d["struct"] = _hip.DecodeWs(d["xn"].data_ptr(), d["rstd"].data_ptr(), d["qkv"].data_ptr(), d["attn"].data_ptr(),
+                                        d["act"].data_ptr(), d["gemv"].data_ptr(), gb, d["attn_ws"].data_ptr(), ab)
+            self._ws[key] = d
+        return d
+
+    def decode_step(self, ws: WeightSet, tokens, cache: KVCache):
+        """One new token per sequence against the cache (transformers LlamaModel.forward with a DynamicCache, one query row):
+        embedding row gather -> L x vlr_decoder_layer_decode -> final RMSNorm -> lm-head (skinny GEMM, fp32 out).
+        tokens [B] (ids appended at column cache.len) -> logits fp32 [B][V]; the cache advances by one column."""
+        if not self.supports_kv_cache:
+            raise ValueError(f"{type(self).__name__} has no KV-cache decoding")
+        B, H = cache.B, self.H
+        d = self._decode_ws(B, cache.cap)
+        tok = tokens.to(device=self.dev, dtype=torch.int32).contiguous()
+        length = cache.open_column()
+        x = d["x"]
+        if self.resid_f32:                 # the embedding rows widened exactly (vlr_merge_fwd_f32's rule)
+            _hip.call("vlr_gather_rows", ws.v["embed"], tok, d["xe"], B, H)
+            _hip.call("vlr_cast_bf16_to_f32", d["xe"], x, B * H)
+        else:
+            _hip.call("vlr_gather_rows", ws.v["embed"], tok, x, B, H)
+        for l in range(self.L):
+            _hip.call("vlr_decoder_layer_decode", self.llama_cfg, self.layer_weights(ws, l), d["struct"], x, cache.pos, cache.k[l],
+                      cache.v[l], cache.key_mask, B, cache.cap, length)
+        self._norm_fwd(x, ws.v["norm"], d["hidden"], d["rstd"], B)
+        logits = torch.empty(B, self.V, dtype=torch.float32, device=self.dev)
+        self._gemv_rows(_hip.GEMV_F32, d["hidden"], ws.v["lm_head"], logits, B, self.V, H, d["gemv"])
+        cache.advance()
+        return logits
 
     # ------------------------------------------------------------------------------------------------ log-probs
     def logps_forward(self, ctx, labels, shared_mask=None, average=False, label_pad=-100):

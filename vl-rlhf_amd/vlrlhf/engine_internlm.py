@@ -30,6 +30,7 @@ PLORA_SEED_XOR = 0x2A5A5A5A5A
 
 class InternLMHipEngine(LlavaHipEngine):
     custom_layers = True
+    supports_kv_cache = False      # the PLoRA layers are composed per pass (image rows): generate re-runs the forward
     vision_prefix = "vit.vision_tower."
 
     @property

@@ -95,6 +95,7 @@ class QwenVisionWeights:
 
 class QwenVLHipEngine(LlavaHipEngine):
     vision_prefix = "transformer.visual."
+    supports_kv_cache = False      # generation inputs (image ids inside the text) not wired to the cache yet: generate re-runs the forward
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
         c = dict(cfg, family="qwen_vl")

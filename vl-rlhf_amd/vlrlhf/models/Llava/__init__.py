@@ -404,17 +404,24 @@ class LlavaForRL(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_length=None, max_new_tokens=None, do_sample=False, temperature=1.0,
-                 top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, **img):
+                 top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True, **img):
         """What the reference trainer's `get_batch_samples` calls (base/trainer.py:310-360: `model.generate(input_ids, attention_mask,
         max_length, do_sample=True, pad_token_id, **img_input_dict)`, transformers GenerationMixin defaults: temperature 1, top_k 50,
-        top_p 1).  Evaluation-time sampling only and outside the DPO step, so there is NO KV cache: every new token re-runs the forward
-        of the whole sequence on the HIP path (the vision features of the batch are cached by the engine) and the lm-head is evaluated
-        on the last row of each sequence alone.  Prompts are LEFT-padded (trl's collator; the merge of the reference end-aligns such
-        rows); the running batch is left-padded further to a multiple of 32 tokens so that the engine sees a new shape every 32 steps,
-        not every step.  Finished rows keep receiving `pad_token_id` as in transformers.  Returns prompt + continuation ids."""
+        top_p 1, use_cache True).  Prompts are LEFT-padded (trl's collator; the merge of the reference end-aligns such rows) and padded
+        further to a multiple of 32 tokens.  Finished rows keep receiving `pad_token_id` as in transformers.  Returns prompt +
+        continuation ids.
+
+        use_cache=True (engines with supports_kv_cache: LLaVA-1.5, LLaVA-Next): ONE prefill of the prompt fills a per-layer K / V cache
+        (engine.forward_hidden(kv_cache=...)), then every new token is one decode step (engine.decode_step: skinny GEMMs and
+        split-KV attention over the cache).  The first token's logits are those of the re-forward loop bit for bit (same prefill, same
+        lm-head call); later ones differ by the decode kernels' rounding.  With active LoRA adapters both run on the merged weights
+        (computed once per call).  use_cache=False, or an engine without the cache (Qwen-VL, InternLM-XComposer2): every new token
+        re-runs the forward of the whole sequence (the vision features of the batch are cached by the engine), the running batch
+        left-padded to a multiple of 32 tokens so that the engine sees a new shape every 32 steps, not every step."""
         if generation_config is not None:
             max_new_tokens = max_new_tokens if max_new_tokens is not None else getattr(generation_config, "max_new_tokens", None)
             do_sample = bool(getattr(generation_config, "do_sample", do_sample))
+            use_cache = bool(getattr(generation_config, "use_cache", use_cache))
         if input_ids is None:
             raise ValueError("generate needs input_ids")
         dev = self.engine.dev
@@ -435,6 +442,11 @@ class LlavaForRL(nn.Module):
         self.eval()
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         lm_head = self.weights.v["lm_head"]
+        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
+            try:
+                return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img)
+            finally:
+                self.train(was_training)
         try:
             while ids.shape[1] < limit and bool(unfinished.any()):
                 T = ids.shape[1]
@@ -445,16 +457,7 @@ class LlavaForRL(nn.Module):
                 else:
                     run_ids, run_mask = ids, mask
                 out = self(input_ids=run_ids, attention_mask=run_mask, labels=None, use_cache=False, **img)
-                c = out.logits.c
-                S, H = c["S"], self.engine.H
-                valid = c["mask"].view(B, S) != 0
-                last = S - 1 - torch.flip(valid, dims=[1]).float().argmax(1)           # last attended position of every row
-                rows = max(8, B)
-                h_last = torch.zeros(rows, H, dtype=torch.bfloat16, device=dev)
-                h_last[:B] = c["hidden"].view(B, S, H)[torch.arange(B, device=dev), last]
-                logits = torch.empty(rows, self.engine.V, dtype=torch.float32, device=dev)
-                _hip.call("vlr_gemm_bf16", 0, h_last, lm_head, logits, None, None, rows, self.engine.V, H, H, H, self.engine.V, 0, 0, 0, 1)
-                logits = logits[:B]
+                logits = self._last_logits(out.logits.c, B, lm_head)
                 if do_sample:
                     nxt = torch.multinomial(sampling_filter(logits, temperature, top_k, top_p).softmax(-1), 1, generator=generator).squeeze(1)
                 else:
@@ -467,6 +470,65 @@ class LlavaForRL(nn.Module):
         finally:
             self.train(was_training)
         return ids
+
+    def _last_logits(self, c, B, lm_head):
+        """fp32 logits [B][V] of the last attended merged row of every sequence (vlr_gemm_bf16 on at least 8 rows)"""
+        dev, H = self.engine.dev, self.engine.H
+        S = c["S"]
+        valid = c["mask"].view(B, S) != 0
+        last = S - 1 - torch.flip(valid, dims=[1]).float().argmax(1)           # last attended position of every row
+        rows = max(8, B)
+        h_last = torch.zeros(rows, H, dtype=torch.bfloat16, device=dev)
+        h_last[:B] = c["hidden"].view(B, S, H)[torch.arange(B, device=dev), last]
+        logits = torch.empty(rows, self.engine.V, dtype=torch.float32, device=dev)
+        _hip.call("vlr_gemm_bf16", 0, h_last, lm_head, logits, None, None, rows, self.engine.V, H, H, H, self.engine.V, 0, 0, 0, 1)
+        return logits[:B]
+
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img):
+        """generate's KV-cache path: the prefill is the first iteration of the re-forward loop (same padded input, same lm-head
+        call) with the K / V rows kept; each further token is one engine.decode_step."""
+        eng, dev = self.engine, self.engine.dev
+        B, T = ids.shape
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        if T >= limit:
+            return ids
+        ws = self.weights
+        if ws is eng.policy:
+            eng.wait_optimizer()
+            if eng.lora is not None and eng.lora_active:
+                ws = eng.merged_weights()          # peft merge: the adapters folded in once for the whole call
+        Tp = (T + 31) // 32 * 32
+        if Tp != T:                   # left padding: masked out, and the merged rows stay end-aligned
+            fill = torch.full((B, Tp - T), pad, dtype=ids.dtype, device=dev)
+            run_ids, run_mask = torch.cat([fill, ids], 1), torch.cat([torch.zeros_like(fill), mask], 1)
+        else:
+            run_ids, run_mask = ids, mask
+        pv = img.get("pixel_values")
+        if pv is None:
+            raise ValueError("generate on the MI355X path needs pixel_values")
+        if eng.anyres and img.get("image_sizes") is None:
+            raise ValueError("LLaVA-Next generate needs image_sizes (reference LlavaNext/__init__.py:216-222)")
+        cache = eng.new_kv_cache(B, limit - T)
+        c = eng.forward_hidden(ws, run_ids, run_mask, None, pv, image_dup=int(getattr(pv, "_vlr_dup", 1)), save=False,
+                               tag="policy_ng" if self.weights is eng.policy else "ref", image_sizes=img.get("image_sizes"),
+                               kv_cache=cache)
+        logits = self._last_logits(c, B, ws.v["lm_head"])
+        out = [ids]
+        n = T
+        while True:
+            if do_sample:
+                nxt = torch.multinomial(sampling_filter(logits, temperature, top_k, top_p).softmax(-1), 1, generator=generator).squeeze(1)
+            else:
+                nxt = logits.argmax(-1)
+            nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
+            out.append(nxt[:, None].to(ids.dtype))
+            n += 1
+            for e in eos:
+                unfinished = unfinished & (nxt != e)
+            if n >= limit or not bool(unfinished.any()):
+                break
+            logits = eng.decode_step(ws, nxt, cache)
+        return torch.cat(out, 1)
 
     def zero_grad(self, set_to_none: bool = True):
         self.engine.zero_grad()
