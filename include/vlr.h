@@ -303,6 +303,27 @@ int vlr_lmhead_logps_bwd(const void* hg, const void* w_lm, const int* tgt, const
                          const float* dlogps, int average, void* dlogits, void* workspace, float* logits_ws, int R, int V, int H,
                          vlr_stream_t stream);
 
+/* ---- supervised fine-tuning: the causal-LM cross-entropy `loss` of the model wrappers' forward(labels=...) (reference
+ *      Llava/__init__.py:246-257, LlavaNext/__init__.py:322-331, modeling_qwen.py:839-842, InternLMXC2/__init__.py:211-219) = the mean of
+ *      -log p(label) over the selected rows of the WHOLE batch, on the tok_logp / lse of vlr_lmhead_logps_fwd.
+ * vlr_ce_mean_fwd: out3 = {loss = -sum_r tok_logp[r] / R, R, -1/R}.  Per-block partials, then one fold, in an order that depends on R
+ *      only and without atomics: two calls are bit-equal.  workspace: vlr_ce_mean_workspace_bytes().
+ * vlr_lmhead_ce_bwd: d hg [R][H] bf16 and (dw_lm != NULL) d W_lm [V][H] bf16 (+= when dw_accumulate) for the uniform row gradient
+ *      *coef (device scalar: upstream gradient x out3[2]).  The rows are walked in blocks of at most `row_block` rows (<= 0: the
+ *      default, vlr_lmhead_ce_row_block: the largest multiple of 256 that keeps the block's workspace under 1 GiB) - per block
+ *      vlr_lmhead_logps_bwd into `dlogits` [row_block][V] bf16, then the dgrad and wgrad GEMMs.  `workspace`:
+ *      vlr_lmhead_workspace_bytes(row_block, V); `logits_ws` fp32 [rows][V] for every block size that is not vlr_lmhead_is_fused.
+ *      d hg is computed row by row from operands of that row alone, so it is bit-identical for every block size as long as the blocks
+ *      reach the same GEMM kernels (the dispatcher picks tiles by the row count).  d W_lm is NOT: it sums over the rows, each block's
+ *      product is rounded to bf16 when it is added to the gradient buffer, in block order - deterministic for a given row_block,
+ *      equal to the single-block result only to bf16 rounding. */
+int vlr_ce_mean_workspace_bytes(void);
+int vlr_ce_mean_fwd(const float* tok_logp, int R, void* workspace, float* out3, vlr_stream_t stream);
+int vlr_lmhead_ce_row_block(int R, int V, int H);
+int vlr_lmhead_ce_bwd(const void* hg, const void* w_lm, const int* tgt, const float* lse, const float* coef, void* dlogits,
+                      void* workspace, float* logits_ws, void* dhg, void* dw_lm, int dw_accumulate, int R, int V, int H, int row_block,
+                      vlr_stream_t stream);
+
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d
  * policy_{chosen,rejected}_logps with g = grad_losses or 1/len(losses) when NULL (trl: loss = losses.mean()). */

@@ -108,6 +108,8 @@ _SIGS = {
     "vlr_seq_sum": [P, P, I, I, P, P],
     "vlr_lmhead_logps_fwd": [P, P, P, P, P, P, P, I, I, I, P],
     "vlr_lmhead_logps_bwd": [P, P, P, P, P, I, P, I, P, P, P, I, I, I, P],
+    "vlr_ce_mean_fwd": [P, I, P, P, P],
+    "vlr_lmhead_ce_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vlr_dpo_loss": [P, P, P, P, I, F, F, I, I, P, P, P, P, P, P, P, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
@@ -173,6 +175,8 @@ _INT_HELPERS = {
     "vlr_set_comm_cus": [I],
     "vlr_compute_cus": [],
     "vlr_lmhead_is_fused": [I, I, I],
+    "vlr_ce_mean_workspace_bytes": [],
+    "vlr_lmhead_ce_row_block": [I, I, I],
     "vlr_comm_unique_id_bytes": [],
     "vlr_comm_unique_id": [P],
     "vlr_comm_init": [P, I, I, P],

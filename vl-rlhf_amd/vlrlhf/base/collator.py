@@ -1,4 +1,4 @@
-"""DPO collator (mirror of /root/reference/src/vlrlhf/base/collator.py:8-68)."""
+"""DPO and SFT collators (mirror of the reference src/vlrlhf/base/collator.py:8-94)."""
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
@@ -44,4 +44,36 @@ class VLDPODataCollatorWithPadding:
                 out[k] = torch.tensor([f[k] for f in features])
             else:
                 out[k] = [f[k] for f in features]
+        return out
+
+
+@dataclass
+class VLSFTDataCollatorWithPadding:
+    r"""reference :70-94: right-pads input_ids -> pad_token_id, labels -> label_pad_token_id, attention_mask -> 0 (the padding of
+    torch pad_sequence(batch_first=True)); `img_path` is passed through as a list; any other key raises."""
+
+    pad_token_id: int
+    label_pad_token_id: int
+    processor: Optional[Any] = None
+
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        out: Dict[str, Any] = {}
+        for k in features[0].keys():
+            if k == "img_path":
+                out[k] = [f[k] for f in features]
+                continue
+            if k == "input_ids":
+                pad = self.pad_token_id
+            elif k == "labels":
+                pad = self.label_pad_token_id
+            elif k == "attention_mask":
+                pad = 0
+            else:
+                raise ValueError(f"Unexpected key in batch '{k}'")
+            n = max(len(f[k]) for f in features)
+            t = torch.full((len(features), n), pad, dtype=torch.long)
+            for i, f in enumerate(features):
+                v = torch.as_tensor(f[k], dtype=torch.long)
+                t[i, : v.numel()] = v
+            out[k] = t
         return out

@@ -1,4 +1,4 @@
-"""VLDPOTrainer for MI355X - mirror of /root/reference/src/vlrlhf/base/trainer.py:33-360 plus the parts of
+"""VLDPOTrainer and VLSFTTrainer for MI355X - mirror of /root/reference/src/vlrlhf/base/trainer.py:33-360 plus the parts of
 trl==0.8.1 `DPOTrainer` and transformers `Trainer` the reference inherits on the DPO path (not vendored there:
 constructor bookkeeping, tokenize_row / build_tokenized_answer, concatenated_inputs, compute_loss /
 get_batch_loss_metrics, the step loop, clip + AdamW + cosine schedule).
@@ -8,6 +8,7 @@ runs in libvlr_hip.so through `vlrlhf.engine` - there is no PyTorch/CPU fallback
 reproduced: the per-micro-step `torch.cuda.empty_cache(); gc.collect()` (reference :306-307), ZeRO/DeepSpeed, wandb.
 """
 import contextlib
+import copy
 import math
 import os
 import random
@@ -99,7 +100,336 @@ class _DpoLossFn(torch.autograd.Function):
         return dpc, dpr, None, None, None, None, None, None
 
 
-class VLDPOTrainer:
+class VLTrainerLoop:
+    """The step loop shared by VLDPOTrainer and VLSFTTrainer - what both inherit from transformers.Trainer in the reference: gradient
+    accumulation, clip + AdamW + the lr schedule (engine.optimizer_step), checkpoint / resume, evaluate, logging and the RCCL reducer.
+    A subclass provides `compute_loss(model, inputs)`, `prediction_step(model, inputs)` and the attributes model / args / train_dataset /
+    eval_dataset / data_collator / accelerator / state / log_history / callbacks / is_peft_model / _stored_metrics."""
+
+    # hooks of the loop a subclass may fill (VLDPOTrainer: the reference pre-pass and pipelining, the sampled eval table)
+    def _before_train(self):
+        pass
+
+    def prefetch_reference(self, inputs):
+        return inputs
+
+    def _before_evaluate(self, ds, explicit: bool):
+        pass
+
+    def _evaluate_samples(self, rows, bs):
+        pass
+
+    def store_metrics(self, metrics, train_eval="train"):
+        for k, v in metrics.items():
+            self._stored_metrics[train_eval][k].append(v)
+
+    def log(self, logs: Dict[str, float]):
+        """trl DPOTrainer.log + HF Trainer.log: the stored metrics are averaged over the micro-steps since the last log and -
+        like the loss HF reports (`_nested_gather(tr_loss).mean()`) - over the data-parallel ranks, with ONE all-reduce of
+        the <= 9 scalars (SURVEY.md 8e).  Every rank must call log() at the same steps (they do: same step counter)."""
+        from ..parallel import all_reduce_mean_scalars
+        train_eval = "train" if "loss" in logs else "eval"
+        keys, vals = [], []
+        for k, v in self._stored_metrics[train_eval].items():
+            keys.append(k)
+            vals.append(torch.stack([torch.as_tensor(x, dtype=torch.float32, device=self.accelerator.device) for x in v]).mean())
+        for k in ("loss", "eval_loss"):
+            if k in logs:
+                keys.append(k)
+                vals.append(float(logs[k]))
+        self._stored_metrics[train_eval].clear()
+        if keys:
+            logs.update(zip(keys, all_reduce_mean_scalars(vals, device=self.accelerator.device if _world() > 1 and _backend() == "nccl" else None)))
+        logs = dict(logs, step=self.state.global_step)
+        self.log_history.append(logs)
+        if getattr(self.args, "local_rank", 0) in (0, -1) and _rank() == 0:
+            print({k: (round(v, 6) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
+        return logs
+
+    # ------------------------------------------------------------------------------------------ step + loop
+    def _prepare_inputs(self, inputs):
+        dev = self.accelerator.device
+
+        def mv(v):
+            if isinstance(v, torch.Tensor):
+                return v.to(dev, non_blocking=True)
+            if isinstance(v, dict):
+                return {k: mv(x) for k, x in v.items()}
+            return v
+        return {k: mv(v) for k, v in inputs.items()}
+
+    def training_step(self, model, inputs) -> torch.Tensor:
+        """reference base/trainer.py:303-308 + transformers Trainer.training_step: H2D, loss, backward, return
+        loss.detach() / gradient_accumulation_steps.  (No empty_cache / gc.collect: that flush serialises the device.)"""
+        model.train()
+        inputs = self._prepare_inputs(inputs)
+        loss = self.compute_loss(model, inputs)
+        ga = max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1))
+        loss.backward()
+        return loss.detach() / ga
+
+    def evaluate(self, eval_dataset=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
+        """HF Trainer.evaluate: mean eval loss (+ the metrics prediction_step stores: DPO's eight eval_ metrics) over the (rank-sharded) eval set."""
+        ds = eval_dataset if eval_dataset is not None else self.eval_dataset
+        if not ds:
+            return {}
+        self._before_evaluate(ds, eval_dataset is not None)
+        bs = int(getattr(self.args, "per_device_eval_batch_size", None) or getattr(self.args, "per_device_train_batch_size", 4))
+        # the index list is padded by wrapping to a multiple of the world size (as _train_row_batches does): every rank runs the same
+        # number of prediction steps and reduces the same 9 scalars in log() - an eval set smaller than the world would otherwise
+        # leave ranks without metrics and hang the collective (torch DistributedSampler semantics, as HF's eval dataloader)
+        rows = list(ds)
+        w = _world()
+        if w > 1 and len(rows) % w:
+            pad = (-len(rows)) % w                      # cycled: an eval set smaller than the padding still fills every rank
+            rows = rows + (rows * (pad // len(rows) + 1))[:pad]
+        rows = rows[_rank()::w]
+        was_training = self.model.training
+        self.model.eval()
+        self._evaluate_samples(rows, bs)
+        losses = []
+        for i in range(0, len(rows), bs):
+            loss, _, _ = self.prediction_step(self.model, self.data_collator(rows[i:i + bs]))
+            losses.append(loss)
+        self.model.train(was_training)
+        out = {f"{metric_key_prefix}_loss": float(torch.stack(losses).mean()) if losses else float("nan")}
+        return self.log(out)
+
+    def _train_row_batches(self, epoch: int):
+        """One epoch of this rank's row batches.  torch DistributedSampler semantics (accelerate MULTI_GPU, ddp.yaml): the
+        shuffled index list is padded by wrapping to a multiple of the world size so that EVERY rank gets the same number
+        of batches (unequal counts would dead-lock the gradient all-reduce), then strided by rank.  HF's default
+        dataloader_drop_last=False: the final partial batch is kept."""
+        bs = int(getattr(self.args, "per_device_train_batch_size", 4))
+        world, rank = _world(), _rank()
+        idx = list(range(len(self.train_dataset)))
+        random.Random(int(getattr(self.args, "seed", 42)) + epoch).shuffle(idx)
+        if world > 1 and len(idx) % world:
+            idx += idx[: world - len(idx) % world]
+        idx = idx[rank::world]
+        drop_last = bool(getattr(self.args, "dataloader_drop_last", False))
+        for i in range(0, len(idx), bs):
+            rows = idx[i:i + bs]
+            if len(rows) < bs and drop_last:
+                break
+            yield [self.train_dataset[j] for j in rows]
+
+    def _batches_per_epoch(self) -> int:
+        bs = int(getattr(self.args, "per_device_train_batch_size", 4))
+        n = -(-len(self.train_dataset) // _world())
+        return n // bs if getattr(self.args, "dataloader_drop_last", False) else -(-n // bs)
+
+    def get_train_batches(self, epoch: int, skip: int = 0):
+        """collated batches of one epoch.  The collator (image decode + CLIP preprocess) runs `dataloader_prefetch` batches
+        ahead on a background thread and the H2D copy goes through a copy stream (base/loader.py); 0 = collate inline."""
+        import itertools
+        depth = int(getattr(self.args, "dataloader_prefetch", 2) or 0)
+        rows_iter = lambda: itertools.islice(self._train_row_batches(epoch), skip, None)   # noqa: E731  (resume: skip consumed batches un-collated)
+        if depth <= 0:
+            for rows in rows_iter():
+                yield self.data_collator(rows)
+            return
+        from .loader import PrefetchLoader
+        yield from PrefetchLoader(rows_iter, self.data_collator, self.accelerator.device, depth)
+
+    def lr_at(self, step: int, total: int) -> float:
+        """transformers get_scheduler('cosine' | 'linear' | 'constant') with warmup_ratio / warmup_steps."""
+        a = self.args
+        base = float(getattr(a, "learning_rate", 5e-5))
+        warm = int(getattr(a, "warmup_steps", 0) or 0) or math.ceil(float(getattr(a, "warmup_ratio", 0.0) or 0.0) * total)
+        kind = str(getattr(a, "lr_scheduler_type", "linear")).split(".")[-1].lower()
+        if step < warm:
+            return base * step / max(1, warm)
+        prog = (step - warm) / max(1, total - warm)
+        if kind == "cosine":
+            return base * max(0.0, 0.5 * (1.0 + math.cos(math.pi * prog)))
+        if kind.startswith("constant"):
+            return base
+        return base * max(0.0, 1.0 - prog)
+
+    # ------------------------------------------------------------------------------------------ checkpoints
+    def _checkpoint_dirs(self):
+        import os
+        import re
+        out_dir = str(getattr(self.args, "output_dir", "output"))
+        if not os.path.isdir(out_dir):
+            return []
+        found = [(int(m.group(1)), os.path.join(out_dir, d)) for d in os.listdir(out_dir)
+                 if (m := re.fullmatch(r"checkpoint-(\d+)", d)) and os.path.isfile(os.path.join(out_dir, d, "trainer_state.json"))]
+        return [p for _, p in sorted(found)]
+
+    def save_checkpoint(self, step: int, micro: int, epoch: int, window_len: int = 0):
+        """HF Trainer._save_checkpoint for this path: `output_dir/checkpoint-<step>/` with the weights (adapters under LoRA),
+        the optimizer state (fp32 master / m / v + step), trainer_state.json (step counters, log history, the dropout call counters
+        that seed the counter-based masks, world size / accumulation steps the counters were taken under); rotated to
+        `save_total_limit`.  Rank 0 writes (every rank holds identical state under DDP)."""
+        import json
+        import os
+        import shutil
+        from safetensors.torch import save_file
+        if _rank() != 0:
+            return None
+        eng = self.model.engine
+        path = os.path.join(str(getattr(self.args, "output_dir", "output")), f"checkpoint-{step}")
+        tmp = path + ".tmp"
+        shutil.rmtree(tmp, ignore_errors=True)
+        os.makedirs(tmp)
+        if self.is_peft_model:
+            self.model.save_adapter(tmp)
+        else:
+            self.model.save_pretrained(tmp)
+        st = eng.optimizer_state()
+        if st is not None:
+            for k in ("master", "m", "v"):          # one file per buffer: 27 GB each at 7B full fine-tuning
+                save_file({k: st[k].detach().cpu()}, os.path.join(tmp, f"optimizer_{k}.safetensors"))
+        with open(os.path.join(tmp, "trainer_state.json"), "w") as f:
+            json.dump(dict(global_step=step, micro_step=micro, epoch=epoch, opt_step=eng.opt_step, log_history=self.log_history,
+                           world_size=_world(), lora_calls=getattr(eng, "_lora_calls", 0), plora_calls=getattr(eng, "_plora_calls", 0),
+                           gradient_accumulation_steps=max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1)),
+                           per_device_train_batch_size=int(getattr(self.args, "per_device_train_batch_size", 4))), f, indent=1)
+        shutil.rmtree(path, ignore_errors=True)
+        os.replace(tmp, path)                        # a checkpoint directory is either complete or absent
+        limit = int(getattr(self.args, "save_total_limit", 0) or 0)
+        if limit > 0:
+            for old in self._checkpoint_dirs()[:-limit]:
+                shutil.rmtree(old, ignore_errors=True)
+        return path
+
+    def load_checkpoint(self, path: str) -> dict:
+        import json
+        import os
+        from safetensors.torch import load_file
+        eng = self.model.engine
+        with open(os.path.join(path, "trainer_state.json")) as f:
+            state = json.load(f)
+        # micro_step -> (epoch, batches to skip) only means the same thing under the same sharding
+        for key, now in (("world_size", _world()), ("gradient_accumulation_steps", max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1))),
+                         ("per_device_train_batch_size", int(getattr(self.args, "per_device_train_batch_size", 4)))):
+            if key in state and int(state[key]) != now:
+                raise ValueError(f"resume_from_checkpoint: {path} was written with {key}={state[key]}, this run has {now}")
+        if self.is_peft_model:
+            self.model.load_adapter(path)
+        else:
+            sd = {}
+            for fn in sorted(os.listdir(path)):
+                if fn.startswith("model") and fn.endswith(".safetensors"):
+                    sd.update(load_file(os.path.join(path, fn)))
+            eng.policy.load_state_dict(sd)
+        if os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):
+            bufs = {k: load_file(os.path.join(path, f"optimizer_{k}.safetensors"))[k] for k in ("master", "m", "v")}
+            eng.load_optimizer_state(bufs["master"], bufs["m"], bufs["v"], state["opt_step"])
+        if hasattr(eng, "_lora_calls"):
+            eng._lora_calls = int(state.get("lora_calls", 0))
+        if hasattr(eng, "_plora_calls"):
+            eng._plora_calls = int(state.get("plora_calls", 0))
+        self.log_history = list(state.get("log_history", []))
+        return state
+
+    def train(self, resume_from_checkpoint=None):
+        a = self.args
+        eng = self.model.engine
+        ga = max(1, int(getattr(a, "gradient_accumulation_steps", 1) or 1))
+        n_batches = self._batches_per_epoch()
+        if n_batches == 0:
+            raise ValueError(f"the training set ({len(self.train_dataset)} rows over {_world()} rank(s)) yields no batch of "
+                             f"per_device_train_batch_size={getattr(a, 'per_device_train_batch_size', 4)} with dataloader_drop_last")
+        per_epoch = max(1, n_batches // ga)
+        max_steps = int(getattr(a, "max_steps", -1) or -1)
+        epochs = float(getattr(a, "num_train_epochs", 1.0))
+        total = max_steps if max_steps > 0 else int(math.ceil(per_epoch * epochs))
+        logging_steps = max(1, int(getattr(a, "logging_steps", 10) or 10))
+        save_strategy = str(getattr(a, "save_strategy", "no")).split(".")[-1].lower()
+        save_steps = max(1, int(getattr(a, "save_steps", 500) or 500))
+        self._before_train()
+        eng.init_optimizer() if eng.master is None else None
+        eng.zero_grad()
+        step, micro, ep = 0, 0, 0
+        skip = 0              # micro-batches of the resumed epoch that were already consumed
+        if resume_from_checkpoint:
+            ckpt = resume_from_checkpoint if isinstance(resume_from_checkpoint, str) else (self._checkpoint_dirs() or [None])[-1]
+            if ckpt is None:
+                raise ValueError(f"resume_from_checkpoint: no checkpoint-* directory under {getattr(a, 'output_dir', 'output')}")
+            st = self.load_checkpoint(ckpt)
+            step, micro = int(st["global_step"]), int(st["micro_step"])
+            ep, skip = divmod(micro, n_batches)
+            self.state.global_step = step
+        last_saved = [-1]
+
+        def save(step_, micro_, ep_):
+            last_saved[0] = step_
+            return self.save_checkpoint(step_, micro_, ep_)
+
+        window = []           # device scalars; only read back at logging time (no per-step host sync)
+        epoch_save_due = False
+        while step < total:
+            it = iter(self.get_train_batches(ep, skip=skip))
+            nxt = next(it, None)
+            while nxt is not None:
+                batch = nxt
+                if eng.reducer is not None:        # DDP no_sync: reduce only with the last micro-batch of an accumulation window
+                    eng.reducer.enabled = (micro + 1) % ga == 0
+                window.append(self.training_step(self.model, batch))
+                nxt = next(it, None)
+                if nxt is not None:                # look-ahead of one batch: its reference forward runs under the optimizer step
+                    nxt = self.prefetch_reference(nxt)
+                micro += 1
+                if micro % ga:
+                    continue
+                lr = self.lr_at(step, total)
+                eng.optimizer_step(lr=lr, beta1=float(getattr(a, "adam_beta1", 0.9)), beta2=float(getattr(a, "adam_beta2", 0.999)),
+                                   eps=float(getattr(a, "adam_epsilon", 1e-8)), weight_decay=float(getattr(a, "weight_decay", 0.0)),
+                                   max_grad_norm=float(getattr(a, "max_grad_norm", 1.0) or 0.0),
+                                   grad_scale=(1.0 / (ga * _world())) if eng.reducer is not None else 1.0 / ga)
+                step += 1
+                self.state.global_step = step
+                if step % logging_steps == 0 or step >= total:
+                    n_opt = max(1, len(window) // ga)
+                    self.log({"loss": float(torch.stack(window).sum()) / n_opt, "learning_rate": lr,
+                              "grad_norm": eng.grad_norm(), "epoch": micro / ga / per_epoch})
+                    window = []
+                ev = str(getattr(a, "evaluation_strategy", "no")).split(".")[-1].lower()
+                if ev == "steps" and self.eval_dataset and step % max(1, int(getattr(a, "eval_steps", None) or logging_steps)) == 0:
+                    self.evaluate()
+                if save_strategy == "steps" and step % save_steps == 0:
+                    save(step, micro, ep)
+                elif epoch_save_due:                    # the epoch ended inside an accumulation window: saved at the first optimizer step after it
+                    save(step, micro, ep)
+                epoch_save_due = False
+                if step >= total:
+                    break
+            # HF fires on_epoch_end - and with save_strategy="epoch" saves - at every epoch end INCLUDING the one training stops in, whether
+            # the epoch was consumed or max_steps cut it short (the loop leaves on an optimizer-step boundary in both cases).  A checkpoint is
+            # only state at such a boundary: an epoch that ends inside an accumulation window defers its save to the next optimizer step.
+            if save_strategy == "epoch":
+                if step >= total:
+                    if last_saved[0] != step:
+                        save(step, micro, ep)
+                elif micro % ga == 0:
+                    save(step, micro, ep)
+                else:
+                    epoch_save_due = True
+                    if _rank() == 0:
+                        print(f"[vlrlhf] epoch {ep} ended inside an accumulation window ({micro % ga} of {ga} micro-batches): its checkpoint is written at optimizer step {step + 1}", flush=True)
+            ep += 1
+            skip = 0
+        return self.state
+
+    def save_state(self):
+        """HF Trainer.save_state: trainer_state.json (step counter + log history) in output_dir, rank 0."""
+        import json
+        import os
+        if _rank() != 0:
+            return
+        out_dir = str(getattr(self.args, "output_dir", "output"))
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "trainer_state.json"), "w") as f:
+            json.dump(dict(global_step=self.state.global_step, log_history=self.log_history), f, indent=1)
+
+    def add_callback(self, cb):
+        self.callbacks.append(cb)
+
+
+class VLDPOTrainer(VLTrainerLoop):
     def __init__(
         self,
         model=None,
@@ -437,6 +767,32 @@ class VLDPOTrainer:
             self._ref_pending = (inputs["chosen_input_ids"], rc, rr)
         return inputs
 
+    def _before_train(self):
+        if self.precompute_ref_log_probs and not self._precomputed_train_ref_log_probs:
+            self.precompute_reference_log_probs(self.train_dataset)
+            self._precomputed_train_ref_log_probs = True
+
+    def _before_evaluate(self, ds, explicit: bool):
+        if self.precompute_ref_log_probs and not self._precomputed_eval_ref_log_probs and not explicit:
+            self.precompute_reference_log_probs(ds)
+            self._precomputed_eval_ref_log_probs = True
+
+    def _evaluate_samples(self, rows, bs):
+        if self.generate_during_eval and rows:
+            # trl==0.8.1 DPOTrainer.evaluation_loop: ONE random eval batch is sampled from the policy and the reference and logged as a
+            # (prompt, policy, reference) table (wandb.Table there; a "game_log" entry of log_history + a rank-0 print here).  Every rank
+            # draws its own batch from its shard - no collective is involved.
+            import random
+            pick = random.sample(range(len(rows)), k=min(bs, len(rows)))
+            sample = self._prepare_inputs(self.data_collator([rows[i] for i in pick]))
+            policy_txt, ref_txt = self.get_batch_samples(self.model, sample)
+            prompts = sample.get("prompt") or self.tokenizer.batch_decode(sample["prompt_input_ids"], skip_special_tokens=True)
+            table = [[pr, po[len(pr):], rf[len(pr):]] for pr, po, rf in zip(prompts, policy_txt, ref_txt)]
+            if _rank() == 0:
+                self.log_history.append({"game_log": {"columns": ["Prompt", "Policy", "Ref Model"], "rows": table}, "step": self.state.global_step})
+                for row in table:
+                    print({"prompt": row[0], "policy": row[1], "ref_model": row[2]}, flush=True)
+
     def get_batch_loss_metrics(self, model, batch, train_eval: Literal["train", "eval"] = "train"):
         """trl==0.8.1 DPOTrainer.get_batch_loss_metrics.  The reference forward is issued on a side HIP stream ahead of
         the policy forward (it is frozen and shares only the cached vision features), then joined before the loss."""
@@ -478,55 +834,6 @@ class VLDPOTrainer:
             return loss, metrics
         return loss
 
-    def store_metrics(self, metrics, train_eval="train"):
-        for k, v in metrics.items():
-            self._stored_metrics[train_eval][k].append(v)
-
-    def log(self, logs: Dict[str, float]):
-        """trl DPOTrainer.log + HF Trainer.log: the stored metrics are averaged over the micro-steps since the last log and -
-        like the loss HF reports (`_nested_gather(tr_loss).mean()`) - over the data-parallel ranks, with ONE all-reduce of
-        the <= 9 scalars (SURVEY.md 8e).  Every rank must call log() at the same steps (they do: same step counter)."""
-        from ..parallel import all_reduce_mean_scalars
-        train_eval = "train" if "loss" in logs else "eval"
-        keys, vals = [], []
-        for k, v in self._stored_metrics[train_eval].items():
-            keys.append(k)
-            vals.append(torch.stack([torch.as_tensor(x, dtype=torch.float32, device=self.accelerator.device) for x in v]).mean())
-        for k in ("loss", "eval_loss"):
-            if k in logs:
-                keys.append(k)
-                vals.append(float(logs[k]))
-        self._stored_metrics[train_eval].clear()
-        if keys:
-            logs.update(zip(keys, all_reduce_mean_scalars(vals, device=self.accelerator.device if _world() > 1 and _backend() == "nccl" else None)))
-        logs = dict(logs, step=self.state.global_step)
-        self.log_history.append(logs)
-        if getattr(self.args, "local_rank", 0) in (0, -1) and _rank() == 0:
-            print({k: (round(v, 6) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
-        return logs
-
-    # ------------------------------------------------------------------------------------------ step + loop
-    def _prepare_inputs(self, inputs):
-        dev = self.accelerator.device
-
-        def mv(v):
-            if isinstance(v, torch.Tensor):
-                return v.to(dev, non_blocking=True)
-            if isinstance(v, dict):
-                return {k: mv(x) for k, x in v.items()}
-            return v
-        return {k: mv(v) for k, v in inputs.items()}
-
-    def training_step(self, model, inputs) -> torch.Tensor:
-        """reference base/trainer.py:303-308 + transformers Trainer.training_step: H2D, loss, backward, return
-        loss.detach() / gradient_accumulation_steps.  (No empty_cache / gc.collect: that flush serialises the device.)"""
-        model.train()
-        inputs = self._prepare_inputs(inputs)
-        loss = self.compute_loss(model, inputs)
-        ga = max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1))
-        loss.backward()
-        return loss.detach() / ga
-
     # ------------------------------------------------------------------------------------------ evaluation
     def prediction_step(self, model, inputs, prediction_loss_only: bool = True, ignore_keys=None):
         """trl==0.8.1 DPOTrainer.prediction_step: no-grad loss + metrics of one batch, stored under the eval_ prefix;
@@ -538,48 +845,6 @@ class VLDPOTrainer:
             return loss.detach(), None, None
         logits = torch.stack([metrics["eval_logits/chosen"], metrics["eval_logits/rejected"]]).mean(dim=0, keepdim=True)
         return loss.detach(), logits, torch.zeros(logits.shape[0], device=logits.device)
-
-    def evaluate(self, eval_dataset=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
-        """HF Trainer.evaluate on the DPO objective: mean eval loss + the eight eval_ metrics over the (rank-sharded) eval set."""
-        ds = eval_dataset if eval_dataset is not None else self.eval_dataset
-        if not ds:
-            return {}
-        if self.precompute_ref_log_probs and not self._precomputed_eval_ref_log_probs and eval_dataset is None:
-            self.precompute_reference_log_probs(ds)
-            self._precomputed_eval_ref_log_probs = True
-        bs = int(getattr(self.args, "per_device_eval_batch_size", None) or getattr(self.args, "per_device_train_batch_size", 4))
-        # the index list is padded by wrapping to a multiple of the world size (as _train_row_batches does): every rank runs the same
-        # number of prediction steps and reduces the same 9 scalars in log() - an eval set smaller than the world would otherwise
-        # leave ranks without metrics and hang the collective (torch DistributedSampler semantics, as HF's eval dataloader)
-        rows = list(ds)
-        w = _world()
-        if w > 1 and len(rows) % w:
-            pad = (-len(rows)) % w                      # cycled: an eval set smaller than the padding still fills every rank
-            rows = rows + (rows * (pad // len(rows) + 1))[:pad]
-        rows = rows[_rank()::w]
-        was_training = self.model.training
-        self.model.eval()
-        if self.generate_during_eval and rows:
-            # trl==0.8.1 DPOTrainer.evaluation_loop: ONE random eval batch is sampled from the policy and the reference and logged as a
-            # (prompt, policy, reference) table (wandb.Table there; a "game_log" entry of log_history + a rank-0 print here).  Every rank
-            # draws its own batch from its shard - no collective is involved.
-            import random
-            pick = random.sample(range(len(rows)), k=min(bs, len(rows)))
-            sample = self._prepare_inputs(self.data_collator([rows[i] for i in pick]))
-            policy_txt, ref_txt = self.get_batch_samples(self.model, sample)
-            prompts = sample.get("prompt") or self.tokenizer.batch_decode(sample["prompt_input_ids"], skip_special_tokens=True)
-            table = [[pr, po[len(pr):], rf[len(pr):]] for pr, po, rf in zip(prompts, policy_txt, ref_txt)]
-            if _rank() == 0:
-                self.log_history.append({"game_log": {"columns": ["Prompt", "Policy", "Ref Model"], "rows": table}, "step": self.state.global_step})
-                for row in table:
-                    print({"prompt": row[0], "policy": row[1], "ref_model": row[2]}, flush=True)
-        losses = []
-        for i in range(0, len(rows), bs):
-            loss, _, _ = self.prediction_step(self.model, self.data_collator(rows[i:i + bs]))
-            losses.append(loss)
-        self.model.train(was_training)
-        out = {f"{metric_key_prefix}_loss": float(torch.stack(losses).mean()) if losses else float("nan")}
-        return self.log(out)
 
     # ------------------------------------------------------------------------------------------ reference pre-pass
     def compute_reference_log_probs(self, padded_batch: Dict) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -615,241 +880,6 @@ class VLDPOTrainer:
                 r["reference_chosen_logps"], r["reference_rejected_logps"] = c, j
         return dataset
 
-    def _train_row_batches(self, epoch: int):
-        """One epoch of this rank's row batches.  torch DistributedSampler semantics (accelerate MULTI_GPU, ddp.yaml): the
-        shuffled index list is padded by wrapping to a multiple of the world size so that EVERY rank gets the same number
-        of batches (unequal counts would dead-lock the gradient all-reduce), then strided by rank.  HF's default
-        dataloader_drop_last=False: the final partial batch is kept."""
-        bs = int(getattr(self.args, "per_device_train_batch_size", 4))
-        world, rank = _world(), _rank()
-        idx = list(range(len(self.train_dataset)))
-        random.Random(int(getattr(self.args, "seed", 42)) + epoch).shuffle(idx)
-        if world > 1 and len(idx) % world:
-            idx += idx[: world - len(idx) % world]
-        idx = idx[rank::world]
-        drop_last = bool(getattr(self.args, "dataloader_drop_last", False))
-        for i in range(0, len(idx), bs):
-            rows = idx[i:i + bs]
-            if len(rows) < bs and drop_last:
-                break
-            yield [self.train_dataset[j] for j in rows]
-
-    def _batches_per_epoch(self) -> int:
-        bs = int(getattr(self.args, "per_device_train_batch_size", 4))
-        n = -(-len(self.train_dataset) // _world())
-        return n // bs if getattr(self.args, "dataloader_drop_last", False) else -(-n // bs)
-
-    def get_train_batches(self, epoch: int, skip: int = 0):
-        """collated batches of one epoch.  The collator (image decode + CLIP preprocess) runs `dataloader_prefetch` batches
-        ahead on a background thread and the H2D copy goes through a copy stream (base/loader.py); 0 = collate inline."""
-        import itertools
-        depth = int(getattr(self.args, "dataloader_prefetch", 2) or 0)
-        rows_iter = lambda: itertools.islice(self._train_row_batches(epoch), skip, None)   # noqa: E731  (resume: skip consumed batches un-collated)
-        if depth <= 0:
-            for rows in rows_iter():
-                yield self.data_collator(rows)
-            return
-        from .loader import PrefetchLoader
-        yield from PrefetchLoader(rows_iter, self.data_collator, self.accelerator.device, depth)
-
-    def lr_at(self, step: int, total: int) -> float:
-        """transformers get_scheduler('cosine' | 'linear' | 'constant') with warmup_ratio / warmup_steps."""
-        a = self.args
-        base = float(getattr(a, "learning_rate", 5e-5))
-        warm = int(getattr(a, "warmup_steps", 0) or 0) or math.ceil(float(getattr(a, "warmup_ratio", 0.0) or 0.0) * total)
-        kind = str(getattr(a, "lr_scheduler_type", "linear")).split(".")[-1].lower()
-        if step < warm:
-            return base * step / max(1, warm)
-        prog = (step - warm) / max(1, total - warm)
-        if kind == "cosine":
-            return base * max(0.0, 0.5 * (1.0 + math.cos(math.pi * prog)))
-        if kind.startswith("constant"):
-            return base
-        return base * max(0.0, 1.0 - prog)
-
-    # ------------------------------------------------------------------------------------------ checkpoints
-    def _checkpoint_dirs(self):
-        import os
-        import re
-        out_dir = str(getattr(self.args, "output_dir", "output"))
-        if not os.path.isdir(out_dir):
-            return []
-        found = [(int(m.group(1)), os.path.join(out_dir, d)) for d in os.listdir(out_dir)
-                 if (m := re.fullmatch(r"checkpoint-(\d+)", d)) and os.path.isfile(os.path.join(out_dir, d, "trainer_state.json"))]
-        return [p for _, p in sorted(found)]
-
-    def save_checkpoint(self, step: int, micro: int, epoch: int, window_len: int = 0):
-        """HF Trainer._save_checkpoint for this path: `output_dir/checkpoint-<step>/` with the weights (adapters under LoRA),
-        the optimizer state (fp32 master / m / v + step), trainer_state.json (step counters, log history, the dropout call counters
-        that seed the counter-based masks, world size / accumulation steps the counters were taken under); rotated to
-        `save_total_limit`.  Rank 0 writes (every rank holds identical state under DDP)."""
-        import json
-        import os
-        import shutil
-        from safetensors.torch import save_file
-        if _rank() != 0:
-            return None
-        eng = self.model.engine
-        path = os.path.join(str(getattr(self.args, "output_dir", "output")), f"checkpoint-{step}")
-        tmp = path + ".tmp"
-        shutil.rmtree(tmp, ignore_errors=True)
-        os.makedirs(tmp)
-        if self.is_peft_model:
-            self.model.save_adapter(tmp)
-        else:
-            self.model.save_pretrained(tmp)
-        st = eng.optimizer_state()
-        if st is not None:
-            for k in ("master", "m", "v"):          # one file per buffer: 27 GB each at 7B full fine-tuning
-                save_file({k: st[k].detach().cpu()}, os.path.join(tmp, f"optimizer_{k}.safetensors"))
-        with open(os.path.join(tmp, "trainer_state.json"), "w") as f:
-            json.dump(dict(global_step=step, micro_step=micro, epoch=epoch, opt_step=eng.opt_step, log_history=self.log_history,
-                           world_size=_world(), lora_calls=getattr(eng, "_lora_calls", 0), plora_calls=getattr(eng, "_plora_calls", 0),
-                           gradient_accumulation_steps=max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1)),
-                           per_device_train_batch_size=int(getattr(self.args, "per_device_train_batch_size", 4))), f, indent=1)
-        shutil.rmtree(path, ignore_errors=True)
-        os.replace(tmp, path)                        # a checkpoint directory is either complete or absent
-        limit = int(getattr(self.args, "save_total_limit", 0) or 0)
-        if limit > 0:
-            for old in self._checkpoint_dirs()[:-limit]:
-                shutil.rmtree(old, ignore_errors=True)
-        return path
-
-    def load_checkpoint(self, path: str) -> dict:
-        import json
-        import os
-        from safetensors.torch import load_file
-        eng = self.model.engine
-        with open(os.path.join(path, "trainer_state.json")) as f:
-            state = json.load(f)
-        # micro_step -> (epoch, batches to skip) only means the same thing under the same sharding
-        for key, now in (("world_size", _world()), ("gradient_accumulation_steps", max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1))),
-                         ("per_device_train_batch_size", int(getattr(self.args, "per_device_train_batch_size", 4)))):
-            if key in state and int(state[key]) != now:
-                raise ValueError(f"resume_from_checkpoint: {path} was written with {key}={state[key]}, this run has {now}")
-        if self.is_peft_model:
-            self.model.load_adapter(path)
-        else:
-            sd = {}
-            for fn in sorted(os.listdir(path)):
-                if fn.startswith("model") and fn.endswith(".safetensors"):
-                    sd.update(load_file(os.path.join(path, fn)))
-            eng.policy.load_state_dict(sd)
-        if os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):
-            bufs = {k: load_file(os.path.join(path, f"optimizer_{k}.safetensors"))[k] for k in ("master", "m", "v")}
-            eng.load_optimizer_state(bufs["master"], bufs["m"], bufs["v"], state["opt_step"])
-        if hasattr(eng, "_lora_calls"):
-            eng._lora_calls = int(state.get("lora_calls", 0))
-        if hasattr(eng, "_plora_calls"):
-            eng._plora_calls = int(state.get("plora_calls", 0))
-        self.log_history = list(state.get("log_history", []))
-        return state
-
-    def train(self, resume_from_checkpoint=None):
-        a = self.args
-        eng = self.model.engine
-        ga = max(1, int(getattr(a, "gradient_accumulation_steps", 1) or 1))
-        n_batches = self._batches_per_epoch()
-        if n_batches == 0:
-            raise ValueError(f"the training set ({len(self.train_dataset)} rows over {_world()} rank(s)) yields no batch of "
-                             f"per_device_train_batch_size={getattr(a, 'per_device_train_batch_size', 4)} with dataloader_drop_last")
-        per_epoch = max(1, n_batches // ga)
-        max_steps = int(getattr(a, "max_steps", -1) or -1)
-        epochs = float(getattr(a, "num_train_epochs", 1.0))
-        total = max_steps if max_steps > 0 else int(math.ceil(per_epoch * epochs))
-        logging_steps = max(1, int(getattr(a, "logging_steps", 10) or 10))
-        save_strategy = str(getattr(a, "save_strategy", "no")).split(".")[-1].lower()
-        save_steps = max(1, int(getattr(a, "save_steps", 500) or 500))
-        if self.precompute_ref_log_probs and not self._precomputed_train_ref_log_probs:
-            self.precompute_reference_log_probs(self.train_dataset)
-            self._precomputed_train_ref_log_probs = True
-        eng.init_optimizer() if eng.master is None else None
-        eng.zero_grad()
-        step, micro, ep = 0, 0, 0
-        skip = 0              # micro-batches of the resumed epoch that were already consumed
-        if resume_from_checkpoint:
-            ckpt = resume_from_checkpoint if isinstance(resume_from_checkpoint, str) else (self._checkpoint_dirs() or [None])[-1]
-            if ckpt is None:
-                raise ValueError(f"resume_from_checkpoint: no checkpoint-* directory under {getattr(a, 'output_dir', 'output')}")
-            st = self.load_checkpoint(ckpt)
-            step, micro = int(st["global_step"]), int(st["micro_step"])
-            ep, skip = divmod(micro, n_batches)
-            self.state.global_step = step
-        last_saved = [-1]
-
-        def save(step_, micro_, ep_):
-            last_saved[0] = step_
-            return self.save_checkpoint(step_, micro_, ep_)
-
-        window = []           # device scalars; only read back at logging time (no per-step host sync)
-        epoch_save_due = False
-        while step < total:
-            it = iter(self.get_train_batches(ep, skip=skip))
-            nxt = next(it, None)
-            while nxt is not None:
-                batch = nxt
-                if eng.reducer is not None:        # DDP no_sync: reduce only with the last micro-batch of an accumulation window
-                    eng.reducer.enabled = (micro + 1) % ga == 0
-                window.append(self.training_step(self.model, batch))
-                nxt = next(it, None)
-                if nxt is not None:                # look-ahead of one batch: its reference forward runs under the optimizer step
-                    nxt = self.prefetch_reference(nxt)
-                micro += 1
-                if micro % ga:
-                    continue
-                lr = self.lr_at(step, total)
-                eng.optimizer_step(lr=lr, beta1=float(getattr(a, "adam_beta1", 0.9)), beta2=float(getattr(a, "adam_beta2", 0.999)),
-                                   eps=float(getattr(a, "adam_epsilon", 1e-8)), weight_decay=float(getattr(a, "weight_decay", 0.0)),
-                                   max_grad_norm=float(getattr(a, "max_grad_norm", 1.0) or 0.0),
-                                   grad_scale=(1.0 / (ga * _world())) if eng.reducer is not None else 1.0 / ga)
-                step += 1
-                self.state.global_step = step
-                if step % logging_steps == 0 or step >= total:
-                    n_opt = max(1, len(window) // ga)
-                    self.log({"loss": float(torch.stack(window).sum()) / n_opt, "learning_rate": lr,
-                              "grad_norm": eng.grad_norm(), "epoch": micro / ga / per_epoch})
-                    window = []
-                ev = str(getattr(a, "evaluation_strategy", "no")).split(".")[-1].lower()
-                if ev == "steps" and self.eval_dataset and step % max(1, int(getattr(a, "eval_steps", None) or logging_steps)) == 0:
-                    self.evaluate()
-                if save_strategy == "steps" and step % save_steps == 0:
-                    save(step, micro, ep)
-                elif epoch_save_due:                    # the epoch ended inside an accumulation window: saved at the first optimizer step after it
-                    save(step, micro, ep)
-                epoch_save_due = False
-                if step >= total:
-                    break
-            # HF fires on_epoch_end - and with save_strategy="epoch" saves - at every epoch end INCLUDING the one training stops in, whether
-            # the epoch was consumed or max_steps cut it short (the loop leaves on an optimizer-step boundary in both cases).  A checkpoint is
-            # only state at such a boundary: an epoch that ends inside an accumulation window defers its save to the next optimizer step.
-            if save_strategy == "epoch":
-                if step >= total:
-                    if last_saved[0] != step:
-                        save(step, micro, ep)
-                elif micro % ga == 0:
-                    save(step, micro, ep)
-                else:
-                    epoch_save_due = True
-                    if _rank() == 0:
-                        print(f"[vlrlhf] epoch {ep} ended inside an accumulation window ({micro % ga} of {ga} micro-batches): its checkpoint is written at optimizer step {step + 1}", flush=True)
-            ep += 1
-            skip = 0
-        return self.state
-
-    def save_state(self):
-        """HF Trainer.save_state: trainer_state.json (step counter + log history) in output_dir, rank 0."""
-        import json
-        import os
-        if _rank() != 0:
-            return
-        out_dir = str(getattr(self.args, "output_dir", "output"))
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "trainer_state.json"), "w") as f:
-            json.dump(dict(global_step=self.state.global_step, log_history=self.log_history), f, indent=1)
-
-    def add_callback(self, cb):
-        self.callbacks.append(cb)
-
     def get_batch_samples(self, model, batch):
         """reference base/trainer.py:310-360: sample a continuation of every prompt from the policy and from the reference (the batch's
         `reference_output`, else the reference model, else the policy with its adapters disabled), pad to max_length, decode.
@@ -879,6 +909,120 @@ class VLDPOTrainer:
         reference_output = pad_to_length(reference_output, self.max_length, pad)
         return (self.tokenizer.batch_decode(policy_output, skip_special_tokens=True),
                 self.tokenizer.batch_decode(reference_output, skip_special_tokens=True))
+
+
+class VLSFTTrainer(VLTrainerLoop):
+    """Supervised fine-tuning - mirror of the reference src/vlrlhf/base/trainer.py:573-674 plus what the reference inherits from
+    trl==0.8.1 `SFTTrainer` / transformers `Trainer` on this path: loss = the model's own causal-LM cross-entropy (`outputs.loss`: ONE
+    mean over the label rows of the whole micro-batch), micro-batch means averaged over an accumulation window and over the ranks (a mean of
+    means, as HF does - not token-weighted).  The loop itself (VLTrainerLoop) is VLDPOTrainer's."""
+
+    def __init__(
+        self,
+        model=None,
+        args=None,
+        data_collator: Any = None,
+        train_dataset=None,
+        eval_dataset=None,
+        processor=None,
+        model_init: Optional[Callable] = None,
+        compute_metrics: Optional[Callable] = None,
+        callbacks: Optional[List] = None,
+        optimizers: Tuple = (None, None),
+        preprocess_logits_for_metrics: Optional[Callable] = None,
+        peft_config: Optional[Dict] = None,
+        dataset_text_field: Optional[str] = None,
+        packing: Optional[bool] = True,
+        formatting_func: Optional[Callable] = None,
+        max_seq_length: Optional[int] = None,
+        infinite: Optional[bool] = None,
+        num_of_sequences: Optional[int] = 1024,
+        chars_per_token: Optional[float] = 3.6,
+        dataset_num_proc: Optional[int] = None,
+        dataset_batch_size: int = 1000,
+        neftune_noise_alpha: Optional[float] = None,
+        model_init_kwargs: Optional[Dict] = None,
+        dataset_kwargs: Optional[Dict] = None,
+        eval_packing: Optional[bool] = None,
+    ):
+        # argument order = reference base/trainer.py:574-601
+        if model is None:
+            raise ValueError("VLSFTTrainer needs a model")
+        if neftune_noise_alpha is not None:
+            raise NotImplementedError("neftune_noise_alpha (NEFTune embedding noise) is not on the MI355X SFT path")
+        if peft_config is not None:          # trl SFTTrainer.__init__: model = get_peft_model(model, peft_config)
+            if not hasattr(model, "apply_lora"):
+                raise ValueError("peft_config given but the model wrapper has no apply_lora()")
+            model.apply_lora(peft_config)
+        self.is_peft_model = bool(getattr(model, "is_peft_model", False))
+        self.processor = processor
+        self.tokenizer = processor.tokenizer if processor is not None else None
+        self.model = model
+        self.args = args
+        # trl: max_seq_length None -> min(tokenizer.model_max_length, 1024)
+        self.max_seq_length = max_seq_length if max_seq_length is not None else min(int(getattr(self.tokenizer, "model_max_length", 1024) or 1024), 1024)
+        self.dataset_text_field = dataset_text_field
+        self.packing = packing               # accepted and ignored: the reference's _prepare_dataset override (:656-674) never packs
+        self.dataset_num_proc = dataset_num_proc
+        self.callbacks = list(callbacks or [])
+        self._stored_metrics = defaultdict(lambda: defaultdict(list))
+        self.log_history: List[dict] = []
+        self.accelerator = _Accelerator(model)
+        self.data_collator = data_collator
+        self.train_dataset = self._prepare_dataset(train_dataset)
+        self.eval_dataset = self._prepare_dataset(eval_dataset)
+        self.state = _State()
+
+    # ------------------------------------------------------------------------------------------ tokenisation
+    def tokenize_row(self, element):
+        """reference :631-654, quirk included: every eos INSIDE the conversation gets attention_mask 0 and label -100 (a hole in the
+        middle of the key mask), then one eos is appended with mask 1 and label eos, then everything is cut to max_seq_length."""
+        conv = element["conversations"]
+        image = element["img_path"]
+        first_sentence = conv[0]["value"]
+        first_sentence = self.processor.format_multimodal_prompt(first_sentence, image)
+        conv[0]["value"] = first_sentence
+        tokens = self.processor.process_batch_conv([conv])["full"]  # process_batch_conv adds bos token but no eos token
+        tokens = {k: v[0] for k, v in tokens.items()}
+        eos = self.tokenizer.eos_token_id
+        eos_indices = {i for i, x in enumerate(tokens["input_ids"]) if x == eos}
+        tokens["attention_mask"] = [0 if i in eos_indices else m for i, m in enumerate(tokens["attention_mask"])]
+        tokens["labels"] = [-100 if i in eos_indices else l for i, l in enumerate(tokens["labels"])]
+        tokens["input_ids"] = list(tokens["input_ids"]) + [eos]
+        tokens["attention_mask"] = tokens["attention_mask"] + [1]
+        tokens["labels"] = tokens["labels"] + [eos]
+        tokens = {k: v[: self.max_seq_length] for k, v in tokens.items()}
+        tokens["img_path"] = image
+        return tokens
+
+    def _prepare_dataset(self, dataset, *unused, **unused_kw):
+        """reference :656-674: every row through tokenize_row, only input_ids / labels / attention_mask / img_path kept; no packing.
+        Rows that already carry input_ids (pre-tokenised) pass through."""
+        if dataset is None:
+            return None
+        rows = list(dataset)
+        if rows and "input_ids" not in rows[0]:
+            rows = [self.tokenize_row({k: (copy.deepcopy(v) if k == "conversations" else v) for k, v in dict(r).items()}) for r in rows]
+        keep = ("input_ids", "labels", "attention_mask", "img_path")
+        return [{k: r[k] for k in keep if k in r} for r in rows]
+
+    # ------------------------------------------------------------------------------------------ loss
+    def compute_loss(self, model, inputs, return_outputs: bool = False):
+        """transformers Trainer.compute_loss: outputs = model(**inputs); loss = outputs["loss"] - the cross-entropy the wrapper computes on
+        the fused lm-head when `loss` is read (LlavaForRL.causal_lm_loss)."""
+        outputs = model(**{k: v for k, v in inputs.items() if k != "img_path"})
+        loss = model.causal_lm_loss(outputs) if hasattr(model, "causal_lm_loss") else outputs["loss"]
+        if loss is None:
+            raise ValueError("The model did not return a loss from the inputs, only the following keys: "
+                             f"{','.join(k for k in inputs.keys())}.")
+        return (loss, outputs) if return_outputs else loss
+
+    def prediction_step(self, model, inputs, prediction_loss_only: bool = True, ignore_keys=None):
+        with torch.no_grad():
+            loss, outputs = self.compute_loss(model, self._prepare_inputs(inputs), return_outputs=True)
+        if prediction_loss_only:
+            return loss.detach(), None, None
+        return loss.detach(), outputs.logits, outputs.labels
 
 
 class _State:

@@ -439,6 +439,8 @@ class LlavaHipEngine:
         self._norm_ws = torch.empty(_hip.helper("vlr_rmsnorm_bwd_workspace_bytes", self.H), dtype=torch.uint8, device=self.dev)
         self._colsum_ws = torch.empty(_hip.helper("vlr_colsum_workspace_bytes", max(self.H, self.Nqkv, 8)), dtype=torch.uint8, device=self.dev)
         self._sq_ws = torch.empty(_hip.helper("vlr_grad_sqnorm_workspace_bytes"), dtype=torch.uint8, device=self.dev)
+        self._ce_ws = None                  # partials of vlr_ce_mean_fwd (allocated by the first SFT loss)
+        self.ce_row_block = None            # rows per block of vlr_lmhead_ce_bwd; None = the library's default (< 1 GiB of workspace)
         self.norm_out = torch.zeros(3, dtype=torch.float32, device=self.dev)
         # Optional (VLR_ASYNC_OPT=1): clip + AdamW (HBM-bound, 32 ms) on their own stream so that they overlap the next step's
         # FROZEN reference forward; the policy forward waits for the `_opt_done` event.  Measured on MI355X: no gain (650.7 /
@@ -919,7 +921,7 @@ class LlavaHipEngine:
         return logits
 
     # ------------------------------------------------------------------------------------------------ log-probs
-    def logps_forward(self, ctx, labels, shared_mask=None, average=False, label_pad=-100):
+    def logps_forward(self, ctx, labels, shared_mask=None, average=False, label_pad=-100, reduce_seq=True):
         """get_batch_logps on the lm-head restricted to the response rows (identical result: every other row is
         multiplied by a zero mask in the reference, base/trainer.py:185-188).  Returns (logps [Bn], lp_ctx)."""
         Bn, S, M, H, V = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.V
@@ -932,7 +934,7 @@ class LlavaHipEngine:
         seq_off = torch.empty(Bn + 1, dtype=torch.int32, device=self.dev)
         sm = shared_mask.to(device=self.dev, dtype=torch.uint8).contiguous() if shared_mask is not None else None
         _hip.call("vlr_build_rows", lab, sm, Bn, S, label_pad, rows, tgt, seq_off)
-        meta, rkey = ctx.get("meta"), ("R", sm is not None, int(label_pad))
+        meta, rkey = ctx.get("meta"), ("R" if reduce_seq else "R_ce", sm is not None, int(label_pad))      # (the SFT mask is not the DDPO mask)
         if meta is not None and rkey in meta:
             R = meta[rkey]
         else:
@@ -953,9 +955,53 @@ class LlavaHipEngine:
         tok = torch.empty(R, dtype=torch.float32, device=self.dev)
         lse = torch.empty(R, dtype=torch.float32, device=self.dev)
         _hip.call("vlr_lmhead_logps_fwd", hg, ws.v["lm_head"], tgt, tok, lse, lws, logits, R, V, H)
-        _hip.call("vlr_seq_sum", tok, seq_off, Bn, int(average), logps)
+        if reduce_seq:
+            _hip.call("vlr_seq_sum", tok, seq_off, Bn, int(average), logps)
         lp.update(hg=hg, lse=lse, tok=tok)
         return logps, lp
+
+    def ce_forward(self, ctx, labels, shift_mask=None, label_pad=-100):
+        """The causal-LM cross-entropy of the reference wrappers' forward(labels=...): mean of -log p(label) over the rows of the WHOLE
+        batch whose shifted label is not `label_pad` (and whose shifted `shift_mask` [Bn, S-1] is non-zero, when given: the LLaVA
+        wrappers select by the merged attention mask).  The rows go through the same fused lm-head as the log-probs; vlr_ce_mean_fwd
+        folds them in a fixed order.  Returns (out3 = {loss, row count, -1 / rows} on the device, lp_ctx)."""
+        _, lp = self.logps_forward(ctx, labels, shift_mask, False, label_pad, reduce_seq=False)
+        out3 = torch.empty(3, dtype=torch.float32, device=self.dev)
+        if lp["R"] == 0:                      # nn.CrossEntropyLoss over no row: nan
+            out3.copy_(torch.tensor([float("nan"), 0.0, 0.0]))
+            return out3, lp
+        if self._ce_ws is None:
+            self._ce_ws = torch.empty(_hip.helper("vlr_ce_mean_workspace_bytes"), dtype=torch.uint8, device=self.dev)
+        _hip.call("vlr_ce_mean_fwd", lp["tok"], lp["R"], self._ce_ws, out3)
+        lp["out3"] = out3
+        return out3, lp
+
+    def ce_backward(self, lp, dloss, row_block=None):
+        """d loss (scalar) -> d hidden (dense [M,H], zero outside the label rows) and the lm_head weight gradient, the rows walked in
+        blocks (vlr_lmhead_ce_bwd): d logits exists for `row_block` rows at a time (default: under 1 GiB of workspace)."""
+        ctx = lp["ctx"]
+        M, H, V, R = ctx["M"], self.H, self.V, lp["R"]
+        acc = int(not self.grad_fresh)
+        dhidden = torch.zeros(M, H, dtype=BF16, device=self.dev)
+        if R == 0:
+            if not acc and self.lora is None:
+                self.gv["lm_head"].zero_()
+            return dhidden
+        rb = int(row_block if row_block else (self.ce_row_block or _hip.helper("vlr_lmhead_ce_row_block", R, V, H)))
+        rb = min(rb, R)
+        sizes = {rb} | ({R % rb} if R % rb else set())
+        loose = [n for n in sizes if not _hip.helper("vlr_lmhead_is_fused", n, V, H)]
+        lws = self._buf(("lmhead_ws", ctx["tag"], rb), (int(_hip.lib().vlr_lmhead_workspace_bytes(rb, V)),), torch.uint8)
+        logits = self._buf(("logits", ctx["tag"], max(loose)), (max(loose), V), torch.float32) if loose else None
+        dl = self._buf(("dlogits", rb), (rb, V))
+        coef = (dloss.to(torch.float32).reshape(1) * lp["out3"][2:3]).contiguous()
+        dhg = torch.empty(R, H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_lmhead_ce_bwd", lp["hg"], ctx["ws"].v["lm_head"], lp["tgt"], lp["lse"], coef, dl, lws, logits, dhg,
+                  self.gv["lm_head"] if self.lora is None else None, acc, R, V, H, rb)      # under LoRA the lm_head is frozen
+        _hip.call("vlr_scatter_rows", dhg, lp["rows"], dhidden, R, H)
+        if self.reducer is not None and self.lora is None:
+            self.reducer.bucket_ready("lm_head")
+        return dhidden
 
     def logits_mean(self, ctx, lo, hi):
         """mean over [lo:hi] sequences, all positions, all vocabulary entries of the logits = mean_rows(h . sum_v W_v)/V

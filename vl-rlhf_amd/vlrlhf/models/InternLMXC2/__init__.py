@@ -9,9 +9,9 @@ from typing import Any, Dict, List, Literal, Optional, Union
 
 import torch
 
-from ...base.collator import VLDPODataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer
+from ...base.trainer import VLDPOTrainer, VLSFTTrainer
 from ...engine_internlm import InternLMHipEngine
 from ...utils.common import flatten_list
 from ..Llava import LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
@@ -95,6 +95,8 @@ class InternLMXC2ForRL(LlavaForRL):
         generation_config.eos_token_id = 2
         return dict(generation_config=generation_config)
 
+    ce_selects_by_mask = False     # reference :211-219 shifts without the attention mask: the label alone selects a row
+
     def forward(self, input_ids=None, pixel_values=None, im_mask=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None):
         """reference :107-236 on the training path -> lazy `logits`, the EXPANDED `labels`, `image_position_map` (= im_mask)"""
@@ -115,7 +117,9 @@ class InternLMXC2ForRL(LlavaForRL):
         out_labels = c["labels"] if labels is not None else torch.full_like(c["mask"], -100, dtype=torch.long)
         if c.get("meta") is not None:
             out_labels._vlr_meta = c["meta"]
-        return LlavaRLOutputWithPast(loss=None, logits=LazyLogits(self.engine, c, hidden), labels=out_labels, image_position_map=c["img_map"])
+        logits = LazyLogits(self.engine, c, hidden)
+        return LlavaRLOutputWithPast(loss=None, logits=logits, labels=out_labels, image_position_map=c["img_map"],
+                                     loss_fn=self._loss_fn(logits, c) if labels is not None else None)
 
 
 class InternLMXC2Processor(VLProcessor):
@@ -233,9 +237,24 @@ class InternLMXC2DPOTrainer(VLDPOTrainer):
     ...
 
 
+@dataclass
+class InternLMXC2SFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """reference :445-451: pixel_values at the top level of the batch, img_path dropped"""
+        padded = super().__call__(features)
+        padded["pixel_values"] = self.processor.image_processor(padded.pop("img_path"))
+        return padded
+
+
+class InternLMXC2SFTTRainer(VLSFTTrainer):    # sic: the reference's spelling (:481)
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=InternLMXC2ForRL,
     processor=InternLMXC2Processor,
     dpo_collator=InternLMXC2DPODataCollatorWithPadding,
     dpo_trainer=InternLMXC2DPOTrainer,
+    sft_collator=InternLMXC2SFTDataCollatorWithPadding,
+    sft_trainer=InternLMXC2SFTTRainer,
 )

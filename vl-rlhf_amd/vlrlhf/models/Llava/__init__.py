@@ -6,16 +6,16 @@ never written to HBM unless a caller asks for it."""
 import contextlib
 import json
 import os
-from dataclasses import dataclass
-from typing import Any, Dict, List, Literal, Optional, Tuple, Union
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, List, Literal, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 
 from ... import _hip
-from ...base.collator import VLDPODataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer
+from ...base.trainer import VLDPOTrainer, VLSFTTrainer
 from ...engine import BF16, LlavaHipEngine, WeightSet
 from ...utils.common import flatten_list
 from ..utils import ModelCoreMapper
@@ -31,6 +31,17 @@ class LlavaRLOutputWithPast:
     image_hidden_states: Optional[Tuple[torch.Tensor]] = None
     labels: Optional[torch.Tensor] = None
     image_position_map: Optional[torch.Tensor] = None
+    # the reference computes the causal-LM cross-entropy in every forward(labels=...) and DPO throws it away; here `loss` is computed
+    # on FIRST ACCESS (one lm-head pass over the label rows), so a caller that never reads it - the DPO path - launches nothing for it
+    loss_fn: Optional[Callable[[], torch.Tensor]] = field(default=None, repr=False, compare=False)
+
+    def __getattribute__(self, name):
+        if name == "loss":
+            d = object.__getattribute__(self, "__dict__")
+            if d.get("loss") is None and d.get("loss_fn") is not None:
+                d["loss"], d["loss_fn"] = d["loss_fn"](), None
+            return d.get("loss")
+        return object.__getattribute__(self, name)
 
     def __getitem__(self, k):
         return getattr(self, k) if isinstance(k, str) else (self.loss, self.logits)[k]
@@ -69,6 +80,22 @@ class _LogpsFn(torch.autograd.Function):
         dh = ctx.engine.logps_backward(ctx.lp, dlogps.contiguous())
         ctx.lp = None
         return (dh,) + (None,) * 6
+
+
+class _CeFn(torch.autograd.Function):
+    """batch-mean cross-entropy over the label rows (engine.ce_forward / ce_backward) as one autograd node returning the scalar"""
+
+    @staticmethod
+    def forward(ctx, hidden, engine, c, labels, shift_mask, label_pad):
+        out3, lp = engine.ce_forward(c, labels, shift_mask, label_pad)
+        ctx.lp, ctx.engine = lp, engine
+        return out3[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dh = ctx.engine.ce_backward(ctx.lp, dloss)
+        ctx.lp = None
+        return (dh,) + (None,) * 5
 
 
 class LazyLogits:
@@ -122,6 +149,15 @@ class LazyLogits:
             return _LogpsFn.apply(self.hidden, self.engine, self.c, labels, shared, bool(average), int(label_pad))
         logps, _ = self.engine.logps_forward(self.c, labels, shared, bool(average), int(label_pad))
         return logps
+
+    def cross_entropy(self, labels, shift_mask=None, label_pad=-100):
+        """nn.CrossEntropyLoss()(shift_logits[sel], shift_labels[sel]) of the reference wrappers (scalar; differentiable when the forward
+        was): sel = shifted positions with label != label_pad and, when given, shift_mask [B, S-1] != 0."""
+        assert self.lo == 0 and self.hi == self.c["Bn"], "the loss is a mean over the whole batch"
+        if self.hidden.requires_grad:
+            return _CeFn.apply(self.hidden, self.engine, self.c, labels, shift_mask, int(label_pad))
+        out3, _ = self.engine.ce_forward(self.c, labels, shift_mask, int(label_pad))
+        return out3[0].clone()
 
 
 class _Config(dict):
@@ -542,12 +578,29 @@ class LlavaForRL(nn.Module):
     def get_input_embeddings(self):
         return self.weights.v["embed"]
 
+    # ---- causal-LM loss (SFT) ---------------------------------------------------------------------------
+    ce_selects_by_mask = True      # reference Llava :246-257 / LlavaNext :322-331: rows with shifted merged attention mask != 0
+
+    def _loss_fn(self, logits, c):
+        """the reference's `loss` of forward(labels=...), deferred: CrossEntropyLoss (ignore_index -100) over the shifted positions - for
+        the LLaVA wrappers those the shifted MERGED attention mask keeps, for Qwen-VL / InternLM-XComposer2 (ce_selects_by_mask False)
+        every position; the label alone decides there (modeling_qwen.py:839-842, InternLMXC2/__init__.py:211-219)."""
+        def fn():
+            sel = c["mask"].view(c["Bn"], c["S"])[:, 1:].ne(0).to(torch.uint8).contiguous() if self.ce_selects_by_mask else None
+            return logits.cross_entropy(c["labels"], sel, -100)
+        return fn
+
+    @staticmethod
+    def causal_lm_loss(outputs):
+        """the scalar the reference returns as `outputs.loss` (computed on this call if it has not been read yet)"""
+        return outputs.loss
+
     # ---- forward ----------------------------------------------------------------------------------------
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, image_sizes=None):
         """reference Llava/__init__.py:111-271 on the training path.  Returns `logits` (lazy), the EXPANDED `labels`
-        and `image_position_map`; the reference's internal cross-entropy `loss` (:246-257, unused by DPO) is None."""
+        and `image_position_map`; the reference's cross-entropy `loss` (:246-257) is computed when it is first read (SFT), never on the DPO path."""
         if inputs_embeds is not None or past_key_values is not None or use_cache:
             raise NotImplementedError("generation / KV-cache inputs are outside the MI355X DPO training path")
         if pixel_values is None:
@@ -571,8 +624,9 @@ class LlavaForRL(nn.Module):
         out_labels = c["labels"] if labels is not None else torch.full_like(c["mask"], -100, dtype=torch.long)
         if c.get("meta") is not None:
             out_labels._vlr_meta = c["meta"]          # per-batch host-side facts (trainer.concatenated_inputs)
-        return LlavaRLOutputWithPast(loss=None, logits=LazyLogits(self.engine, c, hidden), labels=out_labels,
-                                     image_position_map=c["img_map"])
+        logits = LazyLogits(self.engine, c, hidden)
+        return LlavaRLOutputWithPast(loss=None, logits=logits, labels=out_labels, image_position_map=c["img_map"],
+                                     loss_fn=self._loss_fn(logits, c) if labels is not None else None)
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -694,9 +748,25 @@ class LlavaDPOTrainer(VLDPOTrainer):
     ...
 
 
+@dataclass
+class LlavaSFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """reference :447-453: pixel_values at the top level of the batch, img_path dropped"""
+        padded = super().__call__(features)
+        ip = self.processor.image_processor if self.processor is not None else None
+        padded["pixel_values"] = load_pixel_values(padded.pop("img_path"), ip)
+        return padded
+
+
+class LlavaSFTTRainer(VLSFTTrainer):          # sic: the reference's spelling (:483)
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=LlavaForRL,
     processor=LlavaProcessor,
     dpo_collator=LlavaDPODataCollatorWithPadding,
     dpo_trainer=LlavaDPOTrainer,
+    sft_collator=LlavaSFTDataCollatorWithPadding,
+    sft_trainer=LlavaSFTTRainer,
 )

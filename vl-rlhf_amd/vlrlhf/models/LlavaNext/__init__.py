@@ -18,9 +18,9 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from ...base.collator import VLDPODataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate
-from ...base.trainer import VLDPOTrainer
+from ...base.trainer import VLDPOTrainer, VLSFTTrainer
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LlavaForRL, LlavaProcessor, LlavaRLOutputWithPast
 from ..utils import ModelCoreMapper
@@ -177,9 +177,25 @@ class LlavaNextDPOTrainer(VLDPOTrainer):
     ...
 
 
+@dataclass
+class LlavaNextSFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """reference :535-541: pixel_values AND image_sizes at the top level of the batch, img_path dropped"""
+        padded = super().__call__(features)
+        ip = self.processor.image_processor if self.processor is not None else None
+        padded.update(load_anyres_images(padded.pop("img_path"), ip))
+        return padded
+
+
+class LlavaNextSFTTrainer(VLSFTTrainer):
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=LlavaNextForRL,
     processor=LlavaNextProcessor,
     dpo_collator=LlavaNextDPODataCollatorWithPadding,
     dpo_trainer=LlavaNextDPOTrainer,
+    sft_collator=LlavaNextSFTDataCollatorWithPadding,
+    sft_trainer=LlavaNextSFTTrainer,
 )

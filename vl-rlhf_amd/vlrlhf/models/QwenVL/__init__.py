@@ -14,9 +14,9 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
-from ...base.collator import VLDPODataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer
+from ...base.trainer import VLDPOTrainer, VLSFTTrainer
 from ...engine_qwen import QwenVLHipEngine
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
@@ -144,6 +144,8 @@ class QwenVLForRL(LlavaForRL):
         self._px_cache = (key, px)
         return px
 
+    ce_selects_by_mask = False     # modeling_qwen.py:839-842 shifts without the attention mask: the label alone selects a row
+
     def forward(self, input_ids=None, past_key_values=None, attention_mask=None, token_type_ids=None, position_ids=None,
                 head_mask=None, inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, pixel_values=None):
@@ -167,8 +169,9 @@ class QwenVLForRL(LlavaForRL):
         out_labels = c["labels"] if labels is not None else None
         if out_labels is not None and c.get("meta") is not None:
             out_labels._vlr_meta = c["meta"]
-        return LlavaRLOutputWithPast(loss=None, logits=LazyLogits(self.engine, c, hidden), labels=out_labels,
-                                     image_position_map=c["img_map"])
+        logits = LazyLogits(self.engine, c, hidden)
+        return LlavaRLOutputWithPast(loss=None, logits=logits, labels=out_labels, image_position_map=c["img_map"],
+                                     loss_fn=self._loss_fn(logits, c) if labels is not None else None)
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -336,9 +339,27 @@ class QwenVLDPOTrainer(VLDPOTrainer):
         return batch
 
 
+@dataclass
+class QwenVLSFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """reference :242-246: img_path dropped and NO pixel_values - the model opens the image files named between <img> and </img>
+        in the ids (QwenVLForRL._pixels_from_ids).  Rows whose img_path already is a pixel tensor (synthetic data) hand it over."""
+        padded = super().__call__(features)
+        imgs = flatten_list(padded.pop("img_path"))
+        if len(imgs) and all(isinstance(i, torch.Tensor) for i in imgs):
+            padded["pixel_values"] = load_qwen_pixel_values(imgs)
+        return padded
+
+
+class QwenVLSFTTrainer(VLSFTTrainer):
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=QwenVLForRL,
     processor=QwenVLProcessor,
     dpo_collator=QwenVLDPODataCollatorWithPadding,
     dpo_trainer=QwenVLDPOTrainer,
+    sft_collator=QwenVLSFTDataCollatorWithPadding,
+    sft_trainer=QwenVLSFTTrainer,
 )

@@ -55,6 +55,16 @@ class MyAutoDPOTrainer:
         return auto_core_mapper(_architecture(model_name_or_path)).dpo_trainer(*args, **kwargs)
 
 
+class MyAutoSFTCollator:
+    def __new__(cls, model_name_or_path, pad_token_id=0, label_pad_token_id=-100, processor=None):
+        return auto_core_mapper(_architecture(model_name_or_path)).sft_collator(pad_token_id, label_pad_token_id, processor)
+
+
+class MyAutoSFTTrainer:
+    def __new__(cls, model_name_or_path, *args, **kwargs):
+        return auto_core_mapper(_architecture(model_name_or_path)).sft_trainer(*args, **kwargs)
+
+
 def auto_load_rlmodel(script_args, training_args, lora_args):
     """-> (model, ref_model=None, lora_config); vision tower frozen (reference :554-555; freeze_vision_tower=False raises).  With use_lora the LoraConfig of
     reference :559-571 is returned as a plain dict (peft itself is not needed: the trainer hands it to

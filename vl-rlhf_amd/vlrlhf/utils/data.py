@@ -36,6 +36,29 @@ def make_synthetic_dataset(script_args):
     return rows
 
 
+def make_synthetic_conversations_dataset(script_args):
+    """`--dataset_name synthetic_conversations`: vlquery_json-shaped SFT rows {conversations, image, img_path} for tests and benchmarks.
+    Every row has two or three user / assistant turns; every assistant turn but the last ends with the literal "</s>", as chat exports
+    that keep the end-of-turn token do - those are the eos tokens INSIDE a conversation that VLSFTTrainer.tokenize_row masks out of
+    attention and labels (the holes in the key mask)."""
+    n = int(getattr(script_args, "synthetic_rows", 64))
+    size = int(getattr(script_args, "synthetic_image_size", 336))
+    g = torch.Generator().manual_seed(4321)
+    words = ["alpha", "beta", "gamma", "delta", "red", "blue", "cat", "dog", "tree", "car", "sky", "left", "right"]
+
+    def sent(k):
+        return " ".join(words[int(i)] for i in torch.randint(0, len(words), (k,), generator=g))
+    rows = []
+    for r in range(n):
+        turns = 2 + r % 2
+        conv = []
+        for t in range(turns):
+            conv.append({"from": "user", "value": ("What is shown? " if t == 0 else "And then? ") + sent(4)})
+            conv.append({"from": "assistant", "value": sent(int(torch.randint(3, 12, (1,), generator=g))) + ("</s>" if t + 1 < turns else "")})
+        rows.append(dict(conversations=conv, image=f"synthetic_{r}", img_path=torch.randn(3, size, size, generator=g)))
+    return rows
+
+
 def _load_rows(path):
     """a local export of a hub dataset: .json (list), .jsonl, or a directory of such files"""
     files = [os.path.join(path, f) for f in sorted(os.listdir(path))] if os.path.isdir(path) else [path]
@@ -124,4 +147,5 @@ DATASET_MAP = {
     "vlquery_json": build_dataset_from_vlquery_json,
     "plain_dpo": make_plain_dpo_dataset,
     "synthetic": make_synthetic_dataset,
+    "synthetic_conversations": make_synthetic_conversations_dataset,
 }
