@@ -469,8 +469,8 @@ int vlr_dropout_bits2(void* bits_u8, void* bits_kt_u8, int rows, int cols, float
 long vlr_dropout_bits_kt_bytes(int rows, int cols);
 int vlr_dropout_mask(void* mask_u8, long n, float p, uint64_t seed, vlr_stream_t stream);
 
-/* vlr_decoder_layer_bwd runs the weight-gradient GEMMs on a library-owned side stream (VLR_BWD_STREAMS=0 disables);
- * vlr_layers_join makes `stream` wait for them - call it before anything reads or reduces the weight gradients. */
+/* Kept for callers of earlier ABI versions, when vlr_decoder_layer_bwd could run its weight-gradient GEMMs on a library-owned side
+ * stream and this call joined it: every layer pass runs on the caller's stream now, so it does nothing and returns VLR_OK. */
 int vlr_layers_join(vlr_stream_t stream);
 
 typedef struct {

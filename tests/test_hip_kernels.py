@@ -1036,8 +1036,8 @@ def test_adapter_segment_row_tile_skip(hip, keep):
 @pytest.mark.parametrize("shape", [(4352, 4352, 512), (12792, 4096, 256), (4104, 4360, 320)])
 def test_gemm_residual_continuous(hip, shape):
     """NT GEMM with a residual add at shapes the persistent kernels take (o_proj / down_proj of the forward), out of place and in
-    place (C == residual).  The residual epilogue of the continuous pipeline itself (default off for plain GEMMs, VLR_GEMM_CONT_RES=1)
-    is what test_gemm_lora_segment runs with residual=True."""
+    place (C == residual).  The residual epilogue of the continuous pipeline itself (plain GEMMs with a bf16 residual never take it:
+    measured slower) is what test_gemm_lora_segment runs with residual=True."""
     M, N, K = shape
     x, W, resid = rnd(M, K, seed=1), rnd(N, K, scale=0.05, seed=2), rnd(M, N, seed=3)
     ref = x.float() @ W.float().t() + resid.float()

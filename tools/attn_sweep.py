@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """attention forward / backward time against sequence length at constant work (B * S^2 fixed), causal, 32 heads x 128:
-a per-workgroup fixed cost shows as TF/s falling with S.  attn_sweep.py [reps]  (env VLR_ATTN_EPI=0/1 selects the epilogue)"""
+a per-workgroup fixed cost shows as TF/s falling with S.  attn_sweep.py [reps]  (A/B another build of the library through VLR_LIB)"""
 import math, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vl-rlhf_amd"))

@@ -1,17 +1,20 @@
 #!/bin/bash
 # Evidence for the clock/power ceiling of bf16 MFMA work on this box:
 #   (1) an MFMA-only register loop (tools/mfma_peak.hip), zero vs random operands;
-#   (2) the production 8-phase GEMM at 8192^3 and at the decoder shape, plain and with parts ablated (VLR_GEMM_ABLATE:
-#       1 no LDS-DMA in the K loop, 4 no barriers, 5 both, 8 no epilogue - timing only, results wrong);
+#   (2) the production 8-phase GEMM at 8192^3 and at the decoder shape, plain and with parts ablated (VLR_GEMM_ABLATE of the
+#       diagnostics build `build_hip.py --ablation`, loaded through VLR_LIB: 1 no LDS-DMA in the K loop, 4 no barriers, 5 both,
+#       8 no epilogue - timing only, results wrong; the product library has none of this);
 #   (3) one PMC pass of the production kernel: busy cycles, MFMA-busy cycles, GRBM_GUI_ACTIVE (effective clock = cycles / wall).
 # usage: bash tools/gemm_ceiling.sh > gpurun_out/r02_gemm_ceiling.txt
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
+python vl-rlhf_amd/build_hip.py --ablation || exit 1
+ABL_LIB=$PWD/vl-rlhf_amd/libvlr_hip_ablation.so
 hipcc --offload-arch=gfx950 -O3 tools/mfma_peak.hip -o /tmp/mfma_peak 2>/dev/null && /tmp/mfma_peak
 for shape in "0 8192 8192 8192" "0 12288 12288 4096" "1 12288 4096 22016" "2 4096 11008 12792"; do
   for abl in 0 1 4 5 8; do
     [ "$abl" != 0 ] && [ "${shape:0:1}" != 0 ] && continue
-    VLR_GEMM_ABLATE=$abl python tools/gemm_time.py $shape
+    if [ "$abl" = 0 ]; then python tools/gemm_time.py $shape; else VLR_LIB=$ABL_LIB VLR_GEMM_ABLATE=$abl python tools/gemm_time.py $shape; fi
   done
 done
 mkdir -p gpurun_out

@@ -3,7 +3,7 @@
 The NT launches of the 7B layer share one instruction stream, yet their K tile takes 1.30 us at [12792, 4096, 4096] and 1.6-1.9 us at the
 larger shapes (tools/gemm_tile_trace.py).  This probe varies one thing at a time on the plain NT kernel - N (the weight's size), M (the
 activation's size), K, and the row stride of A / B at constant bytes touched (address-space footprint: TLB reach / DRAM pages) - and
-prints the timeline line of every case.  Diagnostics build: VLR_LIB=vl-rlhf_amd/libvlr_hip_trace.so VLR_GEMM_SPLIT=0 python tools/gemm_ktile_probe.py"""
+prints the timeline line of every case.  Diagnostics build: VLR_LIB=vl-rlhf_amd/libvlr_hip_trace.so python tools/gemm_ktile_probe.py"""
 import os
 import sys
 

@@ -18,4 +18,4 @@ s.record()
 for _ in range(10): f()
 e.record(); torch.cuda.synchronize()
 t = s.elapsed_time(e) / 10 * 1e-3
-print(f"ABL={os.environ.get('VLR_GEMM_ABLATE','0')} layout {layout} {M}x{N}x{K}: {t*1e3:.3f} ms {2*M*N*K/t/1e12:.1f} TF/s")
+print(f"ABL={os.environ.get('VLR_GEMM_ABLATE', '0') if os.environ.get('VLR_LIB') else '0'} layout {layout} {M}x{N}x{K}: {t*1e3:.3f} ms {2*M*N*K/t/1e12:.1f} TF/s")

@@ -1,5 +1,5 @@
 """time vlr_rmsnorm_fwd_f32 / vlr_rmsnorm_fwd at the step's shape and print a checksum of the outputs:
-   VLR_NORM_FWD_REG=0 python tools/norm_time.py ; VLR_NORM_FWD_REG=1 python tools/norm_time.py   (same checksum: the two forms are bit-identical)"""
+   python tools/norm_time.py   (A/B another build of the library through VLR_LIB: same checksum = bit-identical)"""
 import hashlib
 import os
 import sys
@@ -28,7 +28,7 @@ for name, x in (("vlr_rmsnorm_fwd_f32", x32), ("vlr_rmsnorm_fwd", x16)):
     us = s.elapsed_time(e) * 1000 / 200
     by = M * H * (x.element_size() + 2)
     h = hashlib.sha1(y.cpu().view(torch.int16).numpy().tobytes() + rstd.cpu().numpy().tobytes()).hexdigest()[:12]
-    print(f"{name} [{M} x {H}] reg={os.environ.get('VLR_NORM_FWD_REG', '1')}: {us:.1f} us, {by / us / 1e6:.2f} TB/s, checksum {h}")
+    print(f"{name} [{M} x {H}]: {us:.1f} us, {by / us / 1e6:.2f} TB/s, checksum {h}")
 
 # backward on the fp32 stream: dx = rstd (dy w - xhat mean(dy w xhat)) + dres, dw partials reduced in two deterministic stages
 dy = torch.randn(M, H, generator=g).bfloat16().cuda()
@@ -47,4 +47,4 @@ e.record()
 torch.cuda.synchronize()
 us = s.elapsed_time(e) * 1000 / 200
 h = hashlib.sha1(dx.cpu().view(torch.int16).numpy().tobytes() + dw.cpu().view(torch.int16).numpy().tobytes()).hexdigest()[:12]
-print(f"vlr_rmsnorm_bwd_f32 (+ dw reduction) [{M} x {H}] early={os.environ.get('VLR_NORM_BWD_EARLY', '1')}: {us:.1f} us, {M * H * 10 / us / 1e6:.2f} TB/s, checksum {h}")
+print(f"vlr_rmsnorm_bwd_f32 (+ dw reduction) [{M} x {H}]: {us:.1f} us, {M * H * 10 / us / 1e6:.2f} TB/s, checksum {h}")

@@ -52,7 +52,7 @@ def check_kloop_isa(asm_path):
         name, body = m.group(1), m.group(2).split("\n")
         targs = re.match(r"_Z15gemm256p_kernelILb(\d)ELb(\d)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
         if targs and int(targs.group(3)) != 0:
-            continue                                   # timing-ablation instantiations (VLR_GEMM_ABLATE)
+            continue                                   # timing-ablation instantiations (the --ablation build's VLR_GEMM_ABLATE)
         labels = {l.split(":")[0]: i for i, l in enumerate(body) if l.startswith(".LBB")}
         for i, l in enumerate(body):
             t = re.match(r"\s+s_cbranch_\w+\s+(\.LBB\w+)", l)
@@ -176,6 +176,8 @@ if __name__ == "__main__":
         build(force="--force" in sys.argv, defines=defs, tag=sys.argv[sys.argv.index("--tag") + 1])
     elif "--trace" in sys.argv:      # tile-timeline diagnostics of the persistent GEMM (tools/gemm_tile_trace.py)
         build(force="--force" in sys.argv, defines=("VLR_GEMM_TRACE",), tag="_trace")
+    elif "--ablation" in sys.argv:   # timing-only variants that take work OUT of the GEMM kernels (wrong results): VLR_GEMM_ABLATE / VLR_GEMM_FLAGS are
+        build(force="--force" in sys.argv, defines=("VLR_GEMM_ABLATION",), tag="_ablation")      # read by this build alone (tools/gemm_ceiling.sh, gemm_sweep.sh)
     elif "--classic" in sys.argv:  # the round-3 K loop of the persistent GEMM (12 / 4 / 8 / 0 fragment reads per phase), for A/B through VLR_LIB
         build(force="--force" in sys.argv, defines=("VLR_KLOOP_BAL=0",), tag="_classic")
     else:

@@ -98,7 +98,7 @@ extern "C" int vlr_compute_cus(void) {
         int dev = 0, cus = 0;
         dev_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 8) ? cus : 256;
     }
-    if (g_comm_cus < 0) { const char* e = getenv("VLR_COMM_CUS"); g_comm_cus = e ? atoi(e) : 0; if (g_comm_cus < 0 || g_comm_cus > 128) g_comm_cus = 0; }
+    if (g_comm_cus < 0) { g_comm_cus = vlr_env_int("VLR_COMM_CUS", 0); if (g_comm_cus < 0 || g_comm_cus > 128) g_comm_cus = 0; }
     int n = (dev_cus & ~7) - ((g_comm_cus + 7) & ~7);
     return n < 8 ? 8 : n;
 }

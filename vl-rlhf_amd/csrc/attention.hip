@@ -1054,12 +1054,13 @@ __device__ __forceinline__ void dkv_mma_v(f32x16& d, const bf16x8& a, const bf16
     else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));
 }
 
-// PIPE: the tile body as fenced half-units so that every LDS fragment is requested two half-units (8 MFMAs, 256 cycles) before
+// The tile body is fenced half-units so that every LDS fragment is requested two half-units (8 MFMAs, 256 cycles) before
 // the MFMA that consumes it.  Left to itself hipcc sinks each ds_read next to its MFMA (`ds_read; s_waitcnt lgkmcnt(0);
 // v_mfma`, 64 times per tile): with ONE wave per SIMD (423 registers) nothing hides that latency and the kernel ran at 20 % MFMA
 // utilisation - 4.5 us per tile against 0.9 us of MFMA work.  The unit table is at the tile body.
-// Same arithmetic in the same order per accumulator as the unpipelined body (PIPE = 0, VLR_ATTN_PIPE=0): bit-identical.
-template <bool CAUSAL, int PIPE>
+// (Requesting one half-unit ahead, and the unpipelined body this one replaced, measured slower and were removed; each accumulator
+// still sums in the order of that first body.)
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dkv2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                             const bf16_t* __restrict__ v, int ld,
                                                             const bf16_t* __restrict__ dout, int ldo,
@@ -1118,244 +1119,186 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv2_kernel(const bf16_t* __rest
 #pragma unroll
     for (int st = 0; st < 8; ++st) { ATTN_RETIRE(kf[st]); ATTN_RETIRE(vf[st]); }
 
-    if constexpr (PIPE > 0) {
-        // one tile: barrier, next tile's DMA, the fenced half-units.  Two loops per query head - the leading tiles that need masks
-        // (the diagonal of a causal block; every tile when the key block holds padded keys), then the rest - so that each loop
-        // holds ONE body: with both bodies in one loop hipcc moved all 128 accumulator registers between AGPRs and VGPRs at
-        // every iteration.  Every wave runs nq iterations per head whatever its split, so the barriers match.
-        auto tile = [&](int j, int it, auto mask_c) {
-            const int q0 = q_start + it * KV_TILE;
-            const float* lse_t = reinterpret_cast<const float*>(smem + 4 * TB + (j & 1) * 512);   // this tile's 64 lse | 64 delta (tail = +inf)
-            const float* dl_t = lse_t + 64;
-            ATTN_TILE_BARRIER();
-            if (j + 1 < nit) issue(j + 1);
-            if (CAUSAL && q0 + KV_TILE - 1 < kw0) return;     // every query of the tile precedes this wave's keys
-            const char* q_lds = smem + (j & 1) * 2 * TB;
-            const char* do_lds = q_lds + TB;
-            auto tile_body = [&](auto mask_c) {
-                constexpr bool MASK = decltype(mask_c)::value;
-                // per-tile opaque copy of the lane id: the ~40 lane-derived LDS addresses are recomputed per tile instead of being held
-                // (and spilled) across the loop
-#if ATTN_DKV_ASM
-                const int gl = g;
-                uint32_t arow[8], atr[4][2];         // this tile's fragment bases: the per-lane bases + the stage's offset
-                {
-                    const uint32_t so = (uint32_t)((j & 1) * 2 * TB);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) arow[i] = fa0.row[i] + so;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { atr[i][0] = fa0.tr[i][0] + so; atr[i][1] = fa0.tr[i][1] + so; }
-                }
-#else
-                int ln = lane;
-                asm volatile("" : "+v"(ln));
-                const int gl = ln >> 5;
-#endif
-                // sixteen half-units of 4 MFMAs, each fed by 4 LDS fragments (16 registers) requested AHEAD half-units earlier:
-                //   x = 0..7   S / dP:  qb = x >> 2, k-slots {2 (x & 3), 2 (x & 3) + 1}
-                //   x = 8..15  dV / dK: qb = (x - 8) >> 2, h = ((x - 8) >> 1) & 1, d blocks {2 (x & 1), 2 (x & 1) + 1}
-                // P / dS of accumulator rows 4 rq .. 4 rq + 3 of qb are VALU work beside half-unit 4 + 4 qb + rq (S, dP of qb are complete
-                // after x = 4 qb + 3; dV / dK of (qb, h) start at x = 8 + 4 qb + 2 h); they are packed to bf16 as soon as a half (h) is done
-                constexpr int AHEAD = PIPE;
-                bf16x8 u[16][4];
-                f32x4 l2v[8], dlv[8];
-                f32x16 sc[2], dpc[2];
-                f32x4 pmq[8];
-                bf16x8 pf[2][2], dsf[2][2];
-                auto ldh = [&](auto xc) {
-                    constexpr int X = decltype(xc)::value;
-                    if constexpr (X < 8) {
-                        constexpr int qb = X >> 2;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-#if ATTN_DKV_ASM
-                            u[X][2 * i] = dkv_frag_row(arow, 2 * (X & 3) + i, qb * 32, 0);
-                            u[X][2 * i + 1] = dkv_frag_row(arow, 2 * (X & 3) + i, qb * 32, TB);
-#else
-                            u[X][2 * i] = frag_row<D>(q_lds, qb * 32, 2 * (2 * (X & 3) + i), ln);
-                            u[X][2 * i + 1] = frag_row<D>(do_lds, qb * 32, 2 * (2 * (X & 3) + i), ln);
-#endif
-                        }
-                    } else {
-                        constexpr int qb = (X - 8) >> 2, h = ((X - 8) >> 1) & 1;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-#if ATTN_DKV_ASM
-                            u[X][2 * i] = dkv_frag_tr(atr, 2 * (X & 1) + i, qb * 2 + h, TB);
-                            u[X][2 * i + 1] = dkv_frag_tr(atr, 2 * (X & 1) + i, qb * 2 + h, 0);
-#else
-                            u[X][2 * i] = frag_tr<D>(do_lds, (2 * (X & 1) + i) * 32, qb * 2 + h, ln);
-                            u[X][2 * i + 1] = frag_tr<D>(q_lds, (2 * (X & 1) + i) * 32, qb * 2 + h, ln);
-#endif
-                        }
-                    }
-                };
-                auto ldl = [&](auto pc) {                    // lse / delta of the queries of P / dS slice pc = 4 qb + rq
-                    constexpr int P = decltype(pc)::value, qb = P >> 2, rq = P & 3;
-                    l2v[P] = *reinterpret_cast<const f32x4*>(lse_t + qb * 32 + 8 * rq + 4 * gl);
-                    dlv[P] = *reinterpret_cast<const f32x4*>(dl_t + qb * 32 + 8 * rq + 4 * gl);
-                };
-                auto mmh = [&](auto xc) {
-                    constexpr int X = decltype(xc)::value;
-                    if constexpr (X < 8) {
-                        constexpr int qb = X >> 2;
-#if ATTN_DKV_ASM
-                        dkv_mma_v<(X & 3) == 0>(sc[qb], u[X][0], kf[2 * (X & 3)]);
-                        dkv_mma_v<(X & 3) == 0>(dpc[qb], u[X][1], vf[2 * (X & 3)]);
-                        dkv_mma_v<false>(sc[qb], u[X][2], kf[2 * (X & 3) + 1]);
-                        dkv_mma_v<false>(dpc[qb], u[X][3], vf[2 * (X & 3) + 1]);
-#else
-                        if constexpr ((X & 3) == 0) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) { sc[qb][r] = 0.f; dpc[qb][r] = 0.f; }
-                        }
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            sc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i], kf[2 * (X & 3) + i], sc[qb], 0, 0, 0);
-                            dpc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i + 1], vf[2 * (X & 3) + i], dpc[qb], 0, 0, 0);
-                        }
-#endif
-                    } else {
-                        constexpr int qb = (X - 8) >> 2, h = ((X - 8) >> 1) & 1;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            adv[2 * (X & 1) + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i], pf[qb][h], adv[2 * (X & 1) + i], 0, 0, 0);
-                            adk[2 * (X & 1) + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i + 1], dsf[qb][h], adk[2 * (X & 1) + i], 0, 0, 0);
-                        }
-                    }
-                };
-                auto pds = [&](auto pc) {
-                    constexpr int P = decltype(pc)::value, qb = P >> 2, rq = P & 3;
-                    // MASK: one word of "masked" bits per lane (= key): bit c <-> query q0 + 32 qb + c + 4g (the lane's scores sit at
-                    // c = 8 rq + e); a padded key masks all of them, causality the queries before the key: c < ki - query0.  A select on
-                    // a bit test - the `!key_ok || ki > qq` form compiled to a divergent branch around every exp
-                    uint32_t bad = 0;
-                    if constexpr (MASK) {
-                        const int thr = ki - q0 - 32 * qb - 4 * gl;
-                        bad = !key_ok ? 0xffffffffu : (!CAUSAL || thr <= 0 ? 0u : (thr >= 32 ? 0xffffffffu : ((1u << thr) - 1u)));
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int r = 4 * rq + e;
-                        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[qb][r], scale_log2, -l2v[P][e]));   // l2 = +inf past S -> 0
-                        if constexpr (MASK) pv = (bad & (1u << (8 * rq + e))) ? 0.f : pv;
-                        pmq[P][e] = pv;
-                        sc[qb][r] = attn_ds(pv, dpc[qb][r], dlv[P][e]);   // x scale: once, on dK in the epilogue; delta is finite on padded rows
-                    }
-                    if constexpr (rq & 1) {                  // rows 8h .. 8h+7 done: the bf16 operands of dV / dK (pack_frag order)
-                        constexpr int h = rq >> 1;
-                        u32x4 wp, wd;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const f32x4& pp = pmq[P - 1 + (i >> 1)];
-                            wp[i] = pack_bf16(pp[2 * (i & 1)], pp[2 * (i & 1) + 1]);
-                            wd[i] = pack_bf16(sc[qb][8 * h + 2 * i], sc[qb][8 * h + 2 * i + 1]);
-                        }
-                        pf[qb][h] = __builtin_bit_cast(bf16x8, wp);
-                        dsf[qb][h] = __builtin_bit_cast(bf16x8, wd);
-                    }
-                };
-#define DKV_FENCE() __builtin_amdgcn_sched_barrier(0)
-                auto step = [&](auto xc) {
-                    constexpr int X = decltype(xc)::value;
-                    if constexpr (X + AHEAD < 16) ldh(std::integral_constant<int, X + AHEAD>{});
-#if ATTN_DKV_ASM
-                    // P / dS slice p rides half-unit p + 5 (one later than with builtin MFMAs): hipcc pads no hazard of the asm S / dP
-                    // products, and inside a half-unit it may order the slice's VALU reads in front of the unit's MFMAs - a whole
-                    // half-unit (4 MFMAs, >= 128 cycles) now lies between the last write of S / dP of a query block and their first
-                    // read, whatever that order.  Deadlines hold: P / dS of (qb, h) are packed in unit 6 + 4 qb + 2 h, read in 8 + 4 qb + 2 h.
-                    if constexpr (X >= 4 && X < 12) ldl(std::integral_constant<int, X - 4>{});
-                    DKV_FENCE();
-                    mmh(xc);
-                    if constexpr (X >= 5 && X < 13) pds(std::integral_constant<int, X - 5>{});
-                    DKV_FENCE();
-#else
-                    if constexpr (X + 1 >= 4 && X + 1 < 12) ldl(std::integral_constant<int, X + 1 - 4>{});
-                    DKV_FENCE();
-                    mmh(xc);
-                    if constexpr (X >= 4 && X < 12) pds(std::integral_constant<int, X - 4>{});
-                    DKV_FENCE();
-#endif
-                };
-                ldh(std::integral_constant<int, 0>{});
-                if constexpr (AHEAD > 1) ldh(std::integral_constant<int, 1>{});
-                DKV_FENCE();
-                step(std::integral_constant<int, 0>{});  step(std::integral_constant<int, 1>{});
-                step(std::integral_constant<int, 2>{});  step(std::integral_constant<int, 3>{});
-                step(std::integral_constant<int, 4>{});  step(std::integral_constant<int, 5>{});
-                step(std::integral_constant<int, 6>{});  step(std::integral_constant<int, 7>{});
-                step(std::integral_constant<int, 8>{});  step(std::integral_constant<int, 9>{});
-                step(std::integral_constant<int, 10>{}); step(std::integral_constant<int, 11>{});
-                step(std::integral_constant<int, 12>{}); step(std::integral_constant<int, 13>{});
-                step(std::integral_constant<int, 14>{}); step(std::integral_constant<int, 15>{});
-#undef DKV_FENCE
-            };
-            tile_body(mask_c);
-        };
-        // tiles with q0 < kw0 + 31 hold queries that precede some of this wave's keys
-        const int n_mask = any_bad_key ? nq : (CAUSAL ? min(nq, (kw0 + 31 - q_start + KV_TILE - 1) / KV_TILE) : 0);
-        int j = 0;
-        for (int m = 0; m < group; ++m) {
-            int it = 0;
-            for (; it < n_mask; ++it, ++j) tile(j, it, std::true_type{});
-            for (; it < nq; ++it, ++j) tile(j, it, std::false_type{});
-        }
-    } else
-    for (int j = 0; j < nit; ++j) {
-        const int q0 = q_start + (j % nq) * KV_TILE;
+    // one tile: barrier, next tile's DMA, the fenced half-units.  Two loops per query head - the leading tiles that need masks
+    // (the diagonal of a causal block; every tile when the key block holds padded keys), then the rest - so that each loop
+    // holds ONE body: with both bodies in one loop hipcc moved all 128 accumulator registers between AGPRs and VGPRs at
+    // every iteration.  Every wave runs nq iterations per head whatever its split, so the barriers match.
+    auto tile = [&](int j, int it, auto mask_c) {
+        const int q0 = q_start + it * KV_TILE;
         const float* lse_t = reinterpret_cast<const float*>(smem + 4 * TB + (j & 1) * 512);   // this tile's 64 lse | 64 delta (tail = +inf)
         const float* dl_t = lse_t + 64;
         ATTN_TILE_BARRIER();
         if (j + 1 < nit) issue(j + 1);
-        if (CAUSAL && q0 + KV_TILE - 1 < kw0) continue;   // every query of the tile precedes this wave's keys
+        if (CAUSAL && q0 + KV_TILE - 1 < kw0) return;     // every query of the tile precedes this wave's keys
         const char* q_lds = smem + (j & 1) * 2 * TB;
         const char* do_lds = q_lds + TB;
-        const bool need_mask = (CAUSAL && q0 < kw0 + 31) || any_bad_key;   // wave-uniform
+        auto tile_body = [&](auto mask_c) {
+            constexpr bool MASK = decltype(mask_c)::value;
+            // per-tile opaque copy of the lane id: the ~40 lane-derived LDS addresses are recomputed per tile instead of being held
+            // (and spilled) across the loop
+#if ATTN_DKV_ASM
+            const int gl = g;
+            uint32_t arow[8], atr[4][2];         // this tile's fragment bases: the per-lane bases + the stage's offset
+            {
+                const uint32_t so = (uint32_t)((j & 1) * 2 * TB);
 #pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            f32x16 s, dp;
-
+                for (int i = 0; i < 8; ++i) arow[i] = fa0.row[i] + so;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            ATTN_PRIO(1);
-#pragma unroll
-            for (int st = 0; st < 8; ++st) {
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(q_lds, qb * 32, 2 * st, lane), kf[st], s, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(do_lds, qb * 32, 2 * st, lane), vf[st], dp, 0, 0, 0);
+                for (int i = 0; i < 4; ++i) { atr[i][0] = fa0.tr[i][0] + so; atr[i][1] = fa0.tr[i][1] + so; }
             }
-            ATTN_PRIO(0);
-            f32x16 pm;
+#else
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int gl = ln >> 5;
+#endif
+            // sixteen half-units of 4 MFMAs, each fed by 4 LDS fragments (16 registers) requested AHEAD half-units earlier:
+            //   x = 0..7   S / dP:  qb = x >> 2, k-slots {2 (x & 3), 2 (x & 3) + 1}
+            //   x = 8..15  dV / dK: qb = (x - 8) >> 2, h = ((x - 8) >> 1) & 1, d blocks {2 (x & 1), 2 (x & 1) + 1}
+            // P / dS of accumulator rows 4 rq .. 4 rq + 3 of qb are VALU work beside half-unit 4 + 4 qb + rq (S, dP of qb are complete
+            // after x = 4 qb + 3; dV / dK of (qb, h) start at x = 8 + 4 qb + 2 h); they are packed to bf16 as soon as a half (h) is done
+            constexpr int AHEAD = 2;
+            bf16x8 u[16][4];
+            f32x4 l2v[8], dlv[8];
+            f32x16 sc[2], dpc[2];
+            f32x4 pmq[8];
+            bf16x8 pf[2][2], dsf[2][2];
+            auto ldh = [&](auto xc) {
+                constexpr int X = decltype(xc)::value;
+                if constexpr (X < 8) {
+                    constexpr int qb = X >> 2;
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const f32x4 l2 = *reinterpret_cast<const f32x4*>(lse_t + qb * 32 + 8 * rq + 4 * g);
-                const f32x4 dl = *reinterpret_cast<const f32x4*>(dl_t + qb * 32 + 8 * rq + 4 * g);
+                    for (int i = 0; i < 2; ++i) {
+#if ATTN_DKV_ASM
+                        u[X][2 * i] = dkv_frag_row(arow, 2 * (X & 3) + i, qb * 32, 0);
+                        u[X][2 * i + 1] = dkv_frag_row(arow, 2 * (X & 3) + i, qb * 32, TB);
+#else
+                        u[X][2 * i] = frag_row<D>(q_lds, qb * 32, 2 * (2 * (X & 3) + i), ln);
+                        u[X][2 * i + 1] = frag_row<D>(do_lds, qb * 32, 2 * (2 * (X & 3) + i), ln);
+#endif
+                    }
+                } else {
+                    constexpr int qb = (X - 8) >> 2, h = ((X - 8) >> 1) & 1;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+#if ATTN_DKV_ASM
+                        u[X][2 * i] = dkv_frag_tr(atr, 2 * (X & 1) + i, qb * 2 + h, TB);
+                        u[X][2 * i + 1] = dkv_frag_tr(atr, 2 * (X & 1) + i, qb * 2 + h, 0);
+#else
+                        u[X][2 * i] = frag_tr<D>(do_lds, (2 * (X & 1) + i) * 32, qb * 2 + h, ln);
+                        u[X][2 * i + 1] = frag_tr<D>(q_lds, (2 * (X & 1) + i) * 32, qb * 2 + h, ln);
+#endif
+                    }
+                }
+            };
+            auto ldl = [&](auto pc) {                    // lse / delta of the queries of P / dS slice pc = 4 qb + rq
+                constexpr int P = decltype(pc)::value, qb = P >> 2, rq = P & 3;
+                l2v[P] = *reinterpret_cast<const f32x4*>(lse_t + qb * 32 + 8 * rq + 4 * gl);
+                dlv[P] = *reinterpret_cast<const f32x4*>(dl_t + qb * 32 + 8 * rq + 4 * gl);
+            };
+            auto mmh = [&](auto xc) {
+                constexpr int X = decltype(xc)::value;
+                if constexpr (X < 8) {
+                    constexpr int qb = X >> 2;
+#if ATTN_DKV_ASM
+                    dkv_mma_v<(X & 3) == 0>(sc[qb], u[X][0], kf[2 * (X & 3)]);
+                    dkv_mma_v<(X & 3) == 0>(dpc[qb], u[X][1], vf[2 * (X & 3)]);
+                    dkv_mma_v<false>(sc[qb], u[X][2], kf[2 * (X & 3) + 1]);
+                    dkv_mma_v<false>(dpc[qb], u[X][3], vf[2 * (X & 3) + 1]);
+#else
+                    if constexpr ((X & 3) == 0) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) { sc[qb][r] = 0.f; dpc[qb][r] = 0.f; }
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        sc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i], kf[2 * (X & 3) + i], sc[qb], 0, 0, 0);
+                        dpc[qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i + 1], vf[2 * (X & 3) + i], dpc[qb], 0, 0, 0);
+                    }
+#endif
+                } else {
+                    constexpr int qb = (X - 8) >> 2, h = ((X - 8) >> 1) & 1;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        adv[2 * (X & 1) + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i], pf[qb][h], adv[2 * (X & 1) + i], 0, 0, 0);
+                        adk[2 * (X & 1) + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u[X][2 * i + 1], dsf[qb][h], adk[2 * (X & 1) + i], 0, 0, 0);
+                    }
+                }
+            };
+            auto pds = [&](auto pc) {
+                constexpr int P = decltype(pc)::value, qb = P >> 2, rq = P & 3;
+                // MASK: one word of "masked" bits per lane (= key): bit c <-> query q0 + 32 qb + c + 4g (the lane's scores sit at
+                // c = 8 rq + e); a padded key masks all of them, causality the queries before the key: c < ki - query0.  A select on
+                // a bit test - the `!key_ok || ki > qq` form compiled to a divergent branch around every exp
+                uint32_t bad = 0;
+                if constexpr (MASK) {
+                    const int thr = ki - q0 - 32 * qb - 4 * gl;
+                    bad = !key_ok ? 0xffffffffu : (!CAUSAL || thr <= 0 ? 0u : (thr >= 32 ? 0xffffffffu : ((1u << thr) - 1u)));
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int r = 4 * rq + e;
-                    float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], scale_log2, -l2[e]));   // l2 = +inf past S -> 0
-                    if (need_mask) {
-                        const int qq = q0 + qb * 32 + 8 * rq + 4 * g + e;
-                        if (!key_ok || (CAUSAL && ki > qq)) pv = 0.f;
+                    float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[qb][r], scale_log2, -l2v[P][e]));   // l2 = +inf past S -> 0
+                    if constexpr (MASK) pv = (bad & (1u << (8 * rq + e))) ? 0.f : pv;
+                    pmq[P][e] = pv;
+                    sc[qb][r] = attn_ds(pv, dpc[qb][r], dlv[P][e]);   // x scale: once, on dK in the epilogue; delta is finite on padded rows
+                }
+                if constexpr (rq & 1) {                  // rows 8h .. 8h+7 done: the bf16 operands of dV / dK (pack_frag order)
+                    constexpr int h = rq >> 1;
+                    u32x4 wp, wd;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const f32x4& pp = pmq[P - 1 + (i >> 1)];
+                        wp[i] = pack_bf16(pp[2 * (i & 1)], pp[2 * (i & 1) + 1]);
+                        wd[i] = pack_bf16(sc[qb][8 * h + 2 * i], sc[qb][8 * h + 2 * i + 1]);
                     }
-                    pm[r] = pv;
-                    s[r] = pv * (dp[r] - dl[e]);
+                    pf[qb][h] = __builtin_bit_cast(bf16x8, wp);
+                    dsf[qb][h] = __builtin_bit_cast(bf16x8, wd);
                 }
-            }
-            ATTN_PRIO(1);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const bf16x8 pf = pack_frag(pm, h);
-                const bf16x8 dsf = pack_frag(s, h);
-                const int ks = qb * 2 + h;
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    adv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(do_lds, db * 32, ks, lane), pf, adv[db], 0, 0, 0);
-                    adk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(q_lds, db * 32, ks, lane), dsf, adk[db], 0, 0, 0);
-                }
-            }
-            ATTN_PRIO(0);
-        }
+            };
+#define DKV_FENCE() __builtin_amdgcn_sched_barrier(0)
+            auto step = [&](auto xc) {
+                constexpr int X = decltype(xc)::value;
+                if constexpr (X + AHEAD < 16) ldh(std::integral_constant<int, X + AHEAD>{});
+#if ATTN_DKV_ASM
+                // P / dS slice p rides half-unit p + 5 (one later than with builtin MFMAs): hipcc pads no hazard of the asm S / dP
+                // products, and inside a half-unit it may order the slice's VALU reads in front of the unit's MFMAs - a whole
+                // half-unit (4 MFMAs, >= 128 cycles) now lies between the last write of S / dP of a query block and their first
+                // read, whatever that order.  Deadlines hold: P / dS of (qb, h) are packed in unit 6 + 4 qb + 2 h, read in 8 + 4 qb + 2 h.
+                if constexpr (X >= 4 && X < 12) ldl(std::integral_constant<int, X - 4>{});
+                DKV_FENCE();
+                mmh(xc);
+                if constexpr (X >= 5 && X < 13) pds(std::integral_constant<int, X - 5>{});
+                DKV_FENCE();
+#else
+                if constexpr (X + 1 >= 4 && X + 1 < 12) ldl(std::integral_constant<int, X + 1 - 4>{});
+                DKV_FENCE();
+                mmh(xc);
+                if constexpr (X >= 4 && X < 12) pds(std::integral_constant<int, X - 4>{});
+                DKV_FENCE();
+#endif
+            };
+            ldh(std::integral_constant<int, 0>{});
+            ldh(std::integral_constant<int, 1>{});
+            DKV_FENCE();
+            step(std::integral_constant<int, 0>{});  step(std::integral_constant<int, 1>{});
+            step(std::integral_constant<int, 2>{});  step(std::integral_constant<int, 3>{});
+            step(std::integral_constant<int, 4>{});  step(std::integral_constant<int, 5>{});
+            step(std::integral_constant<int, 6>{});  step(std::integral_constant<int, 7>{});
+            step(std::integral_constant<int, 8>{});  step(std::integral_constant<int, 9>{});
+            step(std::integral_constant<int, 10>{}); step(std::integral_constant<int, 11>{});
+            step(std::integral_constant<int, 12>{}); step(std::integral_constant<int, 13>{});
+            step(std::integral_constant<int, 14>{}); step(std::integral_constant<int, 15>{});
+#undef DKV_FENCE
+        };
+        tile_body(mask_c);
+    };
+    // tiles with q0 < kw0 + 31 hold queries that precede some of this wave's keys
+    const int n_mask = any_bad_key ? nq : (CAUSAL ? min(nq, (kw0 + 31 - q_start + KV_TILE - 1) / KV_TILE) : 0);
+    int j = 0;
+    for (int m = 0; m < group; ++m) {
+        int it = 0;
+        for (; it < n_mask; ++it, ++j) tile(j, it, std::true_type{});
+        for (; it < nq; ++it, ++j) tile(j, it, std::false_type{});
     }
     if (ag.epi) {
         char* stage = smem + (nit & 1) * 2 * TB + wave * (32 * D * 2);   // the buffer the last tile did not use
@@ -1368,46 +1311,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv2_kernel(const bf16_t* __rest
 }
 
 // ============================================================================================================
-static int attn_lpt_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_ATTN_LPT");      // K/V heads per bundle: 1 = head-major, large = slot-major over all heads
-        on = e ? atoi(e) : 8;
-        if (on < 1) on = 1;
-    }
-    return on;
-}
-static int attn_pipe_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_ATTN_PIPE");      // dK,dV kernel: LDS fragments requested this many half-units ahead (0 = unpipelined body)
-        on = e ? atoi(e) : 2;
-    }
-    return on;
-}
-static int attn_epi_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_ATTN_EPI");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
-    return on;
-}
+constexpr int ATTN_LPT = 8;      // AttnGrid::lpt: K/V heads per bundle of the block map (1 = head-major, large = slot-major over all heads)
 // ticket counters of the persistent kernels: one set per stream (the reference forward runs on a side stream beside the policy
 // forward), zero at rest - the kernels reset them on the way out
 #define ATTN_CTR_SLOTS 8
 static unsigned* attn_counters(hipStream_t st) {
-    static int on = -1;
+    static int on = -1;      // 0: no memory for the counters - every launch takes the plain grid
     static unsigned* buf = nullptr;
     static int buf_dev = -1;
     static hipStream_t streams[ATTN_CTR_SLOTS];
     static int nstreams = 0;
     if (on < 0) {
-        const char* e = getenv("VLR_ATTN_PERSIST");
-        on = (e && e[0] == '0') ? 0 : 1;
-        if (on && (hipGetDevice(&buf_dev) != hipSuccess ||
-                   hipMalloc((void**)&buf, ATTN_CTR_SLOTS * 8 * 32 * sizeof(unsigned)) != hipSuccess ||
-                   hipMemset(buf, 0, ATTN_CTR_SLOTS * 8 * 32 * sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) on = 0;
+        on = hipGetDevice(&buf_dev) == hipSuccess && hipMalloc((void**)&buf, ATTN_CTR_SLOTS * 8 * 32 * sizeof(unsigned)) == hipSuccess &&
+             hipMemset(buf, 0, ATTN_CTR_SLOTS * 8 * 32 * sizeof(unsigned)) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     }
     if (!on) return nullptr;
     int dev = -1;
@@ -1419,19 +1335,11 @@ static unsigned* attn_counters(hipStream_t st) {
     return buf + (size_t)(nstreams++) * 8 * 32;
 }
 static int attn_fwd3_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_ATTN_FWD3");      // 64 queries per wave, explicit issue order (attn_fwd3.h); 0 = the 32-query fwd2 kernel
-        on = e ? atoi(e) : 0;
-    }
+    static const int on = vlr_env_int("VLR_ATTN_FWD3", 0);      // 64 queries per wave, explicit issue order (attn_fwd3.h); 0 = the 32-query fwd2 kernel
     return on;
 }
 static int attn_dma_on() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_ATTN_DMA");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
+    static const int on = vlr_env_int("VLR_ATTN_DMA", 1);      // 0: the register-staged kernels at every length
     return on;
 }
 
@@ -1471,8 +1379,8 @@ extern "C" int vlr_attn_fwd_gqa(const void* q, const void* k, const void* v, int
     }
     AttnGrid ag;
     ag.heads = heads; ag.kv_heads = kv_heads; ag.group = heads / kv_heads; ag.nblk = (S + 127) / 128; ag.n_kvp = batch * kv_heads;
-    ag.epi = attn_epi_on();
-    ag.lpt = attn_lpt_on();
+    ag.epi = 1;
+    ag.lpt = ATTN_LPT;
     int fgrid = ag.grid(false);
     const int resident = 2 * vlr_compute_cus();       // workgroups the chip holds at once: two per CU, whole XCD octets (minus the CUs left to RCCL)
     ag.ctr = fgrid > resident ? attn_counters(st) : nullptr;   // more query blocks than that: persistent workgroups
@@ -1539,39 +1447,25 @@ extern "C" int vlr_attn_bwd_gqa(const void* q, const void* k, const void* v, int
         attr = true;
         hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
         hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
+        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
+        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
     }
     AttnGrid ag;
     ag.heads = heads; ag.kv_heads = kv_heads; ag.group = heads / kv_heads; ag.nblk = (S + 127) / 128; ag.n_kvp = batch * kv_heads;
-    ag.epi = attn_epi_on();
-    ag.lpt = attn_lpt_on();
+    ag.epi = 1;
+    ag.lpt = ATTN_LPT;
     ag.ctr = nullptr; ag.items = 0;
     if (dma) {
         if (causal) {
             hipLaunchKernelGGL((attn_bwd_dq2_kernel<true>), dim3(ag.grid(false)), dim3(256), LDS_DQ, st, (const bf16_t*)q, (const bf16_t*)k,
                                (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dq, ldd, S, Sp, scale, ag);
-#define DKV_LAUNCH(P_)                                                                                                    \
-    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, P_>), dim3(ag.grid(true)), dim3(256), LDS_DKV, st, (const bf16_t*)q, (const bf16_t*)k, \
-                       (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale, ag)
-            if (attn_pipe_on() >= 2) DKV_LAUNCH(2);
-            else if (attn_pipe_on() == 1) DKV_LAUNCH(1);
-            else DKV_LAUNCH(0);
-#undef DKV_LAUNCH
+            hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true>), dim3(ag.grid(true)), dim3(256), LDS_DKV, st, (const bf16_t*)q, (const bf16_t*)k,
+                               (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale, ag);
         } else {
             hipLaunchKernelGGL((attn_bwd_dq2_kernel<false>), dim3(ag.grid(false)), dim3(256), LDS_DQ, st, (const bf16_t*)q, (const bf16_t*)k,
                                (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dq, ldd, S, Sp, scale, ag);
-#define DKV_LAUNCH(P_)                                                                                                    \
-    hipLaunchKernelGGL((attn_bwd_dkv2_kernel<false, P_>), dim3(ag.grid(true)), dim3(256), LDS_DKV, st, (const bf16_t*)q, (const bf16_t*)k, \
-                       (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale, ag)
-            if (attn_pipe_on() >= 2) DKV_LAUNCH(2);
-            else if (attn_pipe_on() == 1) DKV_LAUNCH(1);
-            else DKV_LAUNCH(0);
-#undef DKV_LAUNCH
+            hipLaunchKernelGGL((attn_bwd_dkv2_kernel<false>), dim3(ag.grid(true)), dim3(256), LDS_DKV, st, (const bf16_t*)q, (const bf16_t*)k,
+                               (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale, ag);
         }
     } else if (causal) {
         hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,

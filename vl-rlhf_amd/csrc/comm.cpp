@@ -39,7 +39,7 @@ int find_loaded(struct dl_phdr_info* info, size_t, void* out) {
 int load_api() {
     if (g_api.handle) return VLR_OK;
     char loaded[512] = "";
-    const char* env = getenv("VLR_RCCL_LIB");
+    const char* env = vlr_env_str("VLR_RCCL_LIB");
     const char* cand[4] = {env, nullptr, "librccl.so.1", "/opt/rocm/lib/librccl.so"};
     dl_iterate_phdr(find_loaded, loaded);
     cand[1] = loaded[0] ? loaded : nullptr;

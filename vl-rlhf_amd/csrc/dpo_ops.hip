@@ -650,9 +650,7 @@ extern "C" int vlr_merge_index(const long* input_ids, const long* attention_mask
     VLR_REQUIRE(n_feat_rows > 0 && dup >= 1, "vlr_merge_index: n_feat_rows/dup");
     hipMemsetAsync(inv_map, 0xff, (size_t)dup * n_feat_rows * sizeof(int), st);
     hipMemsetAsync(info, 0, 2 * sizeof(int), st);
-    static int serial = -1;
-    if (serial < 0) { const char* e = getenv("VLR_MERGE_SERIAL"); serial = (e && e[0] == '1') ? 1 : 0; }
-    if (Bn <= 64 && !serial)
+    if (Bn <= 64)
         hipLaunchKernelGGL(merge_index_block_kernel, dim3(Bn), dim3(256), 0, st, input_ids, attention_mask, labels, Bn, T, S, P,
                            image_token, pad_token, n_feat_rows, dup, src, out_mask, out_labels, out_pos, img_map, inv_map, info);
     else
@@ -687,8 +685,7 @@ extern "C" int vlr_merge_bwd(const void* dmerged, const int* src, const int* inv
         static int emb2 = -1;
         constexpr size_t EMB2_LDS = 156 * 1024;                   // the positions' ids in LDS: up to 39936 positions (LLaVA-Next recipe: 8 x 4814)
         if (emb2 < 0) {
-            const char* e = getenv("VLR_MERGE_EMBED2");
-            emb2 = (e && e[0] == '0') ? 0 : 1;
+            emb2 = vlr_env_int("VLR_MERGE_EMBED2", 1) != 0;
             if (hipFuncSetAttribute((const void*)merge_bwd_embed2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EMB2_LDS) != hipSuccess) emb2 = 0;
         }
         if (emb2 && (size_t)npos * sizeof(int) <= EMB2_LDS)

@@ -72,16 +72,16 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__
 
 // RMSNorm backward.  dx = rstd * (dy*w - xhat * mean(dy*w*xhat)) (+ dres), dw partial[j] += dy*xhat.
 // Workgroup b walks rows b, b+G, ...; its dw partial goes to dw_part[b][H] (reduced by reduce_partials_kernel).
-// EARLY: the residual-gradient addend of a row is loaded with dy / x, in front of the block reduction, instead of behind it (one exposed
-// memory latency per row less; the same values in the same operations)
+// The residual-gradient addend of a row is loaded with dy / x, in front of the block reduction, not behind it (one exposed memory
+// latency per row less).
 // MAXC: 8-column chunks per thread the register arrays are sized for (H <= 2048 MAXC): with 4 for every H the 7B width (2 used) cost 150
 // registers = 3 waves per SIMD; MAXC = 2 leaves room for more rows in flight per CU (the same instructions on the same values)
-template <typename XT, bool EARLY, int MAXC>
+template <typename XT, int MAXC>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const XT* __restrict__ x,
                                                           const bf16_t* __restrict__ w, const float* __restrict__ rstd,
                                                           const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
                                                           float* __restrict__ dw_part, int M, int H, int row0, int part0) {
-    // rows [row0, M); the workgroup's dw partial goes to row part0 + blockIdx.x of dw_part (two launches over two row ranges share one reduction)
+    // rows [row0, M); the workgroup's dw partial goes to row part0 + blockIdx.x of dw_part (the one launch there is passes row0 = part0 = 0)
     __shared__ float red[16];
     float dwacc[MAXC][8];      // H <= 256*8*MAXC
 #pragma unroll
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
             const int c = (i * 256 + threadIdx.x) * 8;
             if (c < H) {
                 float a[8], b[8], g[8];
-                if constexpr (EARLY) { if (dres) rraw[i] = *reinterpret_cast<const u32x4*>(dres + off + c); }
+                if (dres) rraw[i] = *reinterpret_cast<const u32x4*>(dres + off + c);
                 unpack8(*reinterpret_cast<const u32x4*>(dy + off + c), a);
                 load8(x + off + c, b);
                 unpack8(*reinterpret_cast<const u32x4*>(w + c), g);
@@ -122,8 +122,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
                 for (int e = 0; e < 8; ++e) o[e] = rs * (gx[i][e] - xh[i][e] * dot);
                 if (dres) {
                     float r[8];
-                    if constexpr (EARLY) unpack8(rraw[i], r);
-                    else unpack8(*reinterpret_cast<const u32x4*>(dres + off + c), r);
+                    unpack8(rraw[i], r);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] += r[e];
                 }
@@ -689,15 +688,10 @@ static inline int grid_for(long n, int per_block, int cap = 256 * 16) {
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-static bool norm_fwd_reg() {      // VLR_NORM_FWD_REG=0: the two-pass kernel (A/B; bit-identical)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("VLR_NORM_FWD_REG"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
 extern "C" int vlr_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps,
                                hipStream_t st) {
     VLR_REQUIRE(M > 0 && H > 0 && H % 8 == 0, "vlr_rmsnorm_fwd: bad shape M=%d H=%d", M, H);
-    if (H <= 8192 && norm_fwd_reg())
+    if (H <= 8192)      // the row stays in registers between the two passes; wider rows are read twice
         hipLaunchKernelGGL((rmsnorm_fwd_kernel<bf16_t, true>), dim3(M), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps);
     else
         hipLaunchKernelGGL((rmsnorm_fwd_kernel<bf16_t, false>), dim3(M), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps);
@@ -707,7 +701,7 @@ extern "C" int vlr_rmsnorm_fwd(const void* x, const void* w, void* y, float* rst
 extern "C" int vlr_rmsnorm_fwd_f32(const float* x, const void* w, void* y, float* rstd, int M, int H, float eps, hipStream_t st) {
     VLR_REQUIRE(x && w && y, "vlr_rmsnorm_fwd_f32: null argument");
     VLR_REQUIRE(M > 0 && H > 0 && H % 8 == 0, "vlr_rmsnorm_fwd_f32: bad shape M=%d H=%d", M, H);
-    if (H <= 8192 && norm_fwd_reg())
+    if (H <= 8192)
         hipLaunchKernelGGL((rmsnorm_fwd_kernel<float, true>), dim3(M), dim3(256), 0, st, x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps);
     else
         hipLaunchKernelGGL((rmsnorm_fwd_kernel<float, false>), dim3(M), dim3(256), 0, st, x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps);
@@ -721,8 +715,7 @@ extern "C" int vlr_rmsnorm_fwd_f32(const float* x, const void* w, void* y, float
 extern "C" int vlr_rmsnorm_bwd_workspace_bytes(int H) { return (VLR_NORM_BWD_BLOCKS + VLR_NORM_BWD_STAGE2) * H * 4; }
 
 static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void* w, const float* rstd, const void* dres,
-                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st, int M1 = 0,
-                            hipEvent_t tail_done = nullptr);
+                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st);
 extern "C" int vlr_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres,
                                void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
     return rmsnorm_bwd_impl(dy, x, 0, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st);
@@ -732,40 +725,22 @@ extern "C" int vlr_rmsnorm_bwd_f32(const void* dy, const float* x, const void* w
                                    void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
     return rmsnorm_bwd_impl(dy, x, 1, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st);
 }
-// M1 > 0 (vlr_internal_rmsnorm_bwd_split, common.h: VlrGemmTail): rows [0, M1) now, rows [M1, M) once `tail_done` has fired on the
-// stream - the producer's peeled rows were still being computed on a side stream - and ONE reduction of the dw partials of both launches
 static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void* w, const float* rstd, const void* dres,
-                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st, int M1,
-                            hipEvent_t tail_done) {
+                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
     VLR_REQUIRE(dy && x && w && rstd && dx, "vlr_rmsnorm_bwd: null argument");
     VLR_REQUIRE(M > 0 && H % 8 == 0 && H <= 8192, "vlr_rmsnorm_bwd: bad shape M=%d H=%d (H<=8192)", M, H);
     VLR_REQUIRE(workspace, "vlr_rmsnorm_bwd: workspace of vlr_rmsnorm_bwd_workspace_bytes(H) required");
-    VLR_REQUIRE(M1 >= 0 && M1 < M, "vlr_rmsnorm_bwd: split row %d outside [0, %d)", M1, M);
-    auto launch = [&](int row0, int rows_end, int G, int part0) {
-        static int early = -1;      // VLR_NORM_BWD_EARLY=0: the addend loaded behind the reduction (A/B; bit-identical)
-        if (early < 0) { const char* e = getenv("VLR_NORM_BWD_EARLY"); early = (e && e[0] == '0') ? 0 : 1; }
-#define NORM_BWD_LAUNCH(XT_, E_)                                                                                                       \
+    const int G = M < VLR_NORM_BWD_BLOCKS ? M : VLR_NORM_BWD_BLOCKS;
+#define NORM_BWD_LAUNCH(XT_)                                                                                                           \
     do {                                                                                                                               \
-        if (H <= 4096) hipLaunchKernelGGL((rmsnorm_bwd_kernel<XT_, E_, 2>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,  \
-                                          (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, rows_end, H, row0, part0); \
-        else hipLaunchKernelGGL((rmsnorm_bwd_kernel<XT_, E_, 4>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,          \
-                                (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, rows_end, H, row0, part0); \
+        if (H <= 4096) hipLaunchKernelGGL((rmsnorm_bwd_kernel<XT_, 2>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,    \
+                                          (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, M, H, 0, 0);    \
+        else hipLaunchKernelGGL((rmsnorm_bwd_kernel<XT_, 4>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,              \
+                                (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, M, H, 0, 0);              \
     } while (0)
-        if (x_f32) { if (early) NORM_BWD_LAUNCH(float, true); else NORM_BWD_LAUNCH(float, false); }
-        else { if (early) NORM_BWD_LAUNCH(bf16_t, true); else NORM_BWD_LAUNCH(bf16_t, false); }
+    if (x_f32) NORM_BWD_LAUNCH(float);
+    else NORM_BWD_LAUNCH(bf16_t);
 #undef NORM_BWD_LAUNCH
-    };
-    int G = M < VLR_NORM_BWD_BLOCKS ? M : VLR_NORM_BWD_BLOCKS;
-    if (M1 > 0) {
-        const int GB = (M - M1) < 64 ? (M - M1) : 64;
-        const int GA = M1 < VLR_NORM_BWD_BLOCKS - GB ? M1 : VLR_NORM_BWD_BLOCKS - GB;
-        launch(0, M1, GA, 0);
-        if (tail_done) hipStreamWaitEvent(st, tail_done, 0);
-        launch(M1, M, GB, GA);
-        G = GA + GB;
-    } else {
-        launch(0, M, G, 0);
-    }
     if (dw) {
         float* part2 = (float*)workspace + (size_t)VLR_NORM_BWD_BLOCKS * H;
         const int S2 = G < VLR_NORM_BWD_STAGE2 ? 1 : VLR_NORM_BWD_STAGE2;
@@ -774,10 +749,6 @@ static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void
                            (bf16_t*)dw, dw_accumulate);
     }
     return vlr_check_launch("vlr_rmsnorm_bwd");
-}
-int vlr_internal_rmsnorm_bwd_split(const void* dy, const void* x, int x_f32, const void* w, const float* rstd, const void* dres, void* dx,
-                                   void* dw, int dw_accumulate, void* workspace, int M, int H, int M1, hipEvent_t tail_done, hipStream_t st) {
-    return rmsnorm_bwd_impl(dy, x, x_f32, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st, M1, tail_done);
 }
 
 #define VLR_COLSUM_ROWS 64

@@ -15,7 +15,7 @@ struct GemmParams {
     int act;
     int accumulate;  // C += result (C read in its own dtype)
     int out_f32;
-    int flags;       // tuning experiments (VLR_GEMM_FLAGS), 0 in production
+    int flags;       // tuning experiments (VLR_GEMM_FLAGS of the --ablation build), 0 in the product
     float alpha;     // v = act(alpha * acc + bias) + residual (+ C)
     int splitk;      // > 1: blockIdx.y = K-slice z of kchunk elements, raw alpha*acc -> part[z][M][N] fp32 (128x128 kernel only)
     int kchunk;
@@ -104,7 +104,7 @@ struct GemmParams {
     const int* ktlist;
 #ifdef VLR_GEMM_TRACE
     uint32_t* trace;         // diagnostics build only: set by the launchers of gemm256p.hip (vlr_gemm_set_trace), never by callers
-    int dephase_p, dephase_ticks, epi_abl, trace_clk;
+    int epi_abl, trace_clk;
 #endif
 };
 #define VLR_SCHED_DEFAULT 32          // GemmParams::sched when VLR_GEMM_SCHED is not set: the shared-panel tile map (gemm_tilemap.h, round 5)
@@ -118,7 +118,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 
 
 // 256x256 tile, eight-phase schedule (gemm256p.hip); returns false when the problem does not qualify (fewer than 192 tiles,
-// unaligned operands, VLR_GEMM_8PHASE=0): the caller falls back to the 128x128 kernel
+// unaligned operands): the caller falls back to the 128x128 kernel
 bool vlr_gemm256p_try_launch(int layout, const GemmParams& p, hipStream_t stream);
 // 128x128 tile on the LDS-DMA ring (gemm128p.hip), grid = (tiles, split-K slices, groups) of gemm_bf16_kernel; false: operands it does
 // not take (alignment, masked / dropout-accumulate launches) or VLR_GEMM128P=0 - the caller launches gemm_bf16_kernel

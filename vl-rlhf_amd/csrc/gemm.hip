@@ -430,7 +430,7 @@ extern "C" int vlr_gemm_set_splitk_workspace(void* ws, long bytes) {
 // rotation, XCD round barrier) measured slower or neutral and were removed.
 static int g_sched = -1;
 int vlr_gemm_sched_mode() {
-    if (g_sched < 0) { const char* e = getenv("VLR_GEMM_SCHED"); g_sched = e ? (atoi(e) & 56) : VLR_SCHED_DEFAULT; }
+    if (g_sched < 0) g_sched = vlr_env_int("VLR_GEMM_SCHED", VLR_SCHED_DEFAULT) & 56;
     return g_sched;
 }
 extern "C" int vlr_gemm_set_sched(int mode) {
@@ -464,13 +464,12 @@ static void launch128(int layout, const GemmParams& p, dim3 grid, hipStream_t st
     else if (layout == 1) hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, dim3(256), 0, stream, p);
 }
+constexpr int SPLITK_TARGET = 512;       // workgroups a split-K launch (plain or grouped) aims at: 2 per CU
 static bool launch_splitk128(int layout, GemmParams p, hipStream_t stream, int min_k) {
     if (p.N % 4 != 0 || p.K < min_k) return false;
     const int tiles128 = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     if (tiles128 >= 256) return false;
-    static int target = -1;       // workgroups a split launch aims at (VLR_SPLITK_TARGET; 2 per CU)
-    if (target < 0) { const char* e = getenv("VLR_SPLITK_TARGET"); target = e ? atoi(e) : 512; if (target < 64) target = 512; }
-    int splits = target / tiles128;
+    int splits = SPLITK_TARGET / tiles128;
     if (splits > 16) splits = 16;
     if (splits > p.K / 256) splits = p.K / 256;
     if (splits < 2) return false;
@@ -514,10 +513,8 @@ static int gemm_grouped(int layout, const void* A, const void* B, void* C, int M
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
     int splits = 1;
     float* ws = nullptr;
-    static int gtarget = -1;      // workgroups a grouped launch aims at when it splits along K (VLR_GROUPED_TARGET)
-    if (gtarget < 0) { const char* e = getenv("VLR_GROUPED_TARGET"); gtarget = e ? atoi(e) : 512; if (gtarget < 64) gtarget = 512; }
-    if (tiles * groups < gtarget * 3 / 4 && K >= 1024) {
-        splits = gtarget / (tiles * groups);       // (rounded down on purpose: 2 x 300 workgroups of half the depth measured slower than 300 whole ones)
+    if (tiles * groups < SPLITK_TARGET * 3 / 4 && K >= 1024) {
+        splits = SPLITK_TARGET / (tiles * groups);       // (rounded down on purpose: 2 x 300 workgroups of half the depth measured slower than 300 whole ones)
         if (splits > 16) splits = 16;
         if (splits > K / 256) splits = K / 256;
         ws = splits >= 2 ? splitk_slot(stream) : nullptr;
@@ -656,9 +653,6 @@ static int gemm_impl(int layout, const void* A, const void* B, void* C, const vo
 // most tile rows a launch may give to the 128x128 kernel: 3 on the whole chip (the shapes of the path were tuned with it), 6 when CUs are left
 // to RCCL - 240-CU rounds fit the 7B shapes worse (12792 x 4096: 800 tiles = 3.33 rounds; 45 tile rows = 3 rounds exactly + 1272 rows peeled)
 static int peel_max(int ncu) {
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("VLR_PEEL_MAX"); env = e ? atoi(e) : 0; if (env < 0 || env > 8) env = 0; }
-    if (env) return env;
     int dev = 0, cus = 0;
     static int dev_cus = 0;
     if (!dev_cus) dev_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 8) ? (cus & ~7) : 256;
@@ -736,12 +730,9 @@ extern "C" int vlr_gemm_bf16_tn_pair(const void* A0, const void* B0, void* C0, i
     const int Ms[2] = {M0, M1};
     int sep, bq, br;
     const double best = tn_pair_plan(M0, N0, M1, N1, &sep, &bq, &br);
-    static int pair_on = -1;
-    if (pair_on < 0) { const char* e = getenv("VLR_GEMM_PAIR"); pair_on = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
     // the joint launch was measured neutral at equal round counts on the LLaVA-7B shapes only - shapes that were never A/B'd
-    // take it when it SAVES at least a quarter of a round (the criterion of vlr_internal_tn_pair_saves' callers); VLR_GEMM_PAIR=2: also at equal counts
-    const double need = pair_on == 2 ? -1e-9 : 0.25;
-    if (pair_on && !accumulate && (double)sep - best >= need && K % 8 == 0) {
+    // take it when it SAVES at least a quarter of a round (the criterion of vlr_internal_tn_pair_saves' callers)
+    if (!accumulate && (double)sep - best >= 0.25 && K % 8 == 0) {
         GemmParams p[2] = {fused_params(A0, B0, C0, M0, N0, K, lda0, ldb0, ldc0), fused_params(A1, B1, C1, M1, N1, K, lda1, ldb1, ldc1)};
         GemmParams rest = p[bq];
         if (br) {
@@ -772,14 +763,9 @@ extern "C" int vlr_gemm_bf16_f32res(int layout, const void* A, const void* B, fl
     return gemm_impl_ex(layout, A, B, C, nullptr, residual, M, N, K, lda, ldb, ldc, ldr, 0, 0, 1, 1.0f, 1, stream);
 }
 
-static VlrGemmTail* g_gemm_tail = nullptr;
-void vlr_internal_set_gemm_tail(VlrGemmTail* t) { g_gemm_tail = t; if (t) { t->used = 0; t->M1 = 0; } }
-
 static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const void* bias, const void* residual, int M, int N,
                         int K, int lda, int ldb, int ldc, int ldr, int act, int accumulate, int out_f32, float alpha, int res_f32,
                         hipStream_t stream) {
-    VlrGemmTail* tail = g_gemm_tail;      // (common.h) consumed by this call whatever path it takes
-    g_gemm_tail = nullptr;
     VLR_REQUIRE(!res_f32 || out_f32, "vlr_gemm_bf16: an fp32 residual needs an fp32 output");
     VLR_REQUIRE(layout >= 0 && layout <= 2, "vlr_gemm_bf16: layout must be 0 (NT), 1 (NN) or 2 (TN), got %d", layout);
     VLR_REQUIRE(M > 0 && N > 0 && K > 0, "vlr_gemm_bf16: empty problem M=%d N=%d K=%d", M, N, K);
@@ -798,9 +784,12 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     p.bias = (const bf16_t*)bias; p.residual = (const bf16_t*)residual;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr;
     p.act = act; p.accumulate = accumulate; p.out_f32 = out_f32;
-    static int gflags = -1;
-    if (gflags < 0) { const char* e = getenv("VLR_GEMM_FLAGS"); gflags = e ? atoi(e) : 0; }
+#ifdef VLR_GEMM_ABLATION      // diagnostics build (tools/gemm_sweep.sh): bits that take work out of the 128x128 kernel - timing only, wrong results
+    static const int gflags = vlr_diag_env_int("VLR_GEMM_FLAGS", 0);
     p.flags = gflags;
+#else
+    p.flags = 0;
+#endif
     p.alpha = alpha;
     p.splitk = 1; p.kchunk = 0; p.part = nullptr;
     p.fuse = 0; p.store_c = 1; p.C2 = nullptr; p.ldc2 = 0; p.pos = nullptr; p.rope_cos = p.rope_sin = nullptr; p.max_pos = 0; p.rope_cols = 0;
@@ -827,13 +816,11 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     }
     // ---- wave quantisation: a 256x256-tile grid of T tiles runs ceil(T/256) rounds on the 256 CUs; when the last round is
     // nearly empty (e.g. 12792 x 4096 -> 800 tiles = 3.125 rounds) the last tile-rows are peeled off and run as 128x128
-    // tiles (2 workgroups per CU) so the big-tile part is a whole number of rounds.  VLR_GEMM_SPLIT=0 disables.
-    static int split_on = -1;
-    if (split_on < 0) { const char* e = getenv("VLR_GEMM_SPLIT"); split_on = (e && e[0] == '0') ? 0 : 1; }
+    // tiles (2 workgroups per CU) so the big-tile part is a whole number of rounds.
     const int tm256 = (M + 255) / 256, tn256 = (N + 255) / 256;
     // (launches that take the per-tile kernel - bias, activation, accumulate, a bf16 residual - cannot use the stream-K tail: peel as before)
     const bool sk_elig = !bias && !accumulate && act == ACT_NONE && (out_f32 || !residual);
-    const int peel = split_on ? choose_peel(M, N, tn256, sk_elig ? K : 0, stream) : 0;
+    const int peel = choose_peel(M, N, tn256, sk_elig ? K : 0, stream);
     if (peel) {
         const int M1 = (tm256 - peel) * 256;
         GemmParams p1 = p, p2 = p;
@@ -845,21 +832,9 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
         if (p.residual) p2.residual = (const bf16_t*)((const char*)p.residual + (size_t)M1 * ldr * (p.res_f32 ? 4 : 2));
         if (vlr_gemm256p_try_launch(layout, p1, stream)) {
             const int t2 = ((p2.M + BM - 1) / BM) * ((N + BN - 1) / BN);
-            // the peeled rows on the caller's side stream (VlrGemmTail, common.h): behind the main part, beside the caller's next kernel
-            hipStream_t ps = stream;
-            if (tail) {
-                hipEventRecord(tail->fork, stream);
-                hipStreamWaitEvent(tail->side, tail->fork, 0);
-                ps = tail->side;
-            }
             // the peeled rows are few tiles with the full reduction depth (e.g. 504 x 4096 x 22016 = 128 tiles x 688 k-steps):
             // split them along K so that they fill the chip
-            if (!launch_splitk128(layout, p2, ps, 4096)) launch128(layout, p2, dim3(t2), ps);
-            if (tail) {
-                hipEventRecord(tail->done, ps);
-                tail->M1 = M1;
-                tail->used = 1;
-            }
+            if (!launch_splitk128(layout, p2, stream, 4096)) launch128(layout, p2, dim3(t2), stream);
             vlr_prof_end(pi, stream);
             return vlr_check_launch("vlr_gemm_bf16(256+128)");
         }
@@ -1109,18 +1084,16 @@ extern "C" int vlr_gemm_dropout_acc_bits(const void* v, int ldv, const void* A, 
     g.drop_key = vlr_mix64(seed); g.drop_thr = vlr_dropout_thr(p); g.drop_ld = in; g.drop_bits = (const unsigned char*)bits;
     // K is the adapter rank: the launch is one read-modify-write pass over dx with a few MFMAs per tile.  The 256x256 kernel holds one
     // tile per CU and its load - add - store of the 128 KB output tile is exposed (157 us per [12792 x 4096] launch = 1.3 TB/s);
-    // the 128x128 kernel keeps several workgroups per CU in flight and adds in fp32 before the one rounding.  VLR_GEMM_DROPACC: 2 (default)
-    // 128x128, 1 256x256, 0 product + dropout-accumulate kernel
-    static int mode = -1;
-    if (mode < 0) { const char* e = getenv("VLR_GEMM_DROPACC"); mode = e ? atoi(e) : 2; }
-    if (mode == 2 && in % 8 == 0 && !(((uintptr_t)v | (uintptr_t)A | (uintptr_t)dx) & 15)) {
+    // the 128x128 kernel keeps several workgroups per CU in flight and adds in fp32 before the one rounding.  So, by eligibility:
+    // 128x128 (16-byte aligned operands), else 256x256, else product + dropout-accumulate kernel
+    if (!(((uintptr_t)v | (uintptr_t)A | (uintptr_t)dx) & 15)) {
         const int tiles = ((M + BM - 1) / BM) * ((in + BN - 1) / BN);
         const int pi = vlr_prof_begin(1, 2.0 * M * in * r, stream);
         hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), dim3(tiles), dim3(256), 0, stream, g);
         vlr_prof_end(pi, stream);
         return vlr_check_launch("vlr_gemm_dropout_acc(128)");
     }
-    if (mode && vlr_gemm256p_dropacc_try_launch(g, stream)) return vlr_check_launch("vlr_gemm_dropout_acc(fused)");
+    if (vlr_gemm256p_dropacc_try_launch(g, stream)) return vlr_check_launch("vlr_gemm_dropout_acc(fused)");
     int rc = gemm_impl(1, v, A, scratch, nullptr, nullptr, M, in, r, ldv, in, in, 0, 0, 0, 0, 1.0f, stream);
     if (rc != VLR_OK) return rc;
     return vlr_dropout(scratch, dx, (long)M * in, p, seed, scale, 1, stream);
@@ -1278,8 +1251,6 @@ extern "C" long vlr_lmhead_workspace_bytes(int R, int V) { return ((long)R * vlr
 
 // 1 if the fused kernels take (R, V, H): the caller then needs no fp32 logits buffer
 extern "C" int vlr_lmhead_is_fused(int R, int V, int H) {
-    const char* e = getenv("VLR_GEMM_FUSE");
-    if (e && !((atoi(e) >> 3) & 1)) return 0;
     const long ntiles = (long)((R + 255) / 256) * ((V + 255) / 256);
     return ntiles > vlr_compute_cus() && H >= 256 && H % 8 == 0 && V % 8 == 0;     // the predicate of vlr_gemm256p_lmhead_try_launch
 }

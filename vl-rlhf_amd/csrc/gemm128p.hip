@@ -328,8 +328,7 @@ static bf16_t* q_zero16() {
 static int q_stages() {
     static int nst = -1;
     if (nst < 0) {
-        const char* e = getenv("VLR_GEMM128P");
-        nst = e ? atoi(e) : 2;
+        nst = vlr_env_int("VLR_GEMM128P", 2);
         if (nst == 1 || nst > 4 || nst < 0) nst = 2;
     }
     return nst;

@@ -269,21 +269,10 @@ static uint32_t* g_trace = nullptr;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         \
         }                                                                              \
     } while (0)
-// VLR_GEMM_DEPHASE="P,D" (trace build only): workgroup b idles ((b * 7) % P) * D / P microseconds before its first tile - an experiment
-// on whether the epilogue bursts of workgroups that run in phase are what an epilogue costs
-static int g_dephase_p = -1, g_dephase_ticks = 0;
 static void trace_set(GemmParams& p) {
-    if (g_dephase_p < 0) {
-        g_dephase_p = 0;
-        const char* e = getenv("VLR_GEMM_DEPHASE");
-        int a = 0, b = 0;
-        if (e && sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { g_dephase_p = a; g_dephase_ticks = b * 100; }
-    }
-    static int abl = -1;
-    if (abl < 0) { const char* e = getenv("VLR_EPI_ABLATE"); abl = e ? atoi(e) : 0; }      // timing only (wrong results): 1 no epilogue loads, 2 no epilogue stores
-    static int clk = -1;
-    if (clk < 0) { const char* e = getenv("VLR_GEMM_TRACE_CLK"); clk = (e && e[0] == '1') ? 1 : 0; }      // 1: stamps of the SHADER clock (s_memtime) - cycles instead of 10 ns ticks
-    p.trace = g_trace; p.dephase_p = g_dephase_p; p.dephase_ticks = g_dephase_ticks; p.epi_abl = abl; p.trace_clk = clk;
+    static const int abl = vlr_diag_env_int("VLR_EPI_ABLATE", 0);         // timing only (wrong results): 1 no epilogue loads, 2 no epilogue stores
+    static const int clk = vlr_diag_env_int("VLR_GEMM_TRACE_CLK", 0);     // 1: stamps of the SHADER clock (s_memtime) - cycles instead of 10 ns ticks
+    p.trace = g_trace; p.epi_abl = abl; p.trace_clk = clk != 0;
 }
 #define TRACE_SET(p_) trace_set(p_)
 #define EPI_LD_ON (!(p.epi_abl & 1))
@@ -431,12 +420,6 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
     }
     __syncthreads();
     if (npieces <= 0) return;
-#ifdef VLR_GEMM_TRACE
-    if (CONT && p.dephase_p > 0) {
-        const uint64_t until = __builtin_amdgcn_s_memrealtime() + (uint64_t)(((int)blockIdx.x * 7) % p.dephase_p) * p.dephase_ticks / p.dephase_p;
-        while (__builtin_amdgcn_s_memrealtime() < until) __builtin_amdgcn_s_sleep(16);
-    }
-#endif
     TSTAMP((PTAB_PIECES - 1) * 8 + 5);
     int parb = 0;                 // CONT: buffer parity of the current piece's K tile 0 (K tiles keep alternating across pieces)
     for (int titer = 0;; ++titer) {
@@ -483,7 +466,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
 
     const int a2off = (!SEG || FUSE == 1) ? 0 : (n0 >= p.seg_b0 ? (n0 >= p.seg_b1 ? 2 : 1) : 0) * p.K2;
     // half h of K tile `tile`: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi
-    // diagnostics (template ABL via VLR_GEMM_ABLATE, NT only, timing only - results are wrong): 1 no DMA in the K loop,
+    // diagnostics (template ABL, the --ablation build's VLR_GEMM_ABLATE, NT only, timing only - results are wrong): 1 no DMA in the K loop,
     // 2 no fragment reads after the first K tile, 4 no barriers in the K loop
     constexpr bool abl_dma = ABL & 1, abl_rd = ABL & 2, abl_bar = ABL & 4;
     bool in_loop = false;
@@ -1550,15 +1533,13 @@ static void sched_prepare(GemmParams& p) { p.sched = vlr_gemm_sched_mode() & (24
 
 bool vlr_gemm256p_fused_try_launch(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_FUSE");
-        on = e ? atoi(e) : 3;               // bit 0 SwiGLU, bit 1 RoPE
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
-    if (p.fuse == 3) return false;       // NN: vlr_gemm256p_swiglu_bwd_try_launch
-    if (p.fuse < 1 || p.fuse > 2 || !((on >> (p.fuse - 1)) & 1)) return false;
+    if (p.fuse < 1 || p.fuse > 2) return false;       // SwiGLU, RoPE (3, NN: vlr_gemm256p_swiglu_bwd_try_launch)
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     const int n_cu = gemm256p_n_cu();
@@ -1584,15 +1565,14 @@ bool vlr_gemm256p_fused_try_launch(const GemmParams& p_in, hipStream_t stream) {
 bool vlr_gemm256p_seg_try_launch(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
     sched_prepare(p);
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_SEG");
-        on = (e && e[0] == '0') ? 0 : 1;
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
-    if (!on || p.fuse < 0 || p.fuse > 2 || p.K2 <= 0 || !p.A2 || !p.B2) return false;
+    if (p.fuse < 0 || p.fuse > 2 || p.K2 <= 0 || !p.A2 || !p.B2) return false;
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     const int n_cu = gemm256p_n_cu();
@@ -1624,13 +1604,12 @@ bool vlr_gemm256p_seg_try_launch(const GemmParams& p_in, hipStream_t stream) {
 bool vlr_gemm256p_dropacc_try_launch(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
     TRACE_SET(p);
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_DROPACC");
-        on = (e && e[0] == '0') ? 0 : 1;
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, false, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
     }
-    if (!on || p.fuse != 6) return false;
+    if (p.fuse != 6) return false;
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     const int n_cu = gemm256p_n_cu();
@@ -1646,13 +1625,11 @@ bool vlr_gemm256p_dropacc_try_launch(const GemmParams& p_in, hipStream_t stream)
 // d act = dy . Wdown (NN) with the SwiGLU backward in the epilogue: p.C2 = gate | up [M][2I] (in/out), p.N = I, p.C unused
 bool vlr_gemm256p_swiglu_bwd_try_launch(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_FUSE");
-        on = e ? ((atoi(e) >> 2) & 1) : 1;               // bit 2
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
-    if (!on) return false;
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     const int n_cu = gemm256p_n_cu();
@@ -1683,13 +1660,12 @@ extern "C" int vlr_gemm_set_trace(void* buf, long bytes) {
 // Two TN problems of equal K as ONE persistent launch of the grouped continuous-pipeline kernel (template GRP): C0 = A0^T B0 and
 // C1 = A1^T B1, plain bf16 outputs.  false: the caller launches them one by one.
 bool vlr_gemm256p_tn_pair_try_launch(const GemmParams& p0, const GemmParams& p1, hipStream_t stream) {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_PAIR");
-        on = (e && e[0] == '0') ? 0 : 1;
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<true, true, 0, true, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
-    if (!on || p0.K != p1.K || p0.K < 4 * PK) return false;
+    if (p0.K != p1.K || p0.K < 4 * PK) return false;
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     for (const GemmParams* q : {&p0, &p1}) {
@@ -1713,19 +1689,18 @@ int vlr_gemm256p_lmhead_parts(int V) { return ((V + PT - 1) / PT) * 4; }
 
 bool vlr_gemm256p_lmhead_try_launch(const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLR_GEMM_FUSE");
-        on = e ? ((atoi(e) >> 3) & 1) : 1;               // bit 3
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
-    if (!on || (p.fuse != 4 && p.fuse != 5)) return false;
+    if (p.fuse != 4 && p.fuse != 5) return false;
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
     const int n_cu = gemm256p_n_cu();
     const int ntiles = ((p.M + PT - 1) / PT) * ((p.N + PT - 1) / PT);
-    if (ntiles <= n_cu || persist_grid(ntiles, n_cu) != n_cu || p.K < 4 * PK) return false;
+    if (ntiles <= n_cu || persist_grid(ntiles, n_cu) != n_cu || p.K < 4 * PK) return false;      // (vlr_lmhead_is_fused, gemm.hip, states the same predicate)
     if ((((uintptr_t)p.A | (uintptr_t)p.B) & 15) || p.lda % 8 != 0 || p.ldb % 8 != 0 || p.N % 8 != 0) return false;
     if (p.fuse == 5 && (p.ldc % 8 != 0 || ((uintptr_t)p.C & 15))) return false;
     sched_prepare(p);
@@ -1742,28 +1717,22 @@ bool vlr_gemm256p_try_launch(int layout, const GemmParams& p_in, hipStream_t str
     GemmParams p = p_in;
     sched_prepare(p);
     TRACE_SET(p);
-    static int mode = -1;
+    static int ready = -1;      // 0: no memory for the zero source of the DMA tails - nothing runs on this kernel
     static bf16_t* zero16 = nullptr;
-    if (mode < 0) {
-        const char* e = getenv("VLR_GEMM_8PHASE");
-        mode = e ? atoi(e) : 7;            // bit 0 NT, bit 1 NN, bit 2 TN
-        if (mode) {
-            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
-            hipFuncSetAttribute((const void*)gemm256p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
-            hipFuncSetAttribute((const void*)gemm256p_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
-            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
-            hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
-            hipFuncSetAttribute((const void*)gemm256p_kernel<true, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
-            if (hipMalloc((void**)&zero16, 256) != hipSuccess || hipMemset(zero16, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess) mode = 0;
-        }
+    if (ready < 0) {
+        ready = 1;
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<true, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        if (hipMalloc((void**)&zero16, 256) != hipSuccess || hipMemset(zero16, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess) ready = 0;
     }
-    if (!((mode >> layout) & 1)) return false;
+    if (!ready) return false;
     const int ntiles = ((p.M + PT - 1) / PT) * ((p.N + PT - 1) / PT);
     if (ntiles < 192) return false;
-    static int persist = -1;
-    if (persist < 0) { const char* e = getenv("VLR_GEMM_PERSIST"); persist = (e && e[0] == '0') ? 0 : 1; }
-    const int n_cu = persist ? gemm256p_n_cu() : (1 << 30);
-    const int tiles = persist_grid(ntiles, n_cu);   // grid size: persistent workgroups when there are more tiles than CUs
+    const int tiles = persist_grid(ntiles, gemm256p_n_cu());   // grid size: persistent workgroups when there are more tiles than CUs
     // 16-byte DMA source alignment: k-contiguous operands need ld % 8 and K % 8 (checked by the caller), k-strided
     // operands ld % 8 and at least 8 columns; pointers 16-byte aligned
     const bool a_ks = layout == 2, b_ks = layout != 0;
@@ -1772,33 +1741,26 @@ bool vlr_gemm256p_try_launch(int layout, const GemmParams& p_in, hipStream_t str
     if (b_ks && (p.ldb % 8 != 0 || p.N % 8 != 0)) return false;
     if (!a_ks && p.lda % 8 != 0) return false;
     if (!b_ks && p.ldb % 8 != 0) return false;
-    static int abl = -1;
-    if (abl < 0) { const char* e = getenv("VLR_GEMM_ABLATE"); abl = e ? atoi(e) : 0; }
+#ifdef VLR_GEMM_ABLATION      // diagnostics build (tools/gemm_ceiling.sh): K-loop variants with work taken out - timing only, wrong results
+    static const int abl = vlr_diag_env_int("VLR_GEMM_ABLATE", 0);
     if (layout == 0 && abl) {
 #define PABL(n) case n: hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, n>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES); \
         hipLaunchKernelGGL((gemm256p_kernel<false, false, n>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16); return true;
         switch (abl) { PABL(1) PABL(4) PABL(5) PABL(8) default: break; }   // 2, 3, 6, 7 (no fragment reads) spill; 8 = no epilogue
 #undef PABL
     }
+#endif
     // timed as its own kernel id by the in-library profiler (bench.py quotes the roofline of THIS kernel)
     const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
     // continuous pipeline across tiles: persistent launch, plain bf16 epilogue (C = alpha * A B), at least 4 K tiles
-    static int cont = -1;
-    if (cont < 0) { const char* e = getenv("VLR_GEMM_CONT"); cont = (e && e[0] == '0') ? 0 : 1; }
-    static int cont_res = -1;
-    // residual epilogue on the continuous pipeline: OFF by default - measured 1.4 ms per step SLOWER than the LDS-image epilogue of
-    // the per-tile kernel (635.8 vs 634.4 ms, same box, bit-identical losses): its 8-byte residual reads sit between the K loop and
+    // a bf16 residual stays on the per-tile kernel: the residual epilogue of the continuous pipeline measured 1.4 ms per step SLOWER than
+    // the LDS-image epilogue (635.8 vs 634.4 ms, same box, bit-identical losses) - its 8-byte residual reads sit between the K loop and
     // the stores and are not hidden.  (The adapter-segment kernels use it: they exist only as continuous pipelines.)
-    if (cont_res < 0) { const char* e = getenv("VLR_GEMM_CONT_RES"); cont_res = (e && e[0] == '1') ? 1 : 0; }
-    // (an in-place residual, C == residual, stays on the LDS-image epilogue: the widened store of one lane covers columns another
-    // lane still has to read)
-    const bool res_ok = !p.residual || (cont_res && p.ldr % 4 == 0 && !((uintptr_t)p.residual & 7) && (const void*)p.residual != (const void*)p.C);
+    const bool res_ok = !p.residual;
     // fp32 residual stream: C fp32 = acc + residual fp32, 16-byte accesses in the accumulator layout (in place is fine: a lane reads
-    // exactly the bytes it writes).  VLR_GEMM_F32RES_CONT=0 sends these launches to the per-tile kernel's fp32 patches instead.
-    static int f32_cont = -1;
-    if (f32_cont < 0) { const char* e = getenv("VLR_GEMM_F32RES_CONT"); f32_cont = (e && e[0] == '0') ? 0 : 1; }
-    const bool f32_ok = p.out_f32 && f32_cont && (!p.residual || (p.res_f32 && p.ldr % 4 == 0 && !((uintptr_t)p.residual & 15))) && p.ldc % 4 == 0 && p.N % 4 == 0;
-    if (cont && ntiles > tiles && !p.bias && (p.out_f32 ? f32_ok : (res_ok && !p.res_f32)) && !p.accumulate && p.act == ACT_NONE && p.K >= 4 * PK &&
+    // exactly the bytes it writes); operands that miss the alignment go to the per-tile kernel's fp32 patches instead
+    const bool f32_ok = p.out_f32 && (!p.residual || (p.res_f32 && p.ldr % 4 == 0 && !((uintptr_t)p.residual & 15))) && p.ldc % 4 == 0 && p.N % 4 == 0;
+    if (ntiles > tiles && !p.bias && (p.out_f32 ? f32_ok : (res_ok && !p.res_f32)) && !p.accumulate && p.act == ACT_NONE && p.K >= 4 * PK &&
         (p.out_f32 || (p.ldc % 8 == 0 && p.N % 8 == 0)) && !((uintptr_t)p.C & 15)) {
         sched_prepare(p);
         if (layout == 0) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);

@@ -11,66 +11,11 @@
 #include "../../include/vlr.h"
 #include "common.h"
 
-// ---- optional second stream for the weight-gradient GEMMs: dgrad (NN) and wgrad (TN) of a layer are independent, so the
-// wgrad can run on a side stream and fill the dgrad's last, partly empty wave of workgroups.  Measured (profiles/): +1.5 %
-// with the first 256-tile kernel, -2 % once the GEMM dispatcher peels the ragged tile rows itself (gemm.hip) - two
-// 128 KiB-LDS kernels only time-share the CUs.  Off by default; VLR_BWD_STREAMS=1 enables it.
-#include <stdlib.h>
-static hipStream_t g_side = nullptr;
-static hipEvent_t g_fork = nullptr, g_done[4] = {nullptr, nullptr, nullptr, nullptr};
-static int g_two_streams = -1;
-static bool g_side_used = false;
-
-static bool two_streams() {
-    if (g_two_streams < 0) {
-        const char* e = getenv("VLR_BWD_STREAMS");
-        g_two_streams = (e && e[0] == '1') ? 1 : 0;
-        if (g_two_streams) {
-            if (hipStreamCreateWithFlags(&g_side, hipStreamNonBlocking) != hipSuccess) g_two_streams = 0;
-            hipEventCreateWithFlags(&g_fork, hipEventDisableTiming);
-            for (int i = 0; i < 4; ++i) hipEventCreateWithFlags(&g_done[i], hipEventDisableTiming);
-        }
-    }
-    return g_two_streams == 1;
-}
-// side stream continues from the current point of `main`
-static hipStream_t fork_side(hipStream_t main) {
-    hipEventRecord(g_fork, main);
-    hipStreamWaitEvent(g_side, g_fork, 0);
-    return g_side;
-}
-static void side_done(int i) { hipEventRecord(g_done[i], g_side); g_side_used = true; }
-static void wait_side(int i, hipStream_t main) { if (g_side_used) hipStreamWaitEvent(main, g_done[i], 0); }
-
-// make `stream` wait for every wgrad GEMM issued on the side stream (call before anything reads the weight gradients)
+// (ABI: the backward once ran its weight-gradient GEMMs on a second stream and callers joined it here before reading the gradients;
+// every pass is on the caller's stream now, so there is nothing to wait for)
 extern "C" int vlr_layers_join(vlr_stream_t stream) {
-    if (g_two_streams == 1 && g_side_used)
-        for (int i = 0; i < 4; ++i) hipStreamWaitEvent(stream, g_done[i], 0);
+    (void)stream;
     return VLR_OK;
-}
-
-// ---- side streams for the peeled rows of the decoder GEMMs (VlrGemmTail, common.h): one per main stream (the policy and the reference
-// pass run on different streams), created on first use.  VLR_GEMM_TAIL=0 switches the overlap off (the peel then runs on the main
-// stream as before round 4).
-static int g_tail_on = -1;
-static struct TailSlot { hipStream_t main, side; hipEvent_t fork, done; } g_tails[4];
-static int g_ntails = 0;
-static VlrGemmTail* tail_for(hipStream_t main, VlrGemmTail* t) {
-    if (g_tail_on < 0) { const char* e = getenv("VLR_GEMM_TAIL"); g_tail_on = (e && e[0] == '1') ? 1 : 0; }
-    if (!g_tail_on) return nullptr;
-    TailSlot* sl = nullptr;
-    for (int i = 0; i < g_ntails; ++i)
-        if (g_tails[i].main == main) sl = &g_tails[i];
-    if (!sl) {
-        if (g_ntails == 4) return nullptr;
-        sl = &g_tails[g_ntails];
-        sl->main = main;
-        if (hipStreamCreateWithFlags(&sl->side, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&sl->fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&sl->done, hipEventDisableTiming) != hipSuccess) return nullptr;
-        ++g_ntails;
-    }
-    t->side = sl->side; t->fork = sl->fork; t->done = sl->done; t->M1 = 0; t->used = 0;
-    return t;
 }
 
 #define CHECK(call)                     \
@@ -116,20 +61,8 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
                                  cfg->max_pos, st));
     CHECK(vlr_attn_fwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, Nq, a->lse, key_mask, batch, S,
                            cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    // o_proj: its peeled last tile rows run on a side stream beside the RMSNorm of the rows that are already there (tail_for above)
-    VlrGemmTail tl_, *tl = tail_for(st, &tl_);
-    vlr_internal_set_gemm_tail(tl);
     CHECK(proj_res(rf, a->attn, w->wo, a->x_mid, x_in, M, H, Nq, st));
-    vlr_internal_set_gemm_tail(nullptr);
-    if (tl && tl->used) {
-        const size_t xs = rf ? 4 : 2;
-        CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, tl->M1, H, cfg->rms_eps, st));
-        hipStreamWaitEvent(st, tl->done, 0);
-        CHECK(norm_fwd(rf, (const char*)a->x_mid + (size_t)tl->M1 * H * xs, w->ln2, off(a->xn2, (size_t)tl->M1 * H), a->rstd2 + tl->M1, M - tl->M1, H,
-                       cfg->rms_eps, st));
-    } else {
-        CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
-    }
+    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
     // gate|up projection with act = silu(gate) * up computed in the epilogue
     CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, M, I, H, H, keep_for_backward, st));
     CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
@@ -199,67 +132,29 @@ extern "C" int vlr_decoder_layer_bwd(const vlr_llama_cfg* cfg, const vlr_layer_w
     const int H = cfg->hidden, I = cfg->inter, M = batch * S;
     const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
     const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    const bool two = two_streams();
-    hipStream_t sd = st;
     // ---- MLP
-    if (two) {
-        sd = fork_side(st);
-        CHECK(vlr_gemm_bf16(2, dx_out, a->act, g->wdown, nullptr, nullptr, H, I, M, H, I, I, 0, 0, accumulate, 0, sd));
-        side_done(0);
-    }
     CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]; d act is not materialised
-    if (two) {
-        sd = fork_side(st);
-        CHECK(vlr_gemm_bf16(2, a->gu, a->xn2, g->wgu, nullptr, nullptr, 2 * I, H, M, 2 * I, H, H, 0, 0, accumulate, 0, sd));
-        side_done(1);
-    } else {
-        // dW_gate|up and dW_down as ONE persistent launch: 1376 + 688 output tiles are 8.06 rounds of 256 CUs together, 6 + 3 apart
-        CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
-    }
-    // the data-gradient GEMMs in front of the two RMSNorm backward passes: peeled rows on the side stream, the norm in two row ranges
-    VlrGemmTail tl_, *tl = two ? nullptr : tail_for(st, &tl_);
-    vlr_internal_set_gemm_tail(tl);
+    // dW_gate|up and dW_down as ONE persistent launch: 1376 + 688 output tiles are 8.06 rounds of 256 CUs together, 6 + 3 apart
+    CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
     CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    vlr_internal_set_gemm_tail(nullptr);
-    if (two) wait_side(2, st);                           // previous layer's dWo GEMM still reads ws->dx_mid
-    if (tl && tl->used)
-        CHECK(vlr_internal_rmsnorm_bwd_split(ws->dxn, a->x_mid, cfg->resid_f32, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, M, H,
-                                             tl->M1, tl->done, st));
-    else
-        CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, M, H, st));
+    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, M, H, st));
     // ---- attention
     // dW_o is one round of 256 tiles on its own; together with dW_qkv it would be 768 + 256 = 4 whole rounds of ONE persistent launch
     // (vlr_gemm_bf16_tn_pair below; both operands - dx_mid, attn - stay untouched until the end of this call).  Measured NEUTRAL in round 5
     // (565.9 vs 565.9 ms, same box, twice each) on the whole chip; with CUs left to RCCL (240-CU rounds: 4 + 2 apart, 5 together) it saves a
-    // round - so: paired when the joint launch saves rounds on the CUs the launches have now (VLR_PAIR_QKVO=1 always, =0 never)
-    static int pair_qkvo = -1;
-    if (pair_qkvo < 0) { const char* e = getenv("VLR_PAIR_QKVO"); pair_qkvo = !e ? 2 : (e[0] == '1' ? 1 : 0); }
-    const bool pair_o = !two && !accumulate && (pair_qkvo == 1 || (pair_qkvo == 2 && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25));
-    if (two) { sd = fork_side(st); }
-    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, sd));
-    if (two) side_done(2);
+    // round - so: paired when the joint launch saves at least a quarter round on the CUs the launches have now
+    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;
+    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, st));
     CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
-    if (two) wait_side(3, st);                           // previous layer's dWqkv GEMM still reads ws->dqkv
     CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
                            key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
                            cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
     // transpose of the rotation on the q and k column blocks ((Nq + Nkv) / head_dim consecutive heads)
     CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    if (two) { sd = fork_side(st); }
     if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, M, 0, st));
-    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, sd));
-    if (two) side_done(3);
-    tl = two ? nullptr : tail_for(st, &tl_);
-    vlr_internal_set_gemm_tail(tl);
+    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
     CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
-    vlr_internal_set_gemm_tail(nullptr);
-    if (two) { wait_side(0, st); wait_side(1, st); }     // this layer's dWdown / dWgu read dx_out / gu: done before dx_in (the
-                                                         // buffer the NEXT layer overwrites dx_out with) is produced
-    if (tl && tl->used)
-        CHECK(vlr_internal_rmsnorm_bwd_split(ws->dxn, x_in, cfg->resid_f32, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, M, H,
-                                             tl->M1, tl->done, st));
-    else
-        CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, M, H, st));
+    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, M, H, st));
     return VLR_OK;
 }
 
@@ -292,23 +187,16 @@ static int* row_tiles_buf(hipStream_t st, int ints) {
     return s->p;
 }
 // 256-row tile flags of a row-restricted adapter (1 = no marked row in the tile) for the adapter-segment GEMMs of a layer pass
-// (vlr_gemm_seg_rowskip): per-stream device bytes behind the K-tile list of row_tiles_buf; NULL: VLR_SEG_SKIP=0, M % 256 != 0 never matters
-// (the last tile is simply partial), or no memory
+// (vlr_gemm_seg_rowskip): per-stream device bytes behind the K-tile list of row_tiles_buf; NULL: no row mask or no memory (M % 256 != 0
+// never matters: the last tile is simply partial)
 static const unsigned char* seg_skip_flags(hipStream_t st, const unsigned char* rowmask, int M) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("VLR_SEG_SKIP"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || !rowmask) return nullptr;
+    if (!rowmask) return nullptr;
     const int tiles = (M + 255) / 256;
     int* buf = row_tiles_buf(st, M / 64 + 2 + (tiles + 3) / 4);
     if (!buf) return nullptr;
     unsigned char* flags = (unsigned char*)(buf + M / 64 + 2);
     if (vlr_rows_tile_flags(rowmask, M, 256, flags, st) != VLR_OK) return nullptr;
     return flags;
-}
-static bool row_tiles_on() {      // VLR_ROW_TILES=0: the K reductions of a row-restricted adapter read all token rows (A/B)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("VLR_ROW_TILES"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
 }
 
 // lora_rows.hip: the streaming row-slab adapter products (mode 0: u = alpha (keep . x) A^T, mode 1: v = dy B); false = shape not taken
@@ -367,6 +255,7 @@ static int lora_group_bwd(int n, int r, int in, const int* outs, const void* x, 
                           void* dA, void* dB, const void* u, int ldu, void* v, void* dx, float scale, float p, uint64_t seed,
                           void* ws_xd, int accumulate, int M, hipStream_t st, int dx_fresh = 0, const unsigned char* rowmask = nullptr,
                           const unsigned char* bits = nullptr, const unsigned char* bits_kt = nullptr, const int* ktl = nullptr) {
+    (void)ws_xd;
     const int nr = n * r;
     const long gstride = (long)M * in / 8;       // bytes between the packed keep masks of the group's targets (the forward drew them)
     size_t ofs[4] = {0, 0, 0, 0};
@@ -401,18 +290,8 @@ static int lora_group_bwd(int n, int r, int in, const int* outs, const void* x, 
         else CHECK(vlr_gemm_grouped_bits(2, v, x, dA, r, in, M, nr, in, in, n, (long)r, 0L, (long)r * in, scale / (1.f - p), accumulate, 2, seed, p, in,
                                          bits, gstride, st));
         // dx (+)= s / (1 - p) sum_t mask_t . (v_t A_t): ONE pass over dx for the n targets (vlr_gemm_dropout_acc_multi: the streaming kernel
-        // of lora_dx.hip, 222 us for q, k, v at [12792 x 4096], r = 128, against 3 x 90 us one target at a time; tools/lora_gemm_bench.py).
-        // VLR_LORA_MULTI=0: one pass per target on the 128x128 GEMM kernel (mask in its epilogue)
-        static int multi = -1;
-        if (multi < 0) { const char* e = getenv("VLR_LORA_MULTI"); multi = (e && e[0] == '0') ? 0 : 1; }
-        if (multi || dx_fresh) {
-            CHECK(vlr_gemm_dropout_acc_multi_rows(n, v, nr, A, dx, M, in, r, p, seed, scale, dx_fresh ? 0 : 1, bits, gstride, rowmask, st));
-        } else {
-            VLR_REQUIRE(ws_xd, "lora backward: lora_dropout > 0 needs a scratch buffer [M][in]");
-            for (int t = 0; t < n; ++t)
-                CHECK(vlr_gemm_dropout_acc_bits(off(v, (size_t)t * r), nr, off(A, (size_t)t * r * in), dx, ws_xd, M, in, r, p, seed + t, scale,
-                                                bits ? bits + (size_t)t * gstride : nullptr, st));
-        }
+        // of lora_dx.hip, 222 us for q, k, v at [12792 x 4096], r = 128, against 3 x 90 us one target at a time; tools/lora_gemm_bench.py)
+        CHECK(vlr_gemm_dropout_acc_multi_rows(n, v, nr, A, dx, M, in, r, p, seed, scale, dx_fresh ? 0 : 1, bits, gstride, rowmask, st));
     } else {
         CHECK(vlr_gemm_bf16_scaled(2, v, x, dA, nullptr, nullptr, nr, in, M, nr, in, in, 0, 0, accumulate, 0, scale, st));  // dA = s v^T x
         CHECK(vlr_gemm_bf16_scaled(1, v, A, dx, nullptr, nullptr, M, in, nr, nr, in, in, 0, 0, dx_fresh ? 0 : 1, 0, scale, st));     // dx (+)= s v A
@@ -507,7 +386,7 @@ extern "C" int vlr_decoder_layer_bwd_lora_ex(const vlr_llama_cfg* cfg, const vlr
     const int o_qkv[3] = {Nq, Nkv, Nkv}, o_h[1] = {H}, o_gu[2] = {I, I};
     const float sc = lw->scale, p = lw->dropout;
     const int* ktl = nullptr;         // PLoRA: the 64-row K tiles with an image row, for the adapter-gradient reductions over the token rows
-    if (rowmask && M % 64 == 0 && lg->a_qkv && row_tiles_on()) {
+    if (rowmask && M % 64 == 0 && lg->a_qkv) {
         int* buf = row_tiles_buf(st, M / 64 + 1);
         if (buf) { CHECK(vlr_rows_tile_list(rowmask, M, buf, st)); ktl = buf; }
     }
@@ -515,20 +394,13 @@ extern "C" int vlr_decoder_layer_bwd_lora_ex(const vlr_llama_cfg* cfg, const vlr
 #define MB(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + (size_t)(t) * ((size_t)M * H / 8) : nullptr)      // packed keep mask of target t
 #define MT(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + lora_rowmajor_bytes(H, I, M) + (size_t)(t) * (size_t)vlr_dropout_bits_kt_bytes(M, H) : nullptr)   // ... K-tile-blocked transposed
     // ---- MLP
-    static int fuse_down = -1;     // adapter term of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue (VLR_LORA_FUSE_DOWN=0: three separate kernels)
-    if (fuse_down < 0) { const char* e = getenv("VLR_LORA_FUSE_DOWN"); fuse_down = (e && e[0] == '0') ? 0 : 1; }
-    if (lw->a_down && fuse_down) {
+    if (lw->a_down) {      // adapter term of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue
         // history: SLOWER than the three separate kernels in round 3 (38.8 ms against 25.5 + 7.7 per step: the addend is a third 16-byte
         // load stream in an epilogue that already reads gate | up), equal in round 4 after the epilogue staging, 1.7 ms FASTER in round 5
         // (482.3 against 484.1 ms, same box, twice each): the default now - no swiglu_bwd_kernel launch under LoRA
         CHECK(lora_group_bwd(1, r, I, o_h, a->act, dx_out, H, lw->a_down, lw->b_down, lg->a_down, lg->b_down, off(u, 6 * (size_t)r), ldu, ws_v,
                              ws->dact, sc, p, seed + 6, XD(6), accumulate, M, st, 1, rowmask, MB(6), MT(6), ktl));
         CHECK(vlr_gemm_swiglu_bwd_add(dx_out, w->wdown, a->gu, ws->dact, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]
-    } else if (lw->a_down) {
-        CHECK(vlr_gemm_bf16(1, dx_out, w->wdown, ws->dact, nullptr, nullptr, M, I, H, H, I, I, 0, 0, 0, 0, st));
-        CHECK(lora_group_bwd(1, r, I, o_h, a->act, dx_out, H, lw->a_down, lw->b_down, lg->a_down, lg->b_down, off(u, 6 * (size_t)r), ldu, ws_v,
-                             ws->dact, sc, p, seed + 6, XD(6), accumulate, M, st, 0, rowmask, MB(6), MT(6), ktl));
-        CHECK(vlr_swiglu_bwd(a->gu, ws->dact, M, I, st));   // gu now holds [dgate | dup]
     } else {
         CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));
     }
@@ -716,20 +588,12 @@ extern "C" int vlr_decoder_layer_bwd_lora2(const vlr_llama_cfg* cfg, const vlr_l
     };
     // ---- MLP
     // (as vlr_decoder_layer_bwd_lora_ex: the adapter terms of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue and
-    // those terms as its addend - no separate pass over [M][2I]; VLR_LORA_FUSE_DOWN=0: three kernels)
-    static int fuse_down = -1;
-    if (fuse_down < 0) { const char* e = getenv("VLR_LORA_FUSE_DOWN"); fuse_down = (e && e[0] == '0') ? 0 : 1; }
-    if (lw->a_down && fuse_down) {
+    // those terms as its addend - no separate pass over [M][2I])
+    if (lw->a_down) {
         CHECK(lora2_group_bwd(1, I, o_h, a->act, dx_out, H, side(lw, lw->a_down, lg->a_down, lg->b_down, seed_l, 6),
                               side(pw, pw->a_down, nullptr, nullptr, seed_p, 6), bc->down, off(u, 6 * (size_t)R), ldu, ws_v, ws->dact, accumulate, M,
                               rowmask, st, 1));
         CHECK(vlr_gemm_swiglu_bwd_add(dx_out, w->wdown, a->gu, ws->dact, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]
-    } else if (lw->a_down) {
-        CHECK(vlr_gemm_bf16(1, dx_out, w->wdown, ws->dact, nullptr, nullptr, M, I, H, H, I, I, 0, 0, 0, 0, st));
-        CHECK(lora2_group_bwd(1, I, o_h, a->act, dx_out, H, side(lw, lw->a_down, lg->a_down, lg->b_down, seed_l, 6),
-                              side(pw, pw->a_down, nullptr, nullptr, seed_p, 6), bc->down, off(u, 6 * (size_t)R), ldu, ws_v, ws->dact, accumulate, M,
-                              rowmask, st));
-        CHECK(vlr_swiglu_bwd(a->gu, ws->dact, M, I, st));   // gu now holds [dgate | dup]
     } else {
         CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));
     }

@@ -348,17 +348,11 @@ static bool dx_launch_k(const LoraDxParams& p, int mask, dim3 grid, hipStream_t 
 }
 
 // dx (+)= scale / (1 - p) * sum_t keep_t . (v_t A_t) on the streaming kernel; false: a shape it does not take (the caller runs the
-// tile kernels of gemm.hip): n <= 3 targets, r in {64, 128, 256}, in % 128 == 0, 16-byte aligned operands.  VLR_LORA_DX=0 disables.
+// tile kernels of gemm.hip): n <= 3 targets, r in {64, 128, 256}, in % 128 == 0, 16-byte aligned operands.
 bool vlr_lora_dx_try_launch(int n, const void* v, int ldv, const void* A, void* dx, int M, int in, int r, float p_drop, uint64_t seed,
                             float scale, int accumulate, const void* bits, long bits_gstride, hipStream_t stream, const unsigned char* rowskip) {
-    static int on = -1, wg_per_cu = 4;      // 4 workgroups per CU in the grid (2-4 resident): 196 / 88 / 123 / 255 us for the four groups at the 7B shapes against 222 / 106 / 147 / 303 at 2
-    if (on < 0) {
-        const char* e = getenv("VLR_LORA_DX");
-        on = (e && e[0] == '0') ? 0 : 1;
-        const char* w = getenv("VLR_LORA_DX_WGS");
-        if (w && atoi(w) >= 1 && atoi(w) <= 8) wg_per_cu = atoi(w);
-    }
-    if (!on || n < 1 || n > 3 || in % 128 != 0 || (r != 64 && r != 128 && r != 256) || ldv % 8 != 0 || M < 1) return false;
+    constexpr int WG_PER_CU = 4;      // 4 workgroups per CU in the grid (2-4 resident): 196 / 88 / 123 / 255 us for the four groups at the 7B shapes against 222 / 106 / 147 / 303 at 2
+    if (n < 1 || n > 3 || in % 128 != 0 || (r != 64 && r != 128 && r != 256) || ldv % 8 != 0 || M < 1) return false;
     if (((uintptr_t)v | (uintptr_t)A | (uintptr_t)dx) & 15) return false;
     LoraDxParams q;
     q.v = (const bf16_t*)v; q.ldv = ldv; q.A = (const bf16_t*)A; q.dx = (bf16_t*)dx; q.M = M; q.in = in; q.r = r;
@@ -369,15 +363,11 @@ bool vlr_lora_dx_try_launch(int n, const void* v, int ldv, const void* A, void* 
     // (tools/lora_gemm_bench.py --reps 20, round 6): rank 256 (InternLM-XComposer2's PLoRA: qkv 88.8 -> 78.0, o 88.6 -> 77.2, down 386 -> 258 us)
     // and wide inputs (LLaVA down_proj, in = 11008: 178.7 -> 167.7 us); at r = 128 / in = 4096 the 64-row workgroups win (o 51.0 against
     // 57.9, gate | up 77.7 against 93.7 us: two independent workgroups per CU de-phase, eight waves behind one barrier do not).
-    // VLR_LORA_DX_ROWS=64 | 128 forces one form (A/B).
-    static int rows_env = -1;
-    if (rows_env < 0) { const char* e = getenv("VLR_LORA_DX_ROWS"); rows_env = e ? atoi(e) : 0; }
     const int kt_ = r / 64;
-    const bool rows128 = n * kt_ <= 4 && (rows_env == 128 || (rows_env != 64 && (kt_ == 4 || in >= 8192)));
+    const bool rows128 = n * kt_ <= 4 && (kt_ == 4 || in >= 8192);
     const int rows = rows128 ? 128 : 64;
     const int rb = (M + rows - 1) / rows, tiles_n = in / 128;
-    static bool wgs_forced = getenv("VLR_LORA_DX_WGS") != nullptr;
-    const int wpc = (rows128 && in < 8192 && !wgs_forced) ? 2 : wg_per_cu;      // 128-row workgroups at in = 4096: 2 per CU in the grid (73 / 71 us against 77 at 4, InternLM qkv / o)
+    const int wpc = (rows128 && in < 8192) ? 2 : WG_PER_CU;      // 128-row workgroups at in = 4096: 2 per CU in the grid (73 / 71 us against 77 at 4, InternLM qkv / o)
     int splits = (wpc * vlr_compute_cus() + rb - 1) / rb;
     if (splits < 1) splits = 1;
     if (splits > tiles_n) splits = tiles_n;

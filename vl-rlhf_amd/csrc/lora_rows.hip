@@ -52,7 +52,7 @@ struct LoraRowsParams {
     const unsigned char* bits[LR_MAXT];  // packed keep masks over the dense [M][bits_ld] activation, or null
     int bits_ld;
     const unsigned char* rowmask;        // [M] or null
-    int dbg;                             // VLR_LORA_ROWS_DBG (timing experiments only: 1 = activation staged once, 2 = small operand staged once, 4 = no MFMA)
+    int dbg;                             // 0 in the product (timing experiments only: 1 = activation staged once, 2 = small operand staged once, 4 = no MFMA)
 };
 
 __device__ __forceinline__ void lr_dma16_s(const char* sbase, uint32_t voff, uint32_t lds_addr) {
@@ -297,7 +297,7 @@ static void lr_launch(const LoraRowsParams& p, int wgs, hipStream_t st) {
 // product it can take (LLaVA r 128: 0.3 - 0.4 % slower than the split-K tile GEMMs); 0 = none.  The C-ABI entry points always run it.
 static int lr_mode() {
     static int m = -1;
-    if (m < 0) { const char* e = getenv("VLR_LORA_ROWS"); m = !e ? 2 : (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : 2)); }
+    if (m < 0) { m = vlr_env_int("VLR_LORA_ROWS", 2); if (m < 0 || m > 2) m = 2; }
     return m;
 }
 
@@ -320,7 +320,7 @@ bool vlr_lora_rows_try_launch(int mode, int n, const void* X, int ldx, const int
     if (bits && (mode != 0 || bits_ld % 64 != 0 || gbits % 4 != 0 || ((uintptr_t)bits & 3))) return false;
     LoraRowsParams p;
     p.X = (const bf16_t*)X; p.ldx = ldx; p.M = M; p.n = n * parts; p.ct = rc / 16; p.ldw = ldw;
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("VLR_LORA_ROWS_DBG"); dbg = e ? atoi(e) : 0; } p.dbg = dbg; }
+    p.dbg = 0;
     p.out = (bf16_t*)out; p.ldo = ldo; p.alpha = alpha; p.bits_ld = bits ? bits_ld : 0; p.rowmask = rowmask;
     int ofs = 0;
     for (int t = 0; t < n; ++t) {
@@ -342,10 +342,8 @@ bool vlr_lora_rows_try_launch(int mode, int n, const void* X, int ldx, const int
         if (mode == 1 && ofs % 8 != 0) return false;
         ofs += Ks[t];
     }
-    // 128-row workgroups where they measured faster (rank 256 = two column halves of 128 that share the activation's lines; VLR_LORA_ROWS_R=64 | 128 forces one form)
-    static int rows_env = -1;
-    if (rows_env < 0) { const char* e = getenv("VLR_LORA_ROWS_R"); rows_env = e ? atoi(e) : 0; }
-    const bool big = rc == 128 && (rows_env == 128 || (rows_env != 64 && r == 256));
+    // 128-row workgroups where they measured faster (rank 256 = two column halves of 128 that share the activation's lines)
+    const bool big = rc == 128 && r == 256;
     const int rows = big ? 128 : 64;
     const int slabs = (M + rows - 1) / rows;
     const int wgs = ((slabs + 7) / 8) * 8 * p.n;

@@ -10,7 +10,6 @@ Replaces, for the DPO hot path, what the reference reaches through
   Trainer.training_step / optimizer     (transformers 4.41.0 + torch AdamW; flags scripts/dpo_llava.sh:35-41)
 """
 import math
-import os
 from typing import Dict, List, Optional
 
 import torch
@@ -379,7 +378,7 @@ class LlavaHipEngine:
     custom_layers = False          # True: the subclass composes the decoder layer itself (_layer_forward / _hidden_backward_custom)
     supports_resid_f32 = True      # False: the subclass adds to the residual stream with bf16 primitives
     supports_ckpt = True           # False: the subclass's backward cannot re-run a layer's forward (gradient checkpointing is ignored)
-    proj_out_f32 = True            # with the fp32 stream the projector writes fp32 rows for the merge (VLR_PROJ_F32=0: bf16)
+    proj_out_f32 = True            # with the fp32 stream the projector writes fp32 rows for the merge (False in a subclass: bf16)
     supports_kv_cache = True       # generate(use_cache=True): prefill into a KVCache + decode_step (vlr_decoder_layer_decode)
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
@@ -409,11 +408,10 @@ class LlavaHipEngine:
         self.sin = torch.empty_like(self.cos)
         _hip.call("vlr_rope_table", self.cos, self.sin, max_positions, self.hd, float(c.get("rope_theta", 10000.0)))
         # fp32 residual stream (include/vlr.h vlr_llama_cfg.resid_f32): x0 and every layer's x_mid / x_out are fp32, never rounded.
-        # Default ON (VLR_RESID_F32=0 or cfg["resid_f32"] = False: the bf16 stream of ABI v3); engines that compose their own layers
+        # Default ON (cfg["resid_f32"] = False: the bf16 stream of ABI v3); engines that compose their own layers
         # from bf16 primitives opt out (supports_resid_f32).
-        self.resid_f32 = bool(c.get("resid_f32", os.environ.get("VLR_RESID_F32", "1") != "0")) and self.supports_resid_f32
+        self.resid_f32 = bool(c.get("resid_f32", True)) and self.supports_resid_f32
         self.RDT = torch.float32 if self.resid_f32 else BF16      # dtype of the residual stream
-        self.proj_out_f32 = self.proj_out_f32 and os.environ.get("VLR_PROJ_F32", "1") != "0"
         # gradient checkpointing (reference scripts: --gradient_checkpointing True, dpo.py:99 non-reentrant): only the layer inputs
         # are kept by the forward; the backward re-runs each layer's forward into one scratch set right before its backward
         self.gradient_checkpointing = bool(c.get("gradient_checkpointing", False))
@@ -442,11 +440,6 @@ class LlavaHipEngine:
         self._ce_ws = None                  # partials of vlr_ce_mean_fwd (allocated by the first SFT loss)
         self.ce_row_block = None            # rows per block of vlr_lmhead_ce_bwd; None = the library's default (< 1 GiB of workspace)
         self.norm_out = torch.zeros(3, dtype=torch.float32, device=self.dev)
-        # Optional (VLR_ASYNC_OPT=1): clip + AdamW (HBM-bound, 32 ms) on their own stream so that they overlap the next step's
-        # FROZEN reference forward; the policy forward waits for the `_opt_done` event.  Measured on MI355X: no gain (650.7 /
-        # 652.6 ms without vs 648.5 / 653.1 ms with) - the two kernels do not co-schedule - so it is off by default.
-        self._opt_stream = torch.cuda.Stream(self.dev) if os.environ.get("VLR_ASYNC_OPT", "0") == "1" else None
-        self._opt_done = None
         # split-K scratch of the GEMM dispatcher (ragged last tile rows, LoRA adapter gradients): two 64 MiB slots (main + side stream)
         _hip.ensure_splitk_workspace(self.dev, force=True)      # a new engine brings new streams: forget the old slot assignment
 
@@ -551,8 +544,8 @@ class LlavaHipEngine:
         its adapter GEMMs and again by its backward - 57 MB per layer at the 7B shapes.  The buffer lives IN the activation set of the
         pass that drew it (`acts`: per tag and layer, or the one shared set of a checkpointed pass), so a second training-mode forward
         of the same size cannot overwrite masks a pending backward will read, and checkpointing keeps one buffer instead of one per
-        layer.  VLR_LORA_BITS=0: every kernel hashes instead."""
-        if p <= 0.0 or os.environ.get("VLR_LORA_BITS", "1") == "0" or (M * self.H) % 32 or (M * self.I) % 32:
+        layer.  None (no dropout, or M * width not a multiple of 32): every kernel hashes instead."""
+        if p <= 0.0 or (M * self.H) % 32 or (M * self.I) % 32:
             return None
         n = _hip.helper("vlr_lora_mask_bytes", self.H, self.I, M)
         if acts is None:
@@ -1083,7 +1076,6 @@ class LlavaHipEngine:
             a = ctx["acts"][l]
             x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
             if ctx["ckpt"]:
-                _hip.call("vlr_layers_join")          # the previous layer's weight-gradient GEMMs still read the shared activation set
                 self._layer_fwd_call(ws, l, a, x_in, ctx["embed"], Bn, S, True, False, None)
             _hip.call("vlr_decoder_layer_bwd", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), acc,
                       a["struct"], lws, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
@@ -1091,9 +1083,7 @@ class LlavaHipEngine:
                 _hip.call("vlr_colsum", wsb["dqkv"], M, self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
             cur, nxt = nxt, cur
             if self.reducer is not None:
-                _hip.call("vlr_layers_join")          # wgrad GEMMs of this layer run on the library's side stream
                 self.reducer.bucket_ready(f"layer{l}")
-        _hip.call("vlr_layers_join")
         self._embed_backward(ctx, cur, acc)
         self.grad_fresh = False
         if self.reducer is not None:
@@ -1211,31 +1201,20 @@ class LlavaHipEngine:
         self.grad_fresh = True
 
     def wait_optimizer(self):
-        """make the current stream wait for the last optimizer step (no host synchronisation)"""
-        if self._opt_done is not None:
-            torch.cuda.current_stream(self.dev).wait_event(self._opt_done)
+        """order the current stream behind the last optimizer step.  The step runs on the caller's stream (on a stream of its own it
+        measured no gain: 650.7 / 652.6 ms without, 648.5 / 653.1 ms with), so there is nothing to wait for; kept for callers."""
 
     def grad_norm(self) -> float:
-        """total gradient norm of the last optimizer step (host value; synchronises on the optimizer stream)"""
-        if self._opt_done is not None:
-            self._opt_done.synchronize()
+        """total gradient norm of the last optimizer step (host value; synchronises)"""
         return float(self.norm_out[0])
 
     def optimizer_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, grad_scale=1.0):
-        """clip + AdamW, issued on the optimizer stream behind everything queued on the caller's stream so far."""
+        """clip + AdamW on the caller's stream, behind the gradient exchange."""
         if self.master is None:
             self.init_optimizer()
         if self.reducer is not None:
             self.reducer.wait()
-        if self._opt_stream is None:
-            return self._optimizer_step(lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale)
-        main = torch.cuda.current_stream(self.dev)
-        self._opt_stream.wait_stream(main)
-        with torch.cuda.stream(self._opt_stream):
-            out = self._optimizer_step(lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale)
-            self._opt_done = torch.cuda.Event()
-            self._opt_done.record(self._opt_stream)
-        return out
+        return self._optimizer_step(lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale)
 
     def _optimizer_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, grad_scale=1.0):
         """clip_grad_norm_(max_grad_norm) + AdamW on the flat buffers; no host synchronisation (the clip coefficient
