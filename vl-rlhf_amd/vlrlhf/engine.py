@@ -23,6 +23,20 @@ def _align(n, a=8):
     return (n + a - 1) // a * a
 
 
+def qkv_row_perm(nh, nkv, hd):
+    """InternLM2 stores the rows of its fused grouped-query wqkv per K/V head as [q_0..q_{g-1} | k | v]: the permutation that re-orders
+    them to q | k | v blocks (engine row i = checkpoint row perm[i])"""
+    g = nh // nkv
+    idx = torch.arange((nh + 2 * nkv) * hd).view(nkv, g + 2, hd)
+    return torch.cat([idx[:, :g].reshape(-1), idx[:, g].reshape(-1), idx[:, g + 1].reshape(-1)])
+
+
+def invert_perm(perm):
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(perm.numel())
+    return inv
+
+
 class ParamLayout:
     """Flat layout of the TRAINABLE parameters (LLM + projector; the vision tower is frozen, auto_load.py:554-555).
 
@@ -49,9 +63,7 @@ class ParamLayout:
             nm = dict(lm_head="output.weight", embed="model.tok_embeddings.weight", norm="model.norm.weight", down="feed_forward.w2.weight",
                       gate="feed_forward.w1.weight", up="feed_forward.w3.weight", o="attention.wo.weight", ln1="attention_norm.weight",
                       ln2="ffn_norm.weight")
-            g_ = nh // nkv
-            idx = torch.arange((nh + 2 * nkv) * hd).view(nkv, g_ + 2, hd)
-            qkv_perm = torch.cat([idx[:, :g_].reshape(-1), idx[:, g_].reshape(-1), idx[:, g_ + 1].reshape(-1)])
+            qkv_perm = qkv_row_perm(nh, nkv, hd)
         elif qwen:
             # Qwen-VL (reference models/QwenVL/modeling_qwen.py): fused biased c_attn, MLP c_proj(w1(x) * silu(w2(x))) -> gate = w2,
             # up = w1; no projector (the resampler is part of the frozen vision tower)
@@ -199,9 +211,7 @@ class LoraLayout:
             self.groups, self.prefix = ILM_LORA_GROUPS, "base_model.model.model.layers."
             per = dict(a_qkv=(r, H), b_qkv=(Nq + 2 * Nkv, r), a_o=(r, Nq), b_o=(H, r), a_gu=(2 * r, H), b_gu=(2 * I, r), a_down=(r, I), b_down=(H, r))
             self.out_dim = dict(wqkv=Nq + 2 * Nkv, wo=H, w1=I, w3=I, w2=H)
-            g_ = nh // nkv
-            idx = torch.arange((nh + 2 * nkv) * hd).view(nkv, g_ + 2, hd)
-            self.row_perm["b_qkv"] = torch.cat([idx[:, :g_].reshape(-1), idx[:, g_].reshape(-1), idx[:, g_ + 1].reshape(-1)])
+            self.row_perm["b_qkv"] = qkv_row_perm(nh, nkv, hd)
         elif self.qwen:
             self.groups, self.prefix = QWEN_LORA_GROUPS, "base_model.model.transformer.h."
             per = dict(a_qkv=(r, H), b_qkv=(Nq + 2 * Nkv, r), a_o=(r, Nq), b_o=(H, r), a_gu=(2 * r, H), b_gu=(2 * I, r))
@@ -277,9 +287,7 @@ class WeightSet:
             v = self.v[name]
             perm = self.layout.row_perm.get(name)
             if perm is not None:                  # back to the checkpoint's row order (a copy, not a view)
-                inv = torch.empty_like(perm)
-                inv[perm] = torch.arange(perm.numel())
-                out[hf] = v[inv.to(v.device)]
+                out[hf] = v[invert_perm(perm).to(v.device)]
                 continue
             out[hf] = v if v.dim() == 1 else v[r0:r0 + rows]
         return out
@@ -375,9 +383,8 @@ class KVCache:
 
 
 class LlavaHipEngine:
-    custom_layers = False          # True: the subclass composes the decoder layer itself (_layer_forward / _hidden_backward_custom)
     supports_resid_f32 = True      # False: the subclass adds to the residual stream with bf16 primitives
-    supports_ckpt = True           # False: the subclass's backward cannot re-run a layer's forward (gradient checkpointing is ignored)
+    supports_ckpt = True           # False: the backward cannot re-run a layer's forward (read per pass by forward_hidden: checkpointing is ignored)
     proj_out_f32 = True            # with the fp32 stream the projector writes fp32 rows for the merge (False in a subclass: bf16)
     supports_kv_cache = True       # generate(use_cache=True): prefill into a KVCache + decode_step (vlr_decoder_layer_decode)
 
@@ -516,9 +523,7 @@ class LlavaHipEngine:
             t = self.lv[k][lo:hi].clone()
             perm = self.lora_layout.row_perm.get(k.split(".", 1)[1])
             if perm is not None:                  # back to the checkpoint's row order
-                inv = torch.empty_like(perm)
-                inv[perm] = torch.arange(perm.numel())
-                t = t[inv.to(t.device)]
+                t = t[invert_perm(perm).to(t.device)]
             out[n] = t
         return out
 
@@ -603,9 +608,21 @@ class LlavaHipEngine:
                      x_mid=torch.empty(M, H, dtype=self.RDT, device=self.dev), xn2=torch.empty(M, H, dtype=BF16, device=self.dev),
                      rstd2=torch.empty(M, dtype=torch.float32, device=self.dev), gu=torch.empty(M, 2 * I, dtype=BF16, device=self.dev),
                      act=torch.empty(M, I, dtype=BF16, device=self.dev), x_out=torch.empty(M, H, dtype=self.RDT, device=self.dev))
-            t["struct"] = _hip.LayerActs(*(t[n].data_ptr() for n in ("xn1", "rstd1", "qkv", "attn", "lse", "x_mid", "xn2", "rstd2", "gu", "act", "x_out")))
+            t["struct"] = self._acts_struct(t)
             self._ws[k] = t
         return t
+
+    @staticmethod
+    def _acts_struct(t):
+        return _hip.LayerActs(*(t[n].data_ptr() for n, _ in _hip.LayerActs._fields_))
+
+    def _adapter_scratch(self, a, key, M, width):
+        """the adapters' down-projections of one layer pass ([M][7 ranks]: `u`, or `u2` for two stacked adapters), written by the forward
+        and read by the backward: lives in the activation set, or in the one shared set of a checkpointed pass"""
+        sh = a.get("shared", a)
+        if key not in sh or sh[key].shape[1] != width:
+            sh[key] = torch.empty(M, width, dtype=BF16, device=self.dev)
+        return sh[key]
 
     def _ckpt_acts(self, tag, l, Bn, S):
         """gradient checkpointing: every layer shares ONE scratch activation set; only x_out (= the next layer's input) is per layer"""
@@ -615,7 +632,7 @@ class LlavaHipEngine:
             base = self._layer_acts(tag + "/ckpt", 0, Bn, S)
             t = {n: v for n, v in base.items() if n != "struct"}
             t["x_out"] = torch.empty(Bn * S, self.H, dtype=self.RDT, device=self.dev)
-            t["struct"] = _hip.LayerActs(*(t[n].data_ptr() for n in ("xn1", "rstd1", "qkv", "attn", "lse", "x_mid", "xn2", "rstd2", "gu", "act", "x_out")))
+            t["struct"] = self._acts_struct(t)
             t["shared"] = base            # LoRA: u / xd live in the shared set
             self._ws[k] = t
         return t
@@ -629,17 +646,12 @@ class LlavaHipEngine:
     def _layer_fwd_call(self, ws, l, a, x, e, Bn, S, keep, use_lora, lora_seed):
         """one decoder layer forward into the activation set `a` (keep: also write what only the backward reads)"""
         M = Bn * S
-        if self.custom_layers:
-            self._layer_forward(ws, l, a, x, e, Bn, S, keep, use_lora, lora_seed)
-        elif use_lora:
-            r = self.lora["r"]
-            sh = a.get("shared", a)
-            if "u" not in sh or sh["u"].shape[1] != 7 * r:
-                sh["u"] = torch.empty(M, 7 * r, dtype=BF16, device=self.dev)
+        if use_lora:
+            u = self._adapter_scratch(a, "u", M, 7 * self.lora["r"])
             lw, _ = self._lora_structs(l, train=True, M=M, acts=a)
             # (lora_dropout: the keep mask is applied to x while the adapter GEMMs stage it and regenerated in the backward - no dropped
             # copies of the seven inputs are kept any more: 0.9 GB per layer at the 7B shapes)
-            _hip.call("vlr_decoder_layer_fwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, a["struct"], sh["u"], None,
+            _hip.call("vlr_decoder_layer_fwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, a["struct"], u, None,
                       lora_seed + 8 * l, x, e["pos"], e["mask"], Bn, S)
         else:
             _hip.call("vlr_decoder_layer_fwd_ex", self.llama_cfg, self.layer_weights(ws, l), a["struct"], x, e["pos"], e["mask"], Bn, S,
@@ -811,7 +823,7 @@ class LlavaHipEngine:
         am = attention_mask.to(self.dev).contiguous()
         lab = labels.to(self.dev).contiguous() if labels is not None else None
         e = self._embed_inputs(ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta)
-        e["tag"] = tag               # scratch buffers of custom layers are keyed per pass (the reference pass runs on a side stream)
+        e["tag"] = tag               # scratch buffers of layers composed in Python are keyed per pass (the reference pass runs on a side stream)
         e["grad_pass"] = bool(save)  # this pass will be back-propagated (training-mode dropout applies; a checkpointed forward included)
         S, M = e["S"], e["M"]
         src, mask, pos, mlabels, img_map, inv = e["src"], e["mask"], e["pos"], e["labels"], e["img_map"], e["inv"]
@@ -1052,42 +1064,70 @@ class LlavaHipEngine:
         return dhidden
 
     def hidden_backward(self, ctx, dhidden):
-        """Backward of forward_hidden(save=True): final norm, decoder layers L-1..0, merge, projector.  Gradients
-        land in the flat bf16 gradient buffer (overwrite when `grad_fresh`, else accumulate)."""
+        """Backward of forward_hidden(save=True): final norm, decoder layers L-1..0, then - in a full fine-tune - merge and projector.
+        Gradients land in the flat bf16 gradient buffer (overwrite when `grad_fresh`, else accumulate).  Under LoRA only the adapters
+        receive gradients: nothing below the first decoder layer is trainable (embedding, projector and vision tower are not target
+        modules), so the backward stops there."""
         assert ctx["acts"] is not None, "forward_hidden(save=True) required"
-        ws = ctx["ws"]
-        Bn, S, M, H, I = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I
+        full = self.lora is None
+        if not full and ctx.get("lora_seed") is None:
+            raise RuntimeError("backward through a pass that ran with the adapters disabled")
+        ws, M = ctx["ws"], ctx["M"]
         acc = int(not self.grad_fresh)
-        Sp = _align(S, 64)
-        dxa = self._buf(("dxa", M), (M, H))
-        dxb = self._buf(("dxb", M), (M, H))
-        if self.custom_layers:
-            return self._hidden_backward_custom(ctx, dhidden, dxa, dxb)
-        if self.lora is not None:
-            return self._hidden_backward_lora(ctx, dhidden, dxa, dxb)
-        self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"], acc, M)
-        wsb = dict(dact=self._buf(("dact", M), (M, I)), dxn=self._buf(("dxn", M), (M, H)), dattn=self._buf(("dattn", M), (M, self.Nq)),
+        dxa = self._buf(("dxa", M), (M, self.H))
+        dxb = self._buf(("dxb", M), (M, self.H))
+        self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"] if full else None, acc if full else 0, M)
+        cur = self._layers_backward(ctx, self._layer_bwd(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
+        if full:
+            self._embed_backward(ctx, cur, acc)
+        self.grad_fresh = False
+        if self.reducer is not None:
+            self.reducer.bucket_ready("tail" if full else "lora")
+
+    def _bwd_workspace(self, ctx):
+        """scratch of one decoder layer's backward, shared by every layer: (buffers by name, the library's vlr_layer_bwd_ws over them)"""
+        Bn, S, M, H = ctx["Bn"], ctx["S"], ctx["M"], self.H
+        wsb = dict(dact=self._buf(("dact", M), (M, self.I)), dxn=self._buf(("dxn", M), (M, H)), dattn=self._buf(("dattn", M), (M, self.Nq)),
                    dqkv=self._buf(("dqkv", M), (M, self.Nqkv)), dx_mid=self._buf(("dx_mid", M), (M, H)),
-                   delta=self._buf(("delta", Bn, S), (Bn, self.nh, Sp), torch.float32))
-        lws = _hip.LayerBwdWs(wsb["dact"].data_ptr(), wsb["dxn"].data_ptr(), wsb["dattn"].data_ptr(), wsb["dqkv"].data_ptr(),
-                              wsb["dx_mid"].data_ptr(), wsb["delta"].data_ptr(), self._norm_ws.data_ptr())
-        cur, nxt = dxa, dxb
+                   delta=self._buf(("delta", Bn, S), (Bn, self.nh, _align(S, 64)), torch.float32), norm_ws=self._norm_ws)
+        return wsb, _hip.LayerBwdWs(*(wsb[n].data_ptr() for n, _ in _hip.LayerBwdWs._fields_))
+
+    def _layers_backward(self, ctx, layer_bwd, cur, nxt):
+        """the decoder layers in reverse: layer_bwd(l, a, x_in, cur, nxt) turns d x_out (`cur`) into d x_in (`nxt`) and writes layer l's
+        parameter gradients.  Under gradient checkpointing each layer's forward is re-run first, as the pass itself ran it (same adapters,
+        same dropout seeds).  -> the gradient of the decoder's input"""
+        ws, Bn, S = ctx["ws"], ctx["Bn"], ctx["S"]
         for l in range(self.L - 1, -1, -1):
             a = ctx["acts"][l]
             x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
             if ctx["ckpt"]:
-                self._layer_fwd_call(ws, l, a, x_in, ctx["embed"], Bn, S, True, False, None)
-            _hip.call("vlr_decoder_layer_bwd", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), acc,
-                      a["struct"], lws, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
-            if f"l{l}.bqkv" in self.gv:              # bias of the fused q|k|v projection: column sum of this layer's d qkv (post rope-transpose)
-                _hip.call("vlr_colsum", wsb["dqkv"], M, self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
+                self._layer_fwd_call(ws, l, a, x_in, ctx["embed"], Bn, S, True, ctx["use_lora"], ctx["lora_seed"])
+            layer_bwd(l, a, x_in, cur, nxt)
             cur, nxt = nxt, cur
-            if self.reducer is not None:
+            if self.lora is None and self.reducer is not None:       # (LoRA: one bucket when the backward is done)
                 self.reducer.bucket_ready(f"layer{l}")
-        self._embed_backward(ctx, cur, acc)
-        self.grad_fresh = False
-        if self.reducer is not None:
-            self.reducer.bucket_ready("tail")
+        return cur
+
+    def _layer_bwd(self, ctx, acc, wsb, lws):
+        """the per-layer backward of this engine's current mode, for _layers_backward"""
+        ws, Bn, S, M = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"]
+        if self.lora is None:
+            def full(l, a, x_in, cur, nxt):
+                _hip.call("vlr_decoder_layer_bwd", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), acc,
+                          a["struct"], lws, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
+                if f"l{l}.bqkv" in self.gv:          # bias of the fused q|k|v projection: column sum of this layer's d qkv (post rope-transpose)
+                    _hip.call("vlr_colsum", wsb["dqkv"], M, self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
+            return full
+        # data gradients through the frozen decoder + adapter gradients
+        ws_v = self._buf(("lora_v", M), (M, 3 * self.lora["r"]))
+        drop = self.lora["dropout"] > 0 and self.training
+        scratch = self._buf(("lora_scratch", M), (M, max(self.H, self.I))) if drop else None     # fallback path of the fused dropout-accumulate
+
+        def lora(l, a, x_in, cur, nxt):
+            lw, lg = self._lora_structs(l, train=True, M=M, acts=a)
+            _hip.call("vlr_decoder_layer_bwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, lg, acc, a["struct"],
+                      a.get("shared", a)["u"], lws, ws_v, scratch, ctx["lora_seed"] + 8 * l, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
+        return lora
 
     def _embed_backward(self, ctx, cur, acc):
         """gradient of the merged embeddings `cur` [M,H] -> embed_tokens rows, projector (and image_newline) gradients"""
@@ -1124,40 +1164,6 @@ class LlavaHipEngine:
         _hip.call("vlr_gelu_bwd", ctx["proj_z"], dh, dz, dz.numel())
         _hip.call("vlr_colsum", dz, n_rows, H, H, self.gv["proj.b1"], acc, self._colsum_ws)
         _hip.call("vlr_gemm_bf16", 2, dz, ctx["vit_feat"], self.gv["proj.w1"], None, None, H, D, n_rows, H, D, D, 0, 0, acc, 0)
-
-    def _hidden_backward_lora(self, ctx, dhidden, dxa, dxb):
-        """LoRA backward: data gradients through the frozen decoder + adapter gradients only; nothing below the first
-        decoder layer is trainable (embedding, projector and vision tower are not target modules), so it stops there."""
-        if ctx.get("lora_seed") is None:
-            raise RuntimeError("backward through a pass that ran with the adapters disabled")
-        ws = ctx["ws"]
-        Bn, S, M, H, I = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I
-        acc = int(not self.grad_fresh)
-        Sp = _align(S, 64)
-        r = self.lora["r"]
-        self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, None, 0, M)
-        wsb = dict(dact=self._buf(("dact", M), (M, I)), dxn=self._buf(("dxn", M), (M, H)), dattn=self._buf(("dattn", M), (M, H)),
-                   dqkv=self._buf(("dqkv", M), (M, 3 * H)), dx_mid=self._buf(("dx_mid", M), (M, H)),
-                   delta=self._buf(("delta", Bn, S), (Bn, self.nh, Sp), torch.float32))
-        lws = _hip.LayerBwdWs(wsb["dact"].data_ptr(), wsb["dxn"].data_ptr(), wsb["dattn"].data_ptr(), wsb["dqkv"].data_ptr(),
-                              wsb["dx_mid"].data_ptr(), wsb["delta"].data_ptr(), self._norm_ws.data_ptr())
-        ws_v = self._buf(("lora_v", M), (M, 3 * r))
-        drop = self.lora["dropout"] > 0 and self.training
-        scratch = self._buf(("lora_scratch", M), (M, max(H, I))) if drop else None     # fallback path of the fused dropout-accumulate
-        cur, nxt = dxa, dxb
-        for l in range(self.L - 1, -1, -1):
-            a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
-            lw, lg = self._lora_structs(l, train=True, M=M, acts=a)
-            if ctx["ckpt"]:
-                self._layer_fwd_call(ws, l, a, x_in, ctx["embed"], Bn, S, True, True, ctx["lora_seed"])
-            sh = a.get("shared", a)
-            _hip.call("vlr_decoder_layer_bwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, lg, acc, a["struct"], sh["u"],
-                      lws, ws_v, scratch, ctx["lora_seed"] + 8 * l, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
-            cur, nxt = nxt, cur
-        self.grad_fresh = False
-        if self.reducer is not None:
-            self.reducer.bucket_ready("lora")
 
     def make_reducer(self, group=None):
         """DDP gradient reducer over the trainable flat gradient buffer (full fine-tuning: one bucket per decoder layer in

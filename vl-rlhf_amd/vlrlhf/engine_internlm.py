@@ -8,34 +8,36 @@ What is not:
   * every decoder linear carries a PLoRA pair that acts on the IMAGE rows only: y[img] += Plora_B(Plora_A(dropout(x[img]))) (build_mlp.py
     :158-203).  They are base-model weights - trained by a full fine-tune, frozen but ACTIVE (reference pass included) under peft LoRA,
     which the shipped script stacks on top of the same five linears.
-The PLoRA term is a low-rank update of a row subset, so the decoder layer is composed HERE from the library's primitives instead of
-the fused `vlr_decoder_layer_*` calls: the image rows of the batch are gathered into a compact [R, in] matrix (vlr_gather_rows /
-vlr_rows_gather), run through two skinny GEMMs and added back (vlr_rows_add).  Correctness first: the projections run un-fused (the
-adapter terms must reach the accumulator before RoPE / SwiGLU), ~110 launches per layer and pass.  DESIGN.md lists what a fused version
-needs (a row-masked adapter segment in the GEMM K loop).
+Every pass runs on the library's layer calls, with the adapters as segments in the K loop of the fused projections (qkv + RoPE,
+SwiGLU, residual) and the image rows as the PLoRA row mask, on the fp32 residual stream:
+  * full fine-tune and reference pass: `vlr_decoder_layer_fwd_lora_ex` / `bwd_lora_ex` with the PLoRA pairs as the adapters (base and
+    PLoRA gradients);
+  * peft LoRA over the frozen PLoRA decoder: `vlr_decoder_layer_fwd_lora2` / `bwd_lora2`, two adapters per projection.
+Both can be re-run layer by layer, so gradient checkpointing applies.  VLR_ILM_LORA_FUSED=0 replaces the second one by a layer composed
+HERE from the library's bf16 primitives - the cross-check of the two-adapter calls: the projections run un-fused, the image rows are
+gathered into a compact [R, in] matrix (vlr_gather_rows / vlr_rows_gather), run through two skinny GEMMs and added back (vlr_rows_add),
+the peft adapters accumulate on all rows; bf16 residual stream, ~110 launches per layer and pass, activations kept (no checkpointing).
 Dropout convention (the reference draws from torch's RNG): target t of layer l masks the compact [R, in] matrix with the counter-based
 mask of vlr_dropout(seed + 8 l + t), t = 0 wqkv, 3 wo, 4 w1, 5 w3, 6 w2; PLoRA and LoRA use different seed bases."""
 import math
 import os
-from typing import Dict
 
 import torch
 
 from . import _hip
-from .engine import BF16, LlavaHipEngine, _align
+from .engine import BF16, LlavaHipEngine
 
 PLORA_T = dict(qkv=0, o=3, g=4, u=5, d=6)
 PLORA_SEED_XOR = 0x2A5A5A5A5A
 
 
 class InternLMHipEngine(LlavaHipEngine):
-    custom_layers = True
     supports_kv_cache = False      # the PLoRA layers are composed per pass (image rows): generate re-runs the forward
     vision_prefix = "vit.vision_tower."
 
     @property
     def supports_ckpt(self):       # the C layer passes (full fine-tune / reference / LoRA over PLoRA) can be re-run; the Python-composed peft-LoRA layer keeps its activations
-        return (self.lora is None or bool(getattr(self, "lora_fused", False))) and bool(getattr(self, "fused_forward", True))      # (getattr: read by the base __init__)
+        return self.lora is None or self.lora_fused
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 8192):
         c = dict(cfg, family="internlm_xc2")
@@ -47,11 +49,8 @@ class InternLMHipEngine(LlavaHipEngine):
         self.plora_p = float(c.get("plora_dropout", 0.05))
         self._plora_calls = 0
         self.plora_seed = int(c.get("seed", 0))
-        self.fused_forward = os.environ.get("VLR_ILM_FUSED", "1") != "0"     # PLoRA-only passes on the C layer calls (0: the Python-composed layer everywhere)
         self.lora_fused = False                  # set by enable_lora: peft LoRA over PLoRA on vlr_decoder_layer_*_lora2
         self.last_train_plora_seed = None        # PLoRA dropout seed of the last training-mode policy pass
-        if not self.fused_forward:
-            self._to_bf16_stream()
 
     # ------------------------------------------------------------------------------------------------ embed
     def _embed_inputs(self, ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta):
@@ -76,7 +75,7 @@ class InternLMHipEngine(LlavaHipEngine):
         residual projections, one adapter segment [B_lora | B_plora] in the K loop, fp32 residual stream.  VLR_ILM_LORA_FUSED=0 composes
         the layer from bf16 primitives instead (rows_add, accumulate GEMMs; bf16 residual stream) - the cross-check of the fused path."""
         super().enable_lora(r, alpha, dropout, seed)
-        self.lora_fused = bool(self.fused_forward) and os.environ.get("VLR_ILM_LORA_FUSED", "1") != "0"
+        self.lora_fused = os.environ.get("VLR_ILM_LORA_FUSED", "1") != "0"
         if not self.lora_fused:
             self._to_bf16_stream()
 
@@ -110,7 +109,6 @@ class InternLMHipEngine(LlavaHipEngine):
         g = _hip.LoraGrads(*(self.gv[f"l{l}.{n}"].data_ptr() for n in names)) if self.gv is not None else None
         return w, g
 
-
     def _embed_backward(self, ctx, cur, acc):
         """the projector is frozen with the tower: only tok_embeddings receives a gradient in front of the decoder"""
         if not acc:
@@ -131,68 +129,24 @@ class InternLMHipEngine(LlavaHipEngine):
     def _gemm(self, layout, A, B, C, M, N, K, lda, ldb, ldc, residual=None, ldr=0, accumulate=0, alpha=1.0):
         _hip.call("vlr_gemm_bf16_scaled", layout, A, B, C, None, residual, M, N, K, lda, ldb, ldc, ldr, 0, accumulate, 0, float(alpha))
 
-    def _plora_fwd(self, ws, l, key, x_in, n_in, y, ldy, n_out, ex, train, seed, keep, tag):
+    def _plora_fwd(self, ws, l, key, x_in, n_in, y, ldy, n_out, ex, train, seed, tag):
         """y[img rows] += scale * (drop(x_in[img rows]) A^T) B^T;  y is a [M, n_out] column block with row stride ldy"""
         R, rows, r = ex["R"], ex["rows"], self.plora_r
         if R == 0:
-            return None
+            return
         A, B = self._pab(ws.v, l, key)
-        xs = torch.empty(R, n_in, dtype=BF16, device=self.dev) if keep else self._buf((tag, "pl_xs", R, n_in), (R, n_in))
+        xs = self._buf((tag, "pl_xs", R, n_in), (R, n_in))
         _hip.call("vlr_gather_rows", x_in, rows, xs, R, n_in)
         if train and self.plora_p > 0:
             _hip.call("vlr_dropout", xs, xs, R * n_in, self.plora_p, seed + PLORA_T[key], 1.0, 0)
-        up = torch.empty(R, r, dtype=BF16, device=self.dev) if keep else self._buf((tag, "pl_up", R), (R, r))
+        up = self._buf((tag, "pl_up", R), (R, r))
         self._gemm(0, xs, A, up, R, r, n_in, n_in, n_in, r, alpha=self.plora_scale)
         yp = self._buf((tag, "pl_y", R, n_out), (R, n_out))
         self._gemm(0, up, B, yp, R, n_out, r, r, r, n_out)
         _hip.call("vlr_rows_add", yp, rows, y, ldy, R, n_out)
-        return (xs, up) if keep else None
 
-    def _plora_u(self, ws, l, key, x_in, n_in, u, ldu, ex, train, seed, keep, tag):
-        """u [M][ldu] (column block of r) = scale * drop(x_in[img rows]) A^T on the image rows, ZERO on the text rows: the adapter-segment
-        GEMMs (vlr_gemm_*_lora) then add u B^T inside the K loop of the base projection - PLoRA without a separate pass over y"""
-        R, rows, r = ex["R"], ex["rows"], self.plora_r
-        M = u.shape[0]
-        if ldu == r:
-            u.zero_()
-        else:
-            u[:, :r].zero_()
-        if R == 0:
-            return None
-        A, _ = self._pab(ws.v, l, key)
-        xs = torch.empty(R, n_in, dtype=BF16, device=self.dev) if keep else self._buf((tag, "pl_xs", R, n_in), (R, n_in))
-        _hip.call("vlr_gather_rows", x_in, rows, xs, R, n_in)
-        if train and self.plora_p > 0:
-            _hip.call("vlr_dropout", xs, xs, R * n_in, self.plora_p, seed + PLORA_T[key], 1.0, 0)
-        up = torch.empty(R, r, dtype=BF16, device=self.dev) if keep else self._buf((tag, "pl_up", R), (R, r))
-        self._gemm(0, xs, A, up, R, r, n_in, n_in, n_in, r, alpha=self.plora_scale)
-        _hip.call("vlr_rows_add", up, rows, u, ldu, R, r)
-        return (xs, up) if keep else None
-
-    def _layer_forward_fused(self, ws, l, a, x, e, Bn, S, save, train, pseed, keep_p):
-        """policy (full fine-tune) / reference pass: only PLoRA sits on the linears, and it rides the fused projections"""
-        c, H, I, N, M, r = self.llama_cfg, self.H, self.I, self.Nqkv, Bn * S, self.plora_r
-        ex, pos, mask, tag = e["extra"], e["pos"], e["mask"], e["tag"]
-        kept = {}
-        ub = self._buf((tag, "pl_ufull", M), (M, 2 * r))
-        u1 = ub[:, :r]
-        _hip.call("vlr_rmsnorm_fwd", x, ws.v[f"l{l}.ln1"], a["xn1"], a["rstd1"], M, H, c.rms_eps)
-        kept["p_qkv"] = self._plora_u(ws, l, "qkv", a["xn1"], H, u1, 2 * r, ex, train, pseed, keep_p, tag)
-        _hip.call("vlr_gemm_qkv_rope_lora", a["xn1"], ws.v[f"l{l}.wqkv"], None, a["qkv"], pos, self.cos, self.sin, M, N, self.Nq + self.Nkv, H, H,
-                  self.hd, self.max_pos, u1, 2 * r, ws.v[f"l{l}.pb_qkv"], r, N, 0)
-        _hip.call("vlr_attn_fwd_gqa", a["qkv"], a["qkv"][:, self.Nq:], a["qkv"][:, self.Nq + self.Nkv:], N, a["attn"], self.Nq, a["lse"], mask,
-                  Bn, S, self.nh, self.nkv, self.hd, 1, 1.0 / math.sqrt(self.hd))
-        kept["p_o"] = self._plora_u(ws, l, "o", a["attn"], self.Nq, u1, 2 * r, ex, train, pseed, keep_p, tag)
-        _hip.call("vlr_gemm_lora", a["attn"], self.Nq, ws.v[f"l{l}.wo"], a["x_mid"], H, x, H, M, H, self.Nq, u1, 2 * r, ws.v[f"l{l}.pb_o"], r)
-        _hip.call("vlr_rmsnorm_fwd", a["x_mid"], ws.v[f"l{l}.ln2"], a["xn2"], a["rstd2"], M, H, c.rms_eps)
-        kept["p_g"] = self._plora_u(ws, l, "g", a["xn2"], H, ub, 2 * r, ex, train, pseed, keep_p, tag)
-        kept["p_u"] = self._plora_u(ws, l, "u", a["xn2"], H, ub[:, r:], 2 * r, ex, train, pseed, keep_p, tag)
-        _hip.call("vlr_gemm_swiglu_lora", a["xn2"], ws.v[f"l{l}.wgu"], a["gu"], a["act"], M, I, H, H, ub, 2 * r, ws.v[f"l{l}.pb_gu"], r)
-        kept["p_d"] = self._plora_u(ws, l, "d", a["act"], I, u1, 2 * r, ex, train, pseed, keep_p, tag)
-        _hip.call("vlr_gemm_lora", a["act"], I, ws.v[f"l{l}.wdown"], a["x_out"], H, a["x_mid"], H, M, H, I, u1, 2 * r, ws.v[f"l{l}.pb_d"], r)
-        return kept
-
-    def _plora_bwd(self, ws, l, key, kept, dy, lddy, n_out, dx, n_in, ex, train, seed, acc, trainable):
+    def _plora_bwd(self, ws, l, key, dy, lddy, n_out, dx, n_in, ex, train, seed):
+        """dx[img rows] += the frozen PLoRA pair's input gradient"""
         R, rows, r = ex["R"], ex["rows"], self.plora_r
         if R == 0:
             return
@@ -201,11 +155,6 @@ class InternLMHipEngine(LlavaHipEngine):
         _hip.call("vlr_rows_gather", dy, lddy, rows, dyr, R, n_out)
         v = self._buf(("pl_v", R), (R, r))
         self._gemm(1, dyr, B, v, R, r, n_out, n_out, r, r)                                   # v = dy B
-        if trainable:
-            xs, up = kept
-            gA, gB = self._pab(self.gv, l, key)
-            self._gemm(2, dyr, up, gB, n_out, r, R, n_out, r, r, accumulate=acc)            # dB = dy^T (s u)
-            self._gemm(2, v, xs, gA, r, n_in, R, r, n_in, n_in, accumulate=acc, alpha=self.plora_scale)   # dA = s v^T drop(x)
         dxr = self._buf(("pl_dx", R, n_in), (R, n_in))
         self._gemm(1, v, A, dxr, R, n_in, r, r, n_in, n_in, alpha=self.plora_scale)
         if train and self.plora_p > 0:
@@ -251,48 +200,42 @@ class InternLMHipEngine(LlavaHipEngine):
         #        key   lora group, sub-target, lora_B row0, in, out
         return dict(qkv=("qkv", 0, 0, H, N), o=("o", 0, 0, self.Nq, H), g=("gu", 0, 0, H, I), u=("gu", 1, I, H, I), d=("down", 0, 0, I, H))
 
-    def _layer_forward(self, ws, l, a, x, e, Bn, S, save, use_lora, lora_seed):
-        c, H, I, N, M = self.llama_cfg, self.H, self.I, self.Nqkv, Bn * S
-        ex, pos, mask = e["extra"], e["pos"], e["mask"]
-        train = self.training and ws is self.policy and bool(e.get("grad_pass", save))     # (a checkpointed forward keeps nothing but is the same pass)
+    def _layer_fwd_call(self, ws, l, a, x, e, Bn, S, keep, use_lora, lora_seed):
+        M = Bn * S
+        train = self.training and ws is self.policy and bool(e.get("grad_pass", keep))     # (a checkpointed forward keeps nothing but is the same pass)
         pseed = e["plora_seed"]
-        keep_p = save and self.lora is None          # PLoRA weights are trainable only in a full fine-tune
         if train and l == 0:
             self.last_train_plora_seed = pseed       # (tests: the oracle regenerates the pass's masks from it)
-        if not use_lora and self.fused_forward:
+        if keep:
+            a["pseed"], a["train"] = pseed + 8 * l, train
+        if use_lora and not self.lora_fused:
+            return self._layer_fwd_composed(ws, l, a, x, e, Bn, S, keep, train, lora_seed)
+        pw, _ = self._plora_structs(ws, l, self.plora_p if train else 0.0, M, a)
+        if not use_lora:
             # only PLoRA sits on the linears (reference pass; policy pass of a full fine-tune): the C layer pass with the PLoRA pairs as
-            # its adapters and the image rows as the row mask - fused qkv + RoPE / SwiGLU / residual projections, fp32 residual stream
-            M = Bn * S
-            sh = a.get("shared", a)
-            if "u" not in sh or sh["u"].shape[1] != 7 * self.plora_r:
-                sh["u"] = torch.empty(M, 7 * self.plora_r, dtype=BF16, device=self.dev)
-            pw, _ = self._plora_structs(ws, l, self.plora_p if train else 0.0, M, a)
-            _hip.call("vlr_decoder_layer_fwd_lora_ex", self.llama_cfg, self.layer_weights(ws, l), pw, a["struct"], sh["u"], None,
+            # its adapters and the image rows as the row mask
+            u = self._adapter_scratch(a, "u", M, 7 * self.plora_r)
+            _hip.call("vlr_decoder_layer_fwd_lora_ex", self.llama_cfg, self.layer_weights(ws, l), pw, a["struct"], u, None,
                       pseed + 8 * l, e["img_map"], x, e["pos"], e["mask"], Bn, S)
-            if save:
-                a["pseed"], a["train"] = pseed + 8 * l, train
-            return
-        if use_lora and self.lora_fused:
-            R = self.lora["r"] + self.plora_r
-            sh = a.get("shared", a)
-            if "u2" not in sh or sh["u2"].shape[1] != 7 * R:
-                sh["u2"] = torch.empty(M, 7 * R, dtype=BF16, device=self.dev)
+        else:
+            u2 = self._adapter_scratch(a, "u2", M, 7 * (self.lora["r"] + self.plora_r))
             lw, _ = self._lora_structs(l, train=True, M=M, acts=a)
-            pw, _ = self._plora_structs(ws, l, self.plora_p if train else 0.0, M, a)
             bc = self._bcomb(ws, l)
-            _hip.call("vlr_decoder_layer_fwd_lora2", self.llama_cfg, self.layer_weights(ws, l), lw, pw, bc, a["struct"], sh["u2"],
+            _hip.call("vlr_decoder_layer_fwd_lora2", self.llama_cfg, self.layer_weights(ws, l), lw, pw, bc, a["struct"], u2,
                       lora_seed + 8 * l, pseed + 8 * l, e["img_map"], x, e["pos"], e["mask"], Bn, S)
-            if save:
-                a["pseed"], a["train"] = pseed + 8 * l, train
-            return
-        kept: Dict[str, object] = {}
+
+    def _layer_fwd_composed(self, ws, l, a, x, e, Bn, S, save, train, lora_seed):
+        """peft LoRA over the frozen PLoRA decoder from bf16 primitives (VLR_ILM_LORA_FUSED=0); save: keeps what _layer_bwd_composed reads"""
+        c, H, I, N, M = self.llama_cfg, self.H, self.I, self.Nqkv, Bn * S
+        ex, pos, mask, tag = e["extra"], e["pos"], e["mask"], e["tag"]
+        pseed = e["plora_seed"] + 8 * l
+        kept = {}
         tg = self._targets()
 
         def adapters(key, x_in, y, ldy):
             grp, t, row0, n_in, n_out = tg[key]
-            kept["p_" + key] = self._plora_fwd(ws, l, key, x_in, n_in, y, ldy, n_out, ex, train, pseed + 8 * l, keep_p, e["tag"])
-            if use_lora:
-                kept["l_" + key] = self._lora_fwd(l, grp, t, x_in, n_in, y, ldy, n_out, row0, lora_seed + 8 * l + PLORA_T[key], save, M, e["tag"])
+            self._plora_fwd(ws, l, key, x_in, n_in, y, ldy, n_out, ex, train, pseed, tag)
+            kept[key] = self._lora_fwd(l, grp, t, x_in, n_in, y, ldy, n_out, row0, lora_seed + 8 * l + PLORA_T[key], save, M, tag)
 
         _hip.call("vlr_rmsnorm_fwd", x, ws.v[f"l{l}.ln1"], a["xn1"], a["rstd1"], M, H, c.rms_eps)
         self._gemm(0, a["xn1"], ws.v[f"l{l}.wqkv"], a["qkv"], M, N, H, H, H, N)
@@ -311,137 +254,69 @@ class InternLMHipEngine(LlavaHipEngine):
         adapters("d", a["act"], a["x_out"], H)
         if save:
             a["kept"] = kept
-            a["pseed"] = pseed + 8 * l
-            a["train"] = train
 
     # ------------------------------------------------------------------------------------------------ backward
-    def _hidden_backward_full(self, ctx, dxa, dxb, acc):
-        """full fine-tune: vlr_decoder_layer_bwd_lora_ex per layer - base AND PLoRA gradients, the adapters restricted to the image rows;
-        with gradient checkpointing each layer's forward is re-run (same dropout seed) right before its backward"""
-        ws = ctx["ws"]
-        Bn, S, M, H, I, N = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I, self.Nqkv
-        Sp = _align(S, 64)
-        r = self.plora_r
-        wsb = dict(dact=self._buf(("dact", M), (M, I)), dxn=self._buf(("dxn", M), (M, H)), dattn=self._buf(("dattn", M), (M, self.Nq)),
-                   dqkv=self._buf(("dqkv", M), (M, N)), dx_mid=self._buf(("dx_mid", M), (M, H)),
-                   delta=self._buf(("delta", Bn, S), (Bn, self.nh, Sp), torch.float32))
-        lws = _hip.LayerBwdWs(wsb["dact"].data_ptr(), wsb["dxn"].data_ptr(), wsb["dattn"].data_ptr(), wsb["dqkv"].data_ptr(),
-                              wsb["dx_mid"].data_ptr(), wsb["delta"].data_ptr(), self._norm_ws.data_ptr())
-        ws_v = self._buf(("plora_v", M), (M, 3 * r))
-        scratch = self._buf(("plora_scratch", M), (M, max(H, I)))
+    def _layer_bwd(self, ctx, acc, wsb, lws):
+        ws, Bn, S, M = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"]
         e = ctx["embed"]
-        cur, nxt = dxa, dxb
-        for l in range(self.L - 1, -1, -1):
-            a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
-            if ctx["ckpt"]:
-                self._layer_forward(ws, l, a, x_in, e, Bn, S, True, False, None)
-            train = a["train"]
-            pw, pg = self._plora_structs(ws, l, self.plora_p if train else 0.0, M, a)
-            sh = a.get("shared", a)
-            _hip.call("vlr_decoder_layer_bwd_lora_ex", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), pw, pg, acc, a["struct"],
-                      sh["u"], lws, ws_v, scratch, a["pseed"], e["img_map"], x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
-            cur, nxt = nxt, cur
-            if self.reducer is not None:
-                self.reducer.bucket_ready(f"layer{l}")
-        self._embed_backward(ctx, cur, acc)
-        self.grad_fresh = False
-        if self.reducer is not None:
-            self.reducer.bucket_ready("tail")
+        if self.lora is None:
+            # full fine-tune: base AND PLoRA gradients, the adapters restricted to the image rows
+            ws_v = self._buf(("plora_v", M), (M, 3 * self.plora_r))
+            scratch = self._buf(("plora_scratch", M), (M, max(self.H, self.I)))
 
-    def _hidden_backward_lora2(self, ctx, dxa, dxb, acc):
-        """peft LoRA over the frozen PLoRA decoder: vlr_decoder_layer_bwd_lora2 per layer - gradients of the LoRA pairs only, dx through the
-        base projections and BOTH adapters (PLoRA on the image rows, its own dropout stream)"""
-        ws = ctx["ws"]
-        Bn, S, M, H, I, N = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I, self.Nqkv
-        Sp = _align(S, 64)
-        R = self.lora["r"] + self.plora_r
-        wsb = dict(dact=self._buf(("dact", M), (M, I)), dxn=self._buf(("dxn", M), (M, H)), dattn=self._buf(("dattn", M), (M, self.Nq)),
-                   dqkv=self._buf(("dqkv", M), (M, N)), dx_mid=self._buf(("dx_mid", M), (M, H)),
-                   delta=self._buf(("delta", Bn, S), (Bn, self.nh, Sp), torch.float32))
-        lws = _hip.LayerBwdWs(wsb["dact"].data_ptr(), wsb["dxn"].data_ptr(), wsb["dattn"].data_ptr(), wsb["dqkv"].data_ptr(),
-                              wsb["dx_mid"].data_ptr(), wsb["delta"].data_ptr(), self._norm_ws.data_ptr())
-        ws_v = self._buf(("lora2_v", M), (M, 3 * R))
-        e = ctx["embed"]
-        cur, nxt = dxa, dxb
-        for l in range(self.L - 1, -1, -1):
-            a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
-            if ctx["ckpt"]:
-                self._layer_forward(ws, l, a, x_in, e, Bn, S, True, True, ctx["lora_seed"])
+            def full(l, a, x_in, cur, nxt):
+                pw, pg = self._plora_structs(ws, l, self.plora_p if a["train"] else 0.0, M, a)
+                _hip.call("vlr_decoder_layer_bwd_lora_ex", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), pw, pg, acc,
+                          a["struct"], a.get("shared", a)["u"], lws, ws_v, scratch, a["pseed"], e["img_map"], x_in, cur, nxt,
+                          ctx["pos"], ctx["mask"], Bn, S)
+            return full
+        if not self.lora_fused:
+            return self._layer_bwd_composed(ctx, acc, wsb)
+        # peft LoRA over the frozen PLoRA decoder: gradients of the LoRA pairs only, dx through the base projections and BOTH adapters
+        # (PLoRA on the image rows, its own dropout stream)
+        ws_v = self._buf(("lora2_v", M), (M, 3 * (self.lora["r"] + self.plora_r)))
+
+        def lora2(l, a, x_in, cur, nxt):
             lw, lg = self._lora_structs(l, train=True, M=M, acts=a)
             pw, _ = self._plora_structs(ws, l, self.plora_p if a["train"] else 0.0, M, a)
             bc = self._bcomb(ws, l)
-            sh = a.get("shared", a)
-            _hip.call("vlr_decoder_layer_bwd_lora2", self.llama_cfg, self.layer_weights(ws, l), lw, lg, pw, bc, acc, a["struct"], sh["u2"], lws,
-                      ws_v, ctx["lora_seed"] + 8 * l, a["pseed"], e["img_map"], x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
-            cur, nxt = nxt, cur
-        self.grad_fresh = False
-        if self.reducer is not None:
-            self.reducer.bucket_ready("lora")
+            _hip.call("vlr_decoder_layer_bwd_lora2", self.llama_cfg, self.layer_weights(ws, l), lw, lg, pw, bc, acc, a["struct"],
+                      a.get("shared", a)["u2"], lws, ws_v, ctx["lora_seed"] + 8 * l, a["pseed"], e["img_map"], x_in, cur, nxt,
+                      ctx["pos"], ctx["mask"], Bn, S)
+        return lora2
 
-    def _hidden_backward_custom(self, ctx, dhidden, dxa, dxb):
-        ws = ctx["ws"]
-        Bn, S, M, H, I, N = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I, self.Nqkv
-        full = self.lora is None
-        acc = int(not self.grad_fresh)
-        Sp = _align(S, 64)
+    def _layer_bwd_composed(self, ctx, acc, wsb):
+        """backward of _layer_fwd_composed: gradients of the LoRA pairs, dx through the base projections and both adapters"""
+        ws, Bn, S, M, H, I, N = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"], self.H, self.I, self.Nqkv
         ex = ctx["extra"]
-        self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"] if full else None, acc if full else 0, M)
-        if full and self.fused_forward:
-            return self._hidden_backward_full(ctx, dxa, dxb, acc)
-        if not full and self.lora_fused:
-            return self._hidden_backward_lora2(ctx, dxa, dxb, acc)
-        dact, dxn = self._buf(("dact", M), (M, I)), self._buf(("dxn", M), (M, H))
-        dattn, dqkv = self._buf(("dattn", M), (M, self.Nq)), self._buf(("dqkv", M), (M, N))
-        dx_mid = self._buf(("dx_mid", M), (M, H))
-        delta = self._buf(("delta", Bn, S), (Bn, self.nh, Sp), torch.float32)
+        dact, dxn, dattn, dqkv, dx_mid, delta = (wsb[k] for k in ("dact", "dxn", "dattn", "dqkv", "dx_mid", "delta"))
         tg = self._targets()
-        cur, nxt = dxa, dxb
-        for l in range(self.L - 1, -1, -1):
-            a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
+
+        def composed(l, a, x_in, cur, nxt):
             kept, pseed, train = a["kept"], a["pseed"], a["train"]
-            g = (lambda k: self.gv[f"l{l}.{k}"]) if full else (lambda k: None)
 
             def adapters_bwd(key, dy, lddy, dx):
                 grp, t, row0, n_in, n_out = tg[key]
-                self._plora_bwd(ws, l, key, kept["p_" + key], dy, lddy, n_out, dx, n_in, ex, train, pseed, acc, full)
-                if not full:
-                    self._lora_bwd(l, grp, t, kept["l_" + key], dy, lddy, n_out, row0, dx, n_in, ctx["lora_seed"] + 8 * l + PLORA_T[key], acc, M)
+                self._plora_bwd(ws, l, key, dy, lddy, n_out, dx, n_in, ex, train, pseed)
+                self._lora_bwd(l, grp, t, kept[key], dy, lddy, n_out, row0, dx, n_in, ctx["lora_seed"] + 8 * l + PLORA_T[key], acc, M)
 
             # ---- MLP
-            if full:
-                self._gemm(2, cur, a["act"], g("wdown"), H, I, M, H, I, I, accumulate=acc)
             self._gemm(1, cur, ws.v[f"l{l}.wdown"], dact, M, I, H, H, I, I)
             adapters_bwd("d", cur, H, dact)
             _hip.call("vlr_swiglu_bwd", a["gu"], dact, M, I)                  # gu now holds [d gate | d up]
-            if full:
-                self._gemm(2, a["gu"], a["xn2"], g("wgu"), 2 * I, H, M, 2 * I, H, H, accumulate=acc)
             self._gemm(1, a["gu"], ws.v[f"l{l}.wgu"], dxn, M, H, 2 * I, 2 * I, H, H)
             adapters_bwd("g", a["gu"], 2 * I, dxn)
             adapters_bwd("u", a["gu"][:, I:], 2 * I, dxn)
-            _hip.call("vlr_rmsnorm_bwd", dxn, a["x_mid"], ws.v[f"l{l}.ln2"], a["rstd2"], cur, dx_mid, g("ln2"), acc if full else 0, self._norm_ws, M, H)
+            _hip.call("vlr_rmsnorm_bwd", dxn, a["x_mid"], ws.v[f"l{l}.ln2"], a["rstd2"], cur, dx_mid, None, 0, self._norm_ws, M, H)
             # ---- attention
-            if full:
-                self._gemm(2, dx_mid, a["attn"], g("wo"), H, self.Nq, M, H, self.Nq, self.Nq, accumulate=acc)
             self._gemm(1, dx_mid, ws.v[f"l{l}.wo"], dattn, M, self.Nq, H, H, self.Nq, self.Nq)
             adapters_bwd("o", dx_mid, H, dattn)
             _hip.call("vlr_attn_bwd_gqa", a["qkv"], a["qkv"][:, self.Nq:], a["qkv"][:, self.Nq + self.Nkv:], N, a["attn"], dattn, self.Nq, a["lse"],
                       delta, ctx["mask"], dqkv, dqkv[:, self.Nq:], dqkv[:, self.Nq + self.Nkv:], N, Bn, S, self.nh, self.nkv, self.hd, 1,
                       1.0 / math.sqrt(self.hd))
             _hip.call("vlr_rope_heads", dqkv, ctx["pos"], self.cos, self.sin, M, self.nh + self.nkv, self.hd, N, self.max_pos, 1)
-            if full:
-                self._gemm(2, dqkv, a["xn1"], g("wqkv"), N, H, M, N, H, H, accumulate=acc)
             self._gemm(1, dqkv, ws.v[f"l{l}.wqkv"], dxn, M, H, N, N, H, H)
             adapters_bwd("qkv", dqkv, N, dxn)
-            _hip.call("vlr_rmsnorm_bwd", dxn, x_in, ws.v[f"l{l}.ln1"], a["rstd1"], dx_mid, nxt, g("ln1"), acc if full else 0, self._norm_ws, M, H)
-            cur, nxt = nxt, cur
+            _hip.call("vlr_rmsnorm_bwd", dxn, x_in, ws.v[f"l{l}.ln1"], a["rstd1"], dx_mid, nxt, None, 0, self._norm_ws, M, H)
             a["kept"] = None
-            if full and self.reducer is not None:
-                self.reducer.bucket_ready(f"layer{l}")
-        if full:
-            self._embed_backward(ctx, cur, acc)
-        self.grad_fresh = False
-        if self.reducer is not None:
-            self.reducer.bucket_ready("tail" if full else "lora")
+        return composed
