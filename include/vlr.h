@@ -548,6 +548,39 @@ int vlr_decoder_layer_decode(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
                              const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len,
                              vlr_stream_t stream);
 
+/* ---- GPTQ int4 base weights (q_lora: LoRA adapters over a 4-bit base that stays packed in HBM; replaces auto_gptq's QuantLinear
+ *      under GPTQConfig(bits=4, disable_exllama=True), reference utils/auto_load.py:520-548).  Checkpoint format "v1" (AutoGPTQ), for a
+ *      linear y = x W^T, W [N][K], group size g:
+ *        qweight int32 [K/8][N]    nibble j (bits 4j .. 4j+3) of qweight[k8][n] = q[8 k8 + j][n], 0 .. 15
+ *        qzeros  int32 [K/g][N/8]  nibble j of qzeros[G][n8] = STORED zero of column 8 n8 + j; the zero used is stored + 1, without
+ *                                  wrap-around (stored 15 means 16)
+ *        scales  fp16  [K/g][N]
+ *        W[n][k] = bf16_rne(float(scales[k/g][n]) * float(q[k][n] - zero[k/g][n]))
+ *      The fp32 product is exact (5 x 11 significant bits), so the bf16 rounding is the only one: every entry point below and the
+ *      host code (vlrlhf/gptq.py) produce the same bits.  group_size is K itself (the checkpoint's -1) or a multiple of 32 that
+ *      divides K; N % 8 == 0; g_idx must be k / g (checked at load time, never read on the device).
+ *
+ * vlr_gptq_dequant_bf16 - packed -> W bf16 [N][K] dense, K contiguous: what every GEMM here reads.  The engine dequantises ONE decoder
+ *   layer into a staging set right before that layer's forward, backward or checkpointed recompute.  qweight and W 16-byte aligned.
+ * vlr_gemv_w4 - vlr_gemv_bf16 (same modes, bias, RoPE and residual forms, M <= 16, fixed summation order, bit-reproducible) with W read
+ *   packed: an int32 of qweight is one lane's B fragment of v_mfma_f32_16x16x32_bf16, unpacked in registers by the rule above.  The
+ *   products are those of vlr_gemv_bf16 on the dequantised matrix; the order in which fp32 partial sums are added differs.  workspace:
+ *   vlr_gemv_w4_workspace_bytes(M, N, K) bytes.
+ * vlr_decoder_layer_decode_w4 - vlr_decoder_layer_decode with the four projections packed: `w` gives ln1, ln2 and bqkv (its matrix
+ *   pointers are not read), `q` the packed q|k|v, o, gate|up and down linears in the engine's fused row order.  ws->gemv_ws must hold
+ *   the largest vlr_gemv_w4_workspace_bytes of the four shapes. */
+typedef struct { const void* qweight; const void* qzeros; const void* scales; int group_size; } vlr_w4_linear;
+typedef struct { vlr_w4_linear qkv, o, gu, down; } vlr_layer_weights_w4;
+int vlr_gptq_dequant_bf16(const void* qweight, const void* qzeros, const void* scales, void* W, int K, int N, int group_size,
+                          vlr_stream_t stream);
+long vlr_gemv_w4_workspace_bytes(int M, int N, int K);
+int vlr_gemv_w4(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size, void* Y,
+                int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t, const float* sin_t,
+                int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace, vlr_stream_t stream);
+int vlr_decoder_layer_decode_w4(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q,
+                                const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache,
+                                const int* key_mask, int batch, int cap, int len, vlr_stream_t stream);
+
 /* ---- data-parallel gradient exchange on RCCL over xGMI (replaces accelerate MULTI_GPU / torch DDP's NCCL all-reduce:
  *      /root/reference accelerate_config/ddp.yaml:1-14; the reference itself never calls a collective).  One process per
  *      GPU, one communicator per process.  RCCL is dlopen'ed at run time (the copy already mapped into the process,

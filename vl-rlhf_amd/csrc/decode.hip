@@ -10,12 +10,17 @@
 //                        meet in LDS in a fixed order.  K slices (split-K, enough workgroups to cover the chip at N = 4096) write
 //                        fp32 partials; gemv_epilogue_kernel sums them in slice order and applies the epilogue: no atomics, the
 //                        result is bit-reproducible.
+//   gemv_w4_kernel       the same product with W read PACKED (GPTQ int4, gptq.h): a quarter of the weight bytes.  One int32 of qweight
+//                        is 8 consecutive k of one column - exactly one lane's B fragment of the MFMA - so a lane loads 16 bytes (4
+//                        columns x 8 k), unpacks them to bf16 in registers by the rule of gptq.h and feeds four MFMAs.  Same partials,
+//                        same epilogue kernel, same fixed summation order.
 //   kv_cache_write_kernel  post-RoPE K / V column blocks of the fused qkv rows -> cache columns slot0 .. slot0 + S - 1 (exact copy)
 //   attn_decode_kernel   flash-decoding: a workgroup owns (sequence, kv head, key chunk) and all heads / kv_heads query heads of the
 //                        group, so a grouped K/V chunk is read once; partials (max, sum, fp32 accumulator) go to a workspace and
 //                        attn_decode_combine_kernel folds them in chunk order.
 #include "../../include/vlr.h"
 #include "common.h"
+#include "gptq.h"
 
 constexpr int GV_COLS = 64;          // output columns per workgroup (4 MFMA n tiles of 16)
 constexpr int GV_CHUNK = 128;        // k per chunk: 4 MFMA k steps of 32, all loads issued before the MFMAs
@@ -138,8 +143,8 @@ __global__ __launch_bounds__(256) void gemv_epilogue_kernel(GemvEpi p, int units
 }
 
 // split count: enough workgroups for the chip, every split at least one chunk per wave where K allows
-static int gemv_splits(int N, int K) {
-    const int nb = (N + GV_COLS - 1) / GV_COLS, nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
+static int gemv_splits(int N, int K, int cols = GV_COLS) {
+    const int nb = (N + cols - 1) / cols, nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
     int s = (GV_TARGET_WGS + nb - 1) / nb;
     const int smax = (nchunks + 3) / 4;
     s = s < 1 ? 1 : (s > smax ? smax : s);
@@ -317,35 +322,173 @@ extern "C" long vlr_gemv_workspace_bytes(int M, int N, int K) {
     return (long)gemv_splits(N, K) * (M > 16 ? 16 : M) * N * 4;
 }
 
-extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
-                             int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
-                             int M, int N, int K, void* workspace, vlr_stream_t st) {
-    VLR_REQUIRE(mode >= VLR_GEMV_BF16 && mode <= VLR_GEMV_SWIGLU, "vlr_gemv_bf16: unknown mode %d", mode);
-    VLR_REQUIRE(X && W && Y && workspace, "vlr_gemv_bf16: null argument");
-    VLR_REQUIRE(M >= 1 && M <= 16, "vlr_gemv_bf16: M = %d rows, the skinny GEMM takes 1 <= M <= 16", M);
-    VLR_REQUIRE(K >= 8 && K % 8 == 0, "vlr_gemv_bf16: K = %d must be a positive multiple of 8", K);
-    VLR_REQUIRE(N >= 1 && ldx >= K && ldx % 8 == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)W & 15) == 0,
-                "vlr_gemv_bf16: N %d, ldx %d (>= K, multiple of 8) and 16-byte aligned X / W required", N, ldx);
+// the argument rules and the epilogue launch the bf16 and the packed skinny GEMM share
+static int gemv_check(const char* fn, int mode, const void* X, int ldx, const void* Y, int ldy, const void* bias, const void* residual,
+                      int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M,
+                      int N, int K, const void* workspace) {
+    VLR_REQUIRE(mode >= VLR_GEMV_BF16 && mode <= VLR_GEMV_SWIGLU, "%s: unknown mode %d", fn, mode);
+    VLR_REQUIRE(X && Y && workspace, "%s: null argument", fn);
+    VLR_REQUIRE(M >= 1 && M <= 16, "%s: M = %d rows, the skinny GEMM takes 1 <= M <= 16", fn, M);
+    VLR_REQUIRE(K >= 8 && K % 8 == 0, "%s: K = %d must be a positive multiple of 8", fn, K);
+    VLR_REQUIRE(N >= 1 && ldx >= K && ldx % 8 == 0 && ((uintptr_t)X & 15) == 0, "%s: N %d, ldx %d (>= K, multiple of 8) and 16-byte aligned X required",
+                fn, N, ldx);
     const int ncols = mode == VLR_GEMV_SWIGLU ? N / 2 : N;
-    VLR_REQUIRE(ldy >= ncols, "vlr_gemv_bf16: ldy %d < output columns %d", ldy, ncols);
-    VLR_REQUIRE(mode != VLR_GEMV_SWIGLU || N % 2 == 0, "vlr_gemv_bf16: gate|up needs an even N (got %d)", N);
-    VLR_REQUIRE(mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32RES || !residual, "vlr_gemv_bf16: mode %d takes no residual", mode);
-    VLR_REQUIRE(!residual || ldr >= N, "vlr_gemv_bf16: ldr %d < N %d", ldr, N);
-    VLR_REQUIRE(!bias || mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32 || mode == VLR_GEMV_QKV_ROPE, "vlr_gemv_bf16: mode %d takes no bias", mode);
+    VLR_REQUIRE(ldy >= ncols, "%s: ldy %d < output columns %d", fn, ldy, ncols);
+    VLR_REQUIRE(mode != VLR_GEMV_SWIGLU || N % 2 == 0, "%s: gate|up needs an even N (got %d)", fn, N);
+    VLR_REQUIRE(mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32RES || !residual, "%s: mode %d takes no residual", fn, mode);
+    VLR_REQUIRE(!residual || ldr >= N, "%s: ldr %d < N %d", fn, ldr, N);
+    VLR_REQUIRE(!bias || mode == VLR_GEMV_BF16 || mode == VLR_GEMV_F32 || mode == VLR_GEMV_QKV_ROPE, "%s: mode %d takes no bias", fn, mode);
     if (mode == VLR_GEMV_QKV_ROPE)
         VLR_REQUIRE(pos && cos_t && sin_t && head_dim >= 16 && head_dim % 16 == 0 && rope_cols % head_dim == 0 && rope_cols >= 0 &&
                         rope_cols <= N && max_pos > 0,
-                    "vlr_gemv_bf16: RoPE needs pos / cos / sin tables, head_dim %d (multiple of 16), rope_cols %d (multiple of head_dim, <= N %d)",
+                    "%s: RoPE needs pos / cos / sin tables, head_dim %d (multiple of 16), rope_cols %d (multiple of head_dim, <= N %d)", fn,
                     head_dim, rope_cols, N);
-    const int S = gemv_splits(N, K);
-    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
-    hipLaunchKernelGGL(gemv_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
-                       (float*)workspace, M, N, K, cps);
+    return VLR_OK;
+}
+
+static void gemv_epilogue(int mode, const void* workspace, int S, void* Y, int ldy, const void* bias, const void* residual, int ldr,
+                          const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N,
+                          hipStream_t st) {
     GemvEpi p{mode, (const float*)workspace, S, M, N, Y, ldy, (const bf16_t*)bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
               head_dim, max_pos};
     const int units = mode == VLR_GEMV_SWIGLU ? N / 2 : (mode == VLR_GEMV_QKV_ROPE ? N - rope_cols / 2 : N);
     hipLaunchKernelGGL(gemv_epilogue_kernel, dim3((M * units + 255) / 256), dim3(256), 0, st, p, units);
+}
+
+extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
+                             int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
+                             int M, int N, int K, void* workspace, vlr_stream_t st) {
+    const int rc = gemv_check("vlr_gemv_bf16", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos,
+                              M, N, K, workspace);
+    if (rc != VLR_OK) return rc;
+    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "vlr_gemv_bf16: W must be non-null and 16-byte aligned");
+    const int S = gemv_splits(N, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    hipLaunchKernelGGL(gemv_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
+                       (float*)workspace, M, N, K, cps);
+    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
     return vlr_check_launch("vlr_gemv_bf16");
+}
+
+// ---- the skinny GEMM over packed int4 weights.  A workgroup owns 128 output columns (two halves of 64) and one K slice.  Lane (r, g)
+// of a 32-k step holds the X fragment A[m = r][k = 8 g + j] and, per half h, ONE 16-byte load of qweight row k / 8: the words of columns
+// n0 + 64 h + 4 r + t, t = 0 .. 3.  MFMA n tile (h, t) is therefore the 16 columns {n0 + 64 h + 4 r + t}: the tiles interleave, every load
+// is 16 bytes and a wave reads 4 rows x 256 contiguous bytes per instruction.  PER_STEP: the group size is below the 128-k chunk, so
+// scales and zeros are reloaded at every 32-k step (a multiple of 32 divides the step into one group); otherwise once per chunk.
+constexpr int GW_COLS = 128;
+
+template <bool PER_STEP>
+__global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
+                                                      const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
+                                                      float* __restrict__ part, int M, int N, int K, int gsz, int cps) {
+    __shared__ float red[4][16][GW_COLS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * GW_COLS, split = blockIdx.y;
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
+    const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
+    const bool mok = r < M;
+    const bf16_t* xrow = X + (size_t)(mok ? r : 0) * ldx;
+    int nb[2];
+    bool nok[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int n = n0 + 64 * h + 4 * r;
+        nok[h] = n < N;                                    // N % 8 == 0: a lane's 4 columns are all in or all out
+        nb[h] = nok[h] ? n : 0;
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+    const int nz = N / 8, lastk = K - 8;
+    constexpr int NS = PER_STEP ? 4 : 1;
+    // every load below is unconditional at a clamped address (no branch, all of a chunk's loads in flight together): a k beyond K reads
+    // row K / 8 - 1 again and meets X = 0, a column beyond N reads column 0 and is never stored
+    for (int c = c0 + wv; c < c1; c += 4) {
+        f16x4 sc[NS][2];
+        uint32_t zw[NS][2];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int G = min(c * GV_CHUNK + s * 32, lastk) / gsz;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                sc[s][h] = __builtin_bit_cast(f16x4, *reinterpret_cast<const u32x2*>(SC + (size_t)G * N + nb[h]));
+                zw[s][h] = QZ[(size_t)G * nz + (nb[h] >> 3)];
+            }
+        }
+        bf16x8 a[4];
+        u32x4 qw[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = c * GV_CHUNK + u * 32 + g * 8;
+            const int kc = min(k, lastk);                  // K % 8 == 0: a lane's 8 k are all in or all out
+            const bf16x8 x = load8(xrow + kc);
+            a[u] = (mok && k < K) ? x : zero;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) qw[u][h] = *reinterpret_cast<const u32x4*>(QW + (size_t)(kc >> 3) * N + nb[h]);
+        }
+        __builtin_amdgcn_sched_barrier(0);                 // every load of the chunk is issued before the first unpack waits on one
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int s = PER_STEP ? u : 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const bf16x8 b = __builtin_bit_cast(bf16x8, w4_unpack(qw[u][h][t], (float)sc[s][h][t], w4_zero(zw[s][h], nb[h] + t)));
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b, acc[h][t], 0, 0, 0);
+                }
+        }
+    }
+    // D map: lane holds D[m = 4 g + i][tile column r] of n tile (h, t) = output column 64 h + 4 r + t
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) red[wv][4 * g + i][64 * h + 4 * r + t] = acc[h][t][i];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int idx = threadIdx.x + 256 * e, m = idx / GW_COLS, n = idx % GW_COLS;
+        if (m < M && n0 + n < N)
+            part[((size_t)split * M + m) * N + n0 + n] = ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n];
+    }
+}
+
+extern "C" long vlr_gemv_w4_workspace_bytes(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 8) return 0;
+    return (long)gemv_splits(N, K, GW_COLS) * (M > 16 ? 16 : M) * N * 4;
+}
+
+extern "C" int vlr_gemv_w4(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
+                           void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t,
+                           const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace,
+                           vlr_stream_t st) {
+    const int rc = gemv_check("vlr_gemv_w4", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M,
+                              N, K, workspace);
+    if (rc != VLR_OK) return rc;
+    VLR_REQUIRE(qweight && qzeros && scales, "vlr_gemv_w4: null packed weights");
+    VLR_REQUIRE(N % 8 == 0, "vlr_gemv_w4: N = %d must be a multiple of 8 (qzeros packs 8 columns per word)", N);
+    VLR_REQUIRE(group_size == K || (group_size >= 32 && group_size % 32 == 0 && K % group_size == 0),
+                "vlr_gemv_w4: group_size %d must be K (%d) or a multiple of 32 that divides it", group_size, K);
+    VLR_REQUIRE(((uintptr_t)qweight & 15) == 0 && ((uintptr_t)scales & 7) == 0 && ((uintptr_t)qzeros & 3) == 0,
+                "vlr_gemv_w4: qweight must be 16-byte, scales 8-byte, qzeros 4-byte aligned");
+    const int S = gemv_splits(N, K, GW_COLS);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    const dim3 grid((N + GW_COLS - 1) / GW_COLS, S);
+    // one group per 128-k chunk when the chunks do not straddle groups; else per 32-k step (a group of K itself never changes)
+    if (group_size == K || group_size % GV_CHUNK == 0)
+        hipLaunchKernelGGL(gemv_w4_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
+                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps);
+    else
+        hipLaunchKernelGGL(gemv_w4_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
+                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps);
+    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch("vlr_gemv_w4");
 }
 
 extern "C" int vlr_kv_cache_write(const void* k, const void* v, int ld, void* k_cache, void* v_cache, int batch, int S, int kv_heads,

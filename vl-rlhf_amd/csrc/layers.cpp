@@ -76,51 +76,75 @@ extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_w
 
 // ---- one decoder layer for one new token per sequence against its KV cache (vlr_decoder_layer_fwd_ex's arithmetic at M = batch rows,
 // the key side read from the cache).  The skinny GEMMs take at most 16 rows: larger batches run them in 16-row groups.
-static int gemv_rows(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, size_t ysz, const void* bias, const void* res,
-                     int ldr, size_t rsz, const int* pos, const vlr_llama_cfg* cfg, int rope_cols, int M, int N, int K, void* ws,
-                     hipStream_t st) {
+// W: the bf16 matrix, or (q != NULL) the packed int4 linear of a GPTQ base (vlr_gemv_w4)
+static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_w4_linear* q, void* Y, int ldy, size_t ysz, const void* bias,
+                     const void* res, int ldr, size_t rsz, const int* pos, const vlr_llama_cfg* cfg, int rope_cols, int M, int N, int K,
+                     void* ws, hipStream_t st) {
     for (int m0 = 0; m0 < M; m0 += 16) {
         const int mr = M - m0 < 16 ? M - m0 : 16;
-        CHECK(vlr_gemv_bf16(mode, (const char*)X + (size_t)m0 * ldx * 2, ldx, W, (char*)Y + (size_t)m0 * ldy * ysz, ldy, bias,
-                            res ? (const char*)res + (size_t)m0 * ldr * rsz : nullptr, ldr, pos ? pos + m0 : nullptr, cfg->rope_cos,
-                            cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, st));
+        const void* x = (const char*)X + (size_t)m0 * ldx * 2;
+        void* y = (char*)Y + (size_t)m0 * ldy * ysz;
+        const void* r = res ? (const char*)res + (size_t)m0 * ldr * rsz : nullptr;
+        const int* p = pos ? pos + m0 : nullptr;
+        if (q)
+            CHECK(vlr_gemv_w4(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
+                              cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, st));
+        else
+            CHECK(vlr_gemv_bf16(mode, x, ldx, W, y, ldy, bias, r, ldr, p, cfg->rope_cos, cfg->rope_sin, rope_cols, cfg->head_dim,
+                                cfg->max_pos, mr, N, K, ws, st));
     }
+    return VLR_OK;
+}
+// q4 == NULL: the four projections are the bf16 matrices of `w`; else the packed linears of q4 (w gives the norms and the bias)
+static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
+                        const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache, const int* key_mask,
+                        int batch, int cap, int len, hipStream_t st) {
+    VLR_REQUIRE(cfg && w && ws && x_inout && pos && k_cache && v_cache && key_mask, "%s: null argument", fn);
+    VLR_REQUIRE(ws->xn && ws->rstd && ws->qkv && ws->attn && ws->act && ws->gemv_ws && ws->attn_ws, "%s: null scratch buffer", fn);
+    VLR_REQUIRE(cfg->head_dim == 128, "%s: head_dim %d unsupported (the decode kernels take head_dim 128)", fn, cfg->head_dim);
+    VLR_REQUIRE(batch >= 1, "%s: batch %d", fn, batch);
+    VLR_REQUIRE(len >= 0 && len < cap, "%s: len %d must be below the cache capacity cap %d (the new token is written at column len)", fn,
+                len, cap);
+    const int H = cfg->hidden, I = cfg->inter;
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    VLR_REQUIRE(cfg->heads % kvh == 0, "%s: heads %d is not a multiple of kv_heads %d", fn, cfg->heads, kvh);
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    const int mb = batch < 16 ? batch : 16;
+    long (*bytes)(int, int, int) = q4 ? vlr_gemv_w4_workspace_bytes : vlr_gemv_workspace_bytes;
+    long need = bytes(mb, N, H);
+    const long shapes[3] = {bytes(mb, H, Nq), bytes(mb, 2 * I, H), bytes(mb, H, I)};
+    for (long b : shapes) need = b > need ? b : need;
+    VLR_REQUIRE(ws->gemv_ws_bytes >= need, "%s: gemv_ws has %ld bytes, %ld needed", fn, ws->gemv_ws_bytes, need);
+    const long need_a = vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
+    VLR_REQUIRE(ws->attn_ws_bytes >= need_a, "%s: attn_ws has %ld bytes, %ld needed", fn, ws->attn_ws_bytes, need_a);
+    const int rf = cfg->resid_f32;
+    const size_t xs = rf ? 4 : 2;
+    const int mode_res = rf ? VLR_GEMV_F32RES : VLR_GEMV_BF16;
+    CHECK(norm_fwd(rf, x_inout, w->ln1, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
+    CHECK(gemv_rows(VLR_GEMV_QKV_ROPE, ws->xn, H, w->wqkv, q4 ? &q4->qkv : nullptr, ws->qkv, N, 2, w->bqkv, nullptr, 0, 0, pos, cfg, Nq + Nkv,
+                    batch, N, H, ws->gemv_ws, st));
+    CHECK(vlr_kv_cache_write(off(ws->qkv, Nq), off(ws->qkv, (size_t)Nq + Nkv), N, k_cache, v_cache, batch, 1, kvh, cfg->head_dim, cap, len, st));
+    CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim, cap,
+                              len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    CHECK(gemv_rows(mode_res, ws->attn, Nq, w->wo, q4 ? &q4->o : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H,
+                    Nq, ws->gemv_ws, st));
+    CHECK(norm_fwd(rf, x_inout, w->ln2, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
+    CHECK(gemv_rows(VLR_GEMV_SWIGLU, ws->xn, H, w->wgu, q4 ? &q4->gu : nullptr, ws->act, I, 2, nullptr, nullptr, 0, 0, nullptr, cfg, 0, batch,
+                    2 * I, H, ws->gemv_ws, st));
+    CHECK(gemv_rows(mode_res, ws->act, I, w->wdown, q4 ? &q4->down : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch,
+                    H, I, ws->gemv_ws, st));
     return VLR_OK;
 }
 extern "C" int vlr_decoder_layer_decode(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_decode_ws* ws, void* x_inout,
                                         const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len,
                                         vlr_stream_t st) {
-    VLR_REQUIRE(cfg && w && ws && x_inout && pos && k_cache && v_cache && key_mask, "vlr_decoder_layer_decode: null argument");
-    VLR_REQUIRE(ws->xn && ws->rstd && ws->qkv && ws->attn && ws->act && ws->gemv_ws && ws->attn_ws, "vlr_decoder_layer_decode: null scratch buffer");
-    VLR_REQUIRE(cfg->head_dim == 128, "vlr_decoder_layer_decode: head_dim %d unsupported (the decode kernels take head_dim 128)", cfg->head_dim);
-    VLR_REQUIRE(batch >= 1, "vlr_decoder_layer_decode: batch %d", batch);
-    VLR_REQUIRE(len >= 0 && len < cap, "vlr_decoder_layer_decode: len %d must be below the cache capacity cap %d (the new token is written at column len)",
-                len, cap);
-    const int H = cfg->hidden, I = cfg->inter;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_decode: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    const int mb = batch < 16 ? batch : 16;
-    long need = vlr_gemv_workspace_bytes(mb, N, H);
-    const long shapes[3] = {vlr_gemv_workspace_bytes(mb, H, Nq), vlr_gemv_workspace_bytes(mb, 2 * I, H), vlr_gemv_workspace_bytes(mb, H, I)};
-    for (long b : shapes) need = b > need ? b : need;
-    VLR_REQUIRE(ws->gemv_ws_bytes >= need, "vlr_decoder_layer_decode: gemv_ws has %ld bytes, %ld needed", ws->gemv_ws_bytes, need);
-    const long need_a = vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
-    VLR_REQUIRE(ws->attn_ws_bytes >= need_a, "vlr_decoder_layer_decode: attn_ws has %ld bytes, %ld needed", ws->attn_ws_bytes, need_a);
-    const int rf = cfg->resid_f32;
-    const size_t xs = rf ? 4 : 2;
-    const int mode_res = rf ? VLR_GEMV_F32RES : VLR_GEMV_BF16;
-    CHECK(norm_fwd(rf, x_inout, w->ln1, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
-    CHECK(gemv_rows(VLR_GEMV_QKV_ROPE, ws->xn, H, w->wqkv, ws->qkv, N, 2, w->bqkv, nullptr, 0, 0, pos, cfg, Nq + Nkv, batch, N, H,
-                    ws->gemv_ws, st));
-    CHECK(vlr_kv_cache_write(off(ws->qkv, Nq), off(ws->qkv, (size_t)Nq + Nkv), N, k_cache, v_cache, batch, 1, kvh, cfg->head_dim, cap, len, st));
-    CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim, cap,
-                              len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(gemv_rows(mode_res, ws->attn, Nq, w->wo, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H, Nq, ws->gemv_ws, st));
-    CHECK(norm_fwd(rf, x_inout, w->ln2, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
-    CHECK(gemv_rows(VLR_GEMV_SWIGLU, ws->xn, H, w->wgu, ws->act, I, 2, nullptr, nullptr, 0, 0, nullptr, cfg, 0, batch, 2 * I, H, ws->gemv_ws, st));
-    CHECK(gemv_rows(mode_res, ws->act, I, w->wdown, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H, I, ws->gemv_ws, st));
-    return VLR_OK;
+    return layer_decode("vlr_decoder_layer_decode", cfg, w, nullptr, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st);
+}
+extern "C" int vlr_decoder_layer_decode_w4(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
+                                           const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache,
+                                           const int* key_mask, int batch, int cap, int len, vlr_stream_t st) {
+    VLR_REQUIRE(q4, "vlr_decoder_layer_decode_w4: null packed weights");
+    return layer_decode("vlr_decoder_layer_decode_w4", cfg, w, q4, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st);
 }
 
 double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip: rounds vlr_gemm_bf16_tn_pair saves over two launches on the compute CUs of the moment

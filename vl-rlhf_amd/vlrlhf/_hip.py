@@ -51,6 +51,14 @@ class DecodeWs(C.Structure):      # vlr_decode_ws: scratch of vlr_decoder_layer_
                 ("attn_ws_bytes", L)]
 
 
+class W4Linear(C.Structure):      # vlr_w4_linear: one GPTQ int4 linear, packed (include/vlr.h "GPTQ int4 base weights")
+    _fields_ = [("qweight", P), ("qzeros", P), ("scales", P), ("group_size", I)]
+
+
+class LayerWeightsW4(C.Structure):      # vlr_layer_weights_w4: the four fused projections of one decoder layer, packed
+    _fields_ = [(n, W4Linear) for n in ("qkv", "o", "gu", "down")]
+
+
 class VitCfg(C.Structure):
     _fields_ = [("hidden", I), ("mlp", I), ("heads", I), ("head_dim", I), ("ln_eps", F), ("act", I), ("head_dim_pad", I), ("attn_scale", F)]
 
@@ -159,6 +167,10 @@ _SIGS = {
     "vlr_kv_cache_write": [P, P, I, P, P, I, I, I, I, I, I, P],
     "vlr_attn_decode_gqa": [P, I, P, P, P, P, I, P, I, I, I, I, I, I, F, P],
     "vlr_decoder_layer_decode": [P, P, P, P, P, P, P, P, I, I, I, P],
+    # GPTQ int4 base weights (include/vlr.h "GPTQ int4 base weights")
+    "vlr_gptq_dequant_bf16": [P, P, P, P, I, I, I, P],
+    "vlr_gemv_w4": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P],
+    "vlr_decoder_layer_decode_w4": [P, P, P, P, P, P, P, P, P, I, I, I, P],
 }
 GEMV_BF16, GEMV_F32, GEMV_F32RES, GEMV_QKV_ROPE, GEMV_SWIGLU = range(5)      # vlr_gemv_bf16 modes
 _INT_HELPERS = {
@@ -187,7 +199,7 @@ _INT_HELPERS = {
 }
 
 
-_LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes"]      # (int, int, int) -> long
+_LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes"]      # (int, int, int) -> long
 
 
 class VlrError(RuntimeError):

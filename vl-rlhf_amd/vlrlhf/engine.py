@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _hip
+from . import _hip, gptq
 
 BF16 = torch.bfloat16
 
@@ -150,6 +150,9 @@ class ParamLayout:
             e.append(("proj.w1", (H, D), [("vision_proj.0.weight", 0, H)]))
             e.append(("proj.b2", (H,), [("vision_proj.2.bias", 0, H)]))
             e.append(("proj.b1", (H,), [("vision_proj.0.bias", 0, H)]))
+        # GPTQ base (cfg["gptq"], q_lora): the decoder projections live packed outside the flat buffer (engine.packed) and take no room
+        # in it - they keep their entry (names, shapes, fused row order) so that the packed loader stacks the parts the same way
+        self.packed = {name for name, _, _ in e if gptq.is_packed_entry(name)} if cfg.get("gptq") else set()
         self.offset = {}
         off = 0
         self.n_opt = None
@@ -159,7 +162,8 @@ class ParamLayout:
             if i == self.n_trainable_entries:
                 self.n_opt = off
             self.offset[name] = off
-            off += _align(int(math.prod(shape)))
+            if name not in self.packed:
+                off += _align(int(math.prod(shape)))
         self.numel = off
         if self.n_opt is None:
             self.n_opt = off           # elements [0, n_opt) are trainable (optimizer, gradient norm, DDP buckets); the rest is frozen
@@ -175,8 +179,14 @@ class ParamLayout:
 
     def hf_names(self):
         for name, shape, parts in self.entries:
+            if name in self.packed:
+                continue
             for hf, r0, rows in parts:
                 yield hf, name, r0, rows
+
+    def views(self, flat):
+        """named views of a flat buffer with this layout (packed entries have none)"""
+        return {n: flat[self.offset[n]: self.offset[n] + int(math.prod(s))].view(*s) for n, s in self.shape.items() if n not in self.packed}
 
 
 LORA_KEYS = ("a_qkv", "b_qkv", "a_o", "b_o", "a_gu", "b_gu", "a_down", "b_down")
@@ -255,8 +265,7 @@ class WeightSet:
         self.layout = layout
         self.flat = flat if flat is not None else torch.zeros(layout.numel, dtype=BF16, device=device)
         self.version = 0          # bumped by load_state_dict (caches derived from the weights key on it)
-        self.v = {n: self.flat[layout.offset[n]: layout.offset[n] + int(math.prod(s))].view(*s)
-                  for n, s in layout.shape.items()}
+        self.v = layout.views(self.flat)
 
     def clone(self):
         return WeightSet(self.layout, self.flat.device, self.flat.clone())
@@ -428,8 +437,10 @@ class LlavaHipEngine:
         self.vision: Optional[VisionWeights] = None
         self.policy = WeightSet(self.layout, self.dev)
         self.grads = torch.zeros(self.layout.numel, dtype=BF16, device=self.dev)
-        self.gv = {n: self.grads[self.layout.offset[n]: self.layout.offset[n] + int(math.prod(s))].view(*s)
-                   for n, s in self.layout.shape.items()}
+        self.gv = self.layout.views(self.grads)
+        # GPTQ int4 base (q_lora): {layout entry: gptq.PackedLinear on the device} for the decoder projections, filled by load_state_dict;
+        # the layer passes read a bf16 staging set that layer_weights() dequantises per call, decode_step reads the packed form itself
+        self.packed = {} if c.get("gptq") else None
         self.master = self.m = self.v = None     # fp32 optimizer state, allocated by init_optimizer()
         self.opt_step = 0
         self._weights_version = 0                # bumped whenever weights are (re)loaded: keys caches derived from them
@@ -464,6 +475,9 @@ class LlavaHipEngine:
         return VisionWeights(self.cfg, sd, self.dev, prefix=self.vision_prefix + "vision_model.")
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        if self.packed is not None:
+            host = gptq.load_packed_decoder(sd, self.layout, self.cfg["gptq"]["group_size"])
+            self.packed = {k: v.to(self.dev) for k, v in host.items()}
         self.policy.load_state_dict(sd)
         self.vision = self._load_vision(sd)
         # the frozen tower's ORIGINAL tensors (bf16, ~0.6 GB for CLIP-L): save_pretrained writes them back so that the
@@ -474,10 +488,32 @@ class LlavaHipEngine:
         if self.master is not None:
             self.init_optimizer()
 
-    def layer_weights(self, ws: WeightSet, l):
+    def layer_weights(self, ws: WeightSet, l, tag=None):
+        """the weights of decoder layer l for ONE layer call.  Packed base: the four projections are dequantised here, on the caller's
+        stream, into the bf16 staging set of pass `tag` (the reference pass runs on a side stream beside the policy pass: one set per
+        tag), so call this right before the layer's forward, backward or recompute and never keep the struct."""
         v = ws.v
-        return _hip.LayerWeights(*(v[f"l{l}.{k}"].data_ptr() for k in ("ln1", "wqkv", "wo", "ln2", "wgu", "wdown")),
-                                 v[f"l{l}.bqkv"].data_ptr() if f"l{l}.bqkv" in v else None)
+        bias = v[f"l{l}.bqkv"].data_ptr() if f"l{l}.bqkv" in v else None
+        if self.packed is None:
+            return _hip.LayerWeights(*(v[f"l{l}.{k}"].data_ptr() for k in ("ln1", "wqkv", "wo", "ln2", "wgu", "wdown")), bias)
+        if tag is None:
+            raise ValueError("layer_weights: a packed (GPTQ) base needs the pass tag that keys its staging set")
+        st = {}
+        for k in gptq.DECODER_LINEARS:
+            lin = self.packed[f"l{l}.{k}"]
+            st[k] = self._buf(("gptq_stage", tag, k), (lin.N, lin.K))
+            _hip.call("vlr_gptq_dequant_bf16", lin.qweight, lin.qzeros, lin.scales, st[k], lin.K, lin.N, lin.g)
+        return _hip.LayerWeights(v[f"l{l}.ln1"].data_ptr(), st["wqkv"].data_ptr(), st["wo"].data_ptr(), v[f"l{l}.ln2"].data_ptr(),
+                                 st["wgu"].data_ptr(), st["wdown"].data_ptr(), bias)
+
+    def layer_weights_w4(self, l):
+        """the packed projections of layer l as a vlr_layer_weights_w4 (decode_step)"""
+        lin = lambda k: (lambda p: _hip.W4Linear(p.qweight.data_ptr(), p.qzeros.data_ptr(), p.scales.data_ptr(), p.g))(self.packed[f"l{l}.{k}"])  # noqa: E731
+        return _hip.LayerWeightsW4(*(lin(k) for k in gptq.DECODER_LINEARS))
+
+    def packed_nbytes(self):
+        """bytes of the persistent packed tensors (qweight + qzeros + scales of every decoder projection)"""
+        return sum(p.nbytes() for p in self.packed.values())
 
     def layer_grads(self, l):
         return _hip.LayerGrads(*(self.gv[f"l{l}.{k}"].data_ptr() for k in ("ln1", "wqkv", "wo", "ln2", "wgu", "wdown")))
@@ -489,6 +525,8 @@ class LlavaHipEngine:
         trainable parameters (gradients, optimizer state, DDP bucket) are the adapters."""
         if r <= 0 or r % 8:
             raise ValueError(f"lora_r must be a positive multiple of 8 for the gfx950 GEMM tiles, got {r}")
+        if self.packed is not None and not self.packed:
+            raise ValueError("enable_lora on a packed (GPTQ) engine: load the checkpoint first")
         if self.Nq != self.H:
             raise NotImplementedError("LoRA needs heads * head_dim == hidden_size on the MI355X path")
         if not 0.0 <= dropout < 1.0:
@@ -572,6 +610,9 @@ class LlavaHipEngine:
 
     def merged_weights(self) -> WeightSet:
         """W + (alpha/r) B A for every adapted linear (peft merge_and_unload): a new WeightSet for export / inference."""
+        if self.packed is not None:
+            raise NotImplementedError("merged_weights: adapters cannot be folded into GPTQ int4 base weights (peft refuses merge_and_unload "
+                                      "on a GPTQ model too); save the adapter instead")
         ws = self.policy.clone()
         r, sc = self.lora["r"], self.lora["scale"]
         for l in range(self.L):
@@ -651,10 +692,10 @@ class LlavaHipEngine:
             lw, _ = self._lora_structs(l, train=True, M=M, acts=a)
             # (lora_dropout: the keep mask is applied to x while the adapter GEMMs stage it and regenerated in the backward - no dropped
             # copies of the seven inputs are kept any more: 0.9 GB per layer at the 7B shapes)
-            _hip.call("vlr_decoder_layer_fwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, a["struct"], u, None,
+            _hip.call("vlr_decoder_layer_fwd_lora", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), lw, a["struct"], u, None,
                       lora_seed + 8 * l, x, e["pos"], e["mask"], Bn, S)
         else:
-            _hip.call("vlr_decoder_layer_fwd_ex", self.llama_cfg, self.layer_weights(ws, l), a["struct"], x, e["pos"], e["mask"], Bn, S,
+            _hip.call("vlr_decoder_layer_fwd_ex", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], x, e["pos"], e["mask"], Bn, S,
                       int(keep))
 
     # ------------------------------------------------------------------------------------------------ vision
@@ -887,8 +928,10 @@ class LlavaHipEngine:
         if d is None:
             self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
             mb = min(B, 16)
-            gb = max(int(_hip.lib().vlr_gemv_workspace_bytes(mb, n, k)) for n, k in
-                     ((self.Nqkv, self.H), (self.H, self.Nq), (2 * self.I, self.H), (self.H, self.I), (self.V, self.H)))
+            shapes = ((self.Nqkv, self.H), (self.H, self.Nq), (2 * self.I, self.H), (self.H, self.I), (self.V, self.H))
+            gb = max(int(_hip.lib().vlr_gemv_workspace_bytes(mb, n, k)) for n, k in shapes)
+            if self.packed is not None:      # the packed skinny GEMM splits K differently
+                gb = max([gb] + [int(_hip.lib().vlr_gemv_w4_workspace_bytes(mb, n, k)) for n, k in shapes[:4]])
             ab = int(_hip.lib().vlr_attn_decode_workspace_bytes(B, self.nh, cap))
             d = dict(xn=torch.empty(B, self.H, dtype=BF16, device=self.dev), rstd=torch.empty(B, dtype=torch.float32, device=self.dev),
                      qkv=torch.empty(B, self.Nqkv, dtype=BF16, device=self.dev), attn=torch.empty(B, self.Nq, dtype=BF16, device=self.dev),
@@ -917,6 +960,13 @@ class LlavaHipEngine:
         else:
             _hip.call("vlr_gather_rows", ws.v["embed"], tok, x, B, H)
         for l in range(self.L):
+            if self.packed is not None:      # the projections stream their 4-bit form: nothing is dequantised to HBM
+                v = ws.v
+                w = _hip.LayerWeights(v[f"l{l}.ln1"].data_ptr(), None, None, v[f"l{l}.ln2"].data_ptr(), None, None,
+                                      v[f"l{l}.bqkv"].data_ptr() if f"l{l}.bqkv" in v else None)
+                _hip.call("vlr_decoder_layer_decode_w4", self.llama_cfg, w, self.layer_weights_w4(l), d["struct"], x, cache.pos, cache.k[l],
+                          cache.v[l], cache.key_mask, B, cache.cap, length)
+                continue
             _hip.call("vlr_decoder_layer_decode", self.llama_cfg, self.layer_weights(ws, l), d["struct"], x, cache.pos, cache.k[l],
                       cache.v[l], cache.key_mask, B, cache.cap, length)
         self._norm_fwd(x, ws.v["norm"], d["hidden"], d["rstd"], B)
@@ -1113,7 +1163,7 @@ class LlavaHipEngine:
         ws, Bn, S, M = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"]
         if self.lora is None:
             def full(l, a, x_in, cur, nxt):
-                _hip.call("vlr_decoder_layer_bwd", self.llama_cfg, self.layer_weights(ws, l), self.layer_grads(l), acc,
+                _hip.call("vlr_decoder_layer_bwd", self.llama_cfg, self.layer_weights(ws, l, ctx["tag"]), self.layer_grads(l), acc,
                           a["struct"], lws, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
                 if f"l{l}.bqkv" in self.gv:          # bias of the fused q|k|v projection: column sum of this layer's d qkv (post rope-transpose)
                     _hip.call("vlr_colsum", wsb["dqkv"], M, self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
@@ -1125,7 +1175,7 @@ class LlavaHipEngine:
 
         def lora(l, a, x_in, cur, nxt):
             lw, lg = self._lora_structs(l, train=True, M=M, acts=a)
-            _hip.call("vlr_decoder_layer_bwd_lora", self.llama_cfg, self.layer_weights(ws, l), lw, lg, acc, a["struct"],
+            _hip.call("vlr_decoder_layer_bwd_lora", self.llama_cfg, self.layer_weights(ws, l, ctx["tag"]), lw, lg, acc, a["struct"],
                       a.get("shared", a)["u"], lws, ws_v, scratch, ctx["lora_seed"] + 8 * l, x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
         return lora
 

@@ -66,6 +66,9 @@ class InternLMXC2ForRL(LlavaForRL):
         path = pretrained_model_name_or_path
         with open(os.path.join(path, "config.json")) as f:
             hf = json.load(f)
+        if hf.get("quantization_config"):
+            raise NotImplementedError("InternLM-XComposer2: GPTQ base weights are not supported (the PLoRA pairs ride the fused wqkv, whose "
+                                      "rows are re-ordered at load time; the packed loader takes no row permutation)")
         m = cls(_cfg_from_hf(hf))
         m.hf_config = hf
         sd = {}

@@ -12,7 +12,7 @@ from typing import Any, Callable, Dict, List, Literal, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from ... import _hip
+from ... import _hip, gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
 from ...base.trainer import VLDPOTrainer, VLSFTTrainer
@@ -264,10 +264,15 @@ class LlavaForRL(nn.Module):
         from safetensors.torch import load_file
         path = pretrained_model_name_or_path
         with open(os.path.join(path, "config.json")) as f:
-            cfg = _cfg_from_hf(json.load(f))
+            hf = json.load(f)
+        cfg = _cfg_from_hf(hf)
+        # a GPTQ checkpoint (quantization_config) loads PACKED: the decoder projections stay int4 on the device (vlrlhf/gptq.py);
+        # embedding, lm-head, norms, biases, vision tower and projector are bf16 as always
+        quant = gptq.parse_quantization_config(hf)
+        if quant:
+            cfg["gptq"] = quant
         m = cls(cfg)
-        with open(os.path.join(path, "config.json")) as f:
-            m.hf_config = json.load(f)
+        m.hf_config = hf
         sd = {}
         idx = os.path.join(path, "model.safetensors.index.json")
         files = sorted(set(json.load(open(idx))["weight_map"].values())) if os.path.exists(idx) else \
@@ -282,6 +287,9 @@ class LlavaForRL(nn.Module):
         model - language model, projector and the frozen vision tower's original tensors (reference: HF Trainer._save ->
         model.save_pretrained).  `state_dict`: alternative LLM/projector tensors (e.g. merge_and_unload())."""
         from safetensors.torch import save_file
+        if self.is_packed:
+            raise NotImplementedError("save_pretrained: a model over GPTQ int4 base weights is not written back as a whole (peft saves the "
+                                      "adapter of a GPTQ model, never the base); use save_adapter")
         os.makedirs(output_dir, exist_ok=True)
         hf = dict(getattr(self, "hf_config", None) or _hf_from_cfg(self.engine.cfg))
         hf.setdefault("architectures", ["LlavaForConditionalGeneration"])
@@ -361,6 +369,11 @@ class LlavaForRL(nn.Module):
         return self
 
     @property
+    def is_packed(self):
+        """the decoder projections are GPTQ int4, packed on the device (q_lora)"""
+        return self.engine.packed is not None
+
+    @property
     def is_peft_model(self):
         return self.engine.lora is not None and self._trainable
 
@@ -380,7 +393,7 @@ class LlavaForRL(nn.Module):
         return self.engine.lora_state_dict()
 
     def merge_and_unload(self):
-        """state dict of the base model with the adapters folded in (peft merge_and_unload)"""
+        """state dict of the base model with the adapters folded in (peft merge_and_unload); raises on a packed (GPTQ) base, as peft does"""
         return self.engine.merged_weights().state_dict()
 
     def train(self, mode: bool = True):
@@ -478,7 +491,10 @@ class LlavaForRL(nn.Module):
         self.eval()
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         lm_head = self.weights.v["lm_head"]
-        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
+        # (a packed GPTQ base cannot take the adapters folded in, which is how the cached path applies them: with ACTIVE adapters it
+        # generates through the re-forward loop, whose layer passes add them; adapters off, or none, decode from the packed weights)
+        unmergeable = self.is_packed and self.weights is self.engine.policy and self.engine.lora is not None and self.engine.lora_active
+        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128 and not unmergeable:
             try:
                 return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img)
             finally:

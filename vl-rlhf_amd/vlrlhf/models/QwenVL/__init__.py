@@ -14,6 +14,7 @@ from typing import Any, Dict, List, Optional, Union
 
 import torch
 
+from ... import gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
 from ...base.trainer import VLDPOTrainer, VLSFTTrainer
@@ -97,7 +98,11 @@ class QwenVLForRL(LlavaForRL):
         path = pretrained_model_name_or_path
         with open(os.path.join(path, "config.json")) as f:
             hf = json.load(f)
-        m = cls(_cfg_from_hf(hf))
+        cfg = _cfg_from_hf(hf)
+        quant = gptq.parse_quantization_config(hf)      # Qwen-VL-Chat-Int4: c_attn, attn.c_proj, w1, w2, mlp.c_proj stay packed (LlavaForRL.from_pretrained)
+        if quant:
+            cfg["gptq"] = quant
+        m = cls(cfg)
         m.hf_config = hf
         sd = {}
         idx = os.path.join(path, "model.safetensors.index.json")

@@ -4,6 +4,8 @@ import json
 import os
 from importlib import import_module
 
+from .. import gptq
+
 MODEL_NICKNAME_MAP = {
     "LlavaForConditionalGeneration": "Llava",
     "LlavaNextForConditionalGeneration": "LlavaNext",
@@ -68,9 +70,26 @@ class MyAutoSFTTrainer:
 def auto_load_rlmodel(script_args, training_args, lora_args):
     """-> (model, ref_model=None, lora_config); vision tower frozen (reference :554-555; freeze_vision_tower=False raises).  With use_lora the LoraConfig of
     reference :559-571 is returned as a plain dict (peft itself is not needed: the trainer hands it to
-    LlavaForRL.apply_lora); q_lora (GPTQ, reference :520-548) is not on the MI355X path."""
-    if getattr(training_args, "use_lora", False) and getattr(lora_args, "q_lora", False):
-        raise NotImplementedError("q_lora (GPTQ 4-bit base weights) is outside the MI355X DPO path")
+    LlavaForRL.apply_lora).
+
+    q_lora (reference :520-548 loads the checkpoint under GPTQConfig(bits=lora_args.bits, disable_exllama=True)): a checkpoint whose
+    config.json carries a GPTQ `quantization_config` loads with its decoder projections PACKED (int4 in HBM, vlrlhf/gptq.py), whether
+    or not the flag is given - the reference's from_pretrained does the same.  Packed weights cannot be trained, so such a model needs
+    use_lora (ValueError otherwise); q_lora on an unquantised checkpoint is a ValueError too: nothing here quantises, there is no
+    calibration set.  --bits other than 4, or a checkpoint of another width, raise NotImplementedError."""
+    use_lora = bool(getattr(training_args, "use_lora", False))
+    q_lora = use_lora and bool(getattr(lora_args, "q_lora", False))
+    with open(os.path.join(script_args.model_name_or_path, "config.json")) as f:
+        quant = gptq.parse_quantization_config(json.load(f))      # refuses what the kernels do not take, before anything is loaded
+    if q_lora:
+        if int(getattr(lora_args, "bits", 4)) != 4:
+            raise NotImplementedError(f"--q_lora with --bits {lora_args.bits}: the MI355X kernels unpack 4-bit GPTQ weights only")
+        if quant is None:
+            raise ValueError(f"--q_lora: {script_args.model_name_or_path} has no quantization_config; q_lora trains adapters over an "
+                             "already quantised GPTQ checkpoint (nothing is quantised at load time: there is no calibration set)")
+    if quant is not None and not use_lora:
+        raise ValueError(f"{script_args.model_name_or_path} is a GPTQ checkpoint: packed int4 weights cannot be trained, "
+                         "pass --use_lora True (with --q_lora True)")
     if not getattr(script_args, "freeze_vision_tower", True):
         # reference :554-555 would train the tower (dpo.py:54 --freeze_vision_tower False); the MI355X path has no ViT backward:
         # refuse instead of silently training with a frozen tower
