@@ -581,6 +581,48 @@ int vlr_decoder_layer_decode_w4(const vlr_llama_cfg* cfg, const vlr_layer_weight
                                 const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache,
                                 const int* key_mask, int batch, int cap, int len, vlr_stream_t stream);
 
+/* ---- decoding with LIVE LoRA adapters (peft lora.Linear un-merged during generate: no merged copy of the policy, and the only way to
+ *      decode from the cache over a packed GPTQ base, into which nothing can be merged).  Additive entry points: callers of the
+ *      adapter-free ones are untouched and vlr_abi_version() does not move.
+ *
+ * vlr_gemv_bf16_lora / vlr_gemv_w4_lora - vlr_gemv_bf16 / vlr_gemv_w4 (same modes, same argument rules) with the adapter term in the
+ *   fp32 accumulator BEFORE the epilogue (bias, RoPE rotation, silu(gate) * up, residual):
+ *     acc[m][n] = sum_k X[m][k] W[n][k] + sum_j u[m][t(n) r + j] B[n][j],   u = bf16(scale * X A^T)
+ *   A bf16 [targets * r][K] (the sub-targets' lora_A stacked), B bf16 [N][r] in the fused row order, t(n) the sub-target that owns row n:
+ *   `outs` (HOST array of `targets` row counts summing to N - q | k | v under grouped-query attention) or NULL for equal blocks of
+ *   N / targets rows.  r % 8 == 0 (any such rank), 1 <= targets <= 4; A, B, u 16-byte aligned.
+ *   Rounding of u: the fp32 sum x A^T times scale (= lora_alpha / r) in fp32, rounded once to bf16 - the rule of
+ *   vlr_decoder_layer_fwd_lora_ex, so a decode step stays within bf16 rounding of the prefill's adapters.
+ *   Two steps: the skinny GEMM kernel on A writes split-K partials of x A^T to `u` (vlr_gemv_lora_u_bytes(M, K, targets * r) bytes);
+ *   the main launch carries one more K slice whose workgroups fold them in order, round, and write u B^T as the LAST partial slice of
+ *   `workspace` (vlr_gemv_lora_workspace_bytes(M, N, K, targets * r) bytes: covers both the bf16 and the packed form).  No atomics,
+ *   fixed order, bit-reproducible; B = 0 adds 0.0f last and A = B = NULL runs the adapter-free call: both bit-identical to it.
+ * vlr_decoder_layer_decode_lora / _w4_lora - vlr_decoder_layer_decode / _w4 with the adapters of `lora` on q|k|v, o, gate|up and (when
+ *   a_down is set) down.  lora->dropout and mask_bits are ignored (decoding is inference).  vlr_decode_ws keeps its layout; gemv_ws must
+ *   hold the largest vlr_gemv_lora_workspace_bytes of the four shapes and `lws` gives the u scratch: the largest vlr_gemv_lora_u_bytes
+ *   (min(batch, 16), K, targets * r) of the four adapters (K = hidden, except inter for down). */
+typedef struct {
+    void* u;           /* >= u_bytes */
+    long u_bytes;
+} vlr_decode_lora_ws;
+long vlr_gemv_lora_workspace_bytes(int M, int N, int K, int r_total);
+long vlr_gemv_lora_u_bytes(int M, int K, int r_total);
+int vlr_gemv_bf16_lora(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual, int ldr,
+                       const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
+                       void* workspace, const void* A, const void* B, int r, int targets, const int* outs, float scale, void* u,
+                       vlr_stream_t stream);
+int vlr_gemv_w4_lora(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size, void* Y,
+                     int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t, const float* sin_t,
+                     int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace, const void* A, const void* B, int r,
+                     int targets, const int* outs, float scale, void* u, vlr_stream_t stream);
+int vlr_decoder_layer_decode_lora(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lora,
+                                  const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws, void* x_inout, const int* pos, void* k_cache,
+                                  void* v_cache, const int* key_mask, int batch, int cap, int len, vlr_stream_t stream);
+int vlr_decoder_layer_decode_w4_lora(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q,
+                                     const vlr_lora_weights* lora, const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws, void* x_inout,
+                                     const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len,
+                                     vlr_stream_t stream);
+
 /* ---- data-parallel gradient exchange on RCCL over xGMI (replaces accelerate MULTI_GPU / torch DDP's NCCL all-reduce:
  *      /root/reference accelerate_config/ddp.yaml:1-14; the reference itself never calls a collective).  One process per
  *      GPU, one communicator per process.  RCCL is dlopen'ed at run time (the copy already mapped into the process,

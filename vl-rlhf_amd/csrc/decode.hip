@@ -14,6 +14,8 @@
 //                        is 8 consecutive k of one column - exactly one lane's B fragment of the MFMA - so a lane loads 16 bytes (4
 //                        columns x 8 k), unpacks them to bf16 in registers by the rule of gptq.h and feeds four MFMAs.  Same partials,
 //                        same epilogue kernel, same fixed summation order.
+//   gemv_lora_kernel /   the two products with a live LoRA adapter: one more K slice whose workgroups write u B^T, u = bf16(scale * x A^T)
+//   gemv_w4_lora_kernel  (see "live LoRA adapters" below) - the adapter term is summed last, in front of the epilogue
 //   kv_cache_write_kernel  post-RoPE K / V column blocks of the fused qkv rows -> cache columns slot0 .. slot0 + S - 1 (exact copy)
 //   attn_decode_kernel   flash-decoding: a workgroup owns (sequence, kv head, key chunk) and all heads / kv_heads query heads of the
 //                        group, so a grouped K/V chunk is read once; partials (max, sum, fp32 accumulator) go to a workspace and
@@ -28,12 +30,11 @@ constexpr int GV_TARGET_WGS = 1024;  // split K until about this many workgroups
 
 __device__ __forceinline__ bf16x8 load8(const bf16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
 
-__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
-                                                   float* __restrict__ part, int M, int N, int K, int cps) {
-    __shared__ float red[4][16][GV_COLS];
+// one workgroup's (64 columns, K slice `split`) share of the product; red: the workgroup's LDS
+__device__ __forceinline__ void gemv_tile(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W, float* __restrict__ part,
+                                          int M, int N, int K, int cps, int n0, int split, float (*red)[16][GV_COLS]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * GV_COLS, split = blockIdx.y;
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
     const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
     const bool mok = r < M;
@@ -78,6 +79,88 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ X,
         if (m < M && n0 + n < N)
             part[((size_t)split * M + m) * N + n0 + n] = ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n];
     }
+}
+
+__global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
+                                                   float* __restrict__ part, int M, int N, int K, int cps) {
+    __shared__ float red[4][16][GV_COLS];
+    gemv_tile(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
+}
+
+// ---- live LoRA adapters (peft lora.Linear, un-merged): y = x W^T + u B^T with u = bf16(scale * x A^T), for `targets` sub-targets
+// fused along N (q|k|v: 3, gate|up: 2, o / down: 1).  A [targets * r][K], B [N][r] in the fused row order; row n of target t(n) multiplies
+// columns t(n) r .. t(n) r + r - 1 of u.
+//   Rounding rule of u (vlr_decoder_layer_fwd_lora_ex: lora_group_a -> lora_rows.hip / vlr_gemm_bf16_scaled): the fp32 sum of x A^T is
+//   multiplied by scale = lora_alpha / r in fp32 and rounded ONCE to bf16; the B half then reads bf16 u and accumulates in fp32.
+// Two steps, no atomics, every sum in a fixed order:
+//   1. gemv_kernel itself on A (N = targets * r): the fp32 split-K partials of x A^T go to the caller's `u` scratch
+//   2. the main launch gets ONE more K slice: workgroups with blockIdx.y == S fold those partials in slice order, scale, round to bf16
+//      (LDS) and write  sum_j u[m][t(n) r + j] B[n][j]  (j ascending, plain FMAs - 16 x r x 64 of them per workgroup, against the
+//      64 x K / S MACs of a base workgroup) as partial slice S.  gemv_epilogue_kernel sums slices 0 .. S in order, so the adapter term is
+//      in the fp32 accumulator BEFORE bias / RoPE / SwiGLU / residual, and is added last: B = 0 gives acc + 0.0f = acc, bit for bit.
+// The same slice rides the packed kernel (gemv_w4_lora_kernel, 128 columns per workgroup).
+struct GemvLora {
+    const float* upart;      // [Su][M][R] fp32 partials of x A^T
+    const bf16_t* B;         // [N][r]
+    int Su, r, R, targets;   // R = targets * r
+    int n1, n2, n3;          // target t owns rows [n_t, n_t+1): n0 = 0, n1, n2, n3 (= N from the last target on)
+    float scale;
+};
+__device__ __forceinline__ int lora_target(const GemvLora& lo, int n) { return (n >= lo.n1) + (n >= lo.n2) + (n >= lo.n3); }
+
+// COLS output columns from n0 on; ub: COLS * 256 bytes of LDS = 16 rows x COLS * 8 bf16 columns of u.  The column block spans the
+// targets t_lo .. t_hi (one, or two where a target edge falls inside it); the rank is walked in chunks of RC columns per spanned target
+// so that any r fits (one chunk whenever (t_hi - t_lo + 1) * r <= COLS * 8: every shipped configuration); j stays ascending across chunks
+template <int COLS>
+__device__ __forceinline__ void gemv_lora_slice(const GemvLora& lo, float* __restrict__ slice, int M, int N, int n0, bf16_t* ub) {
+    constexpr int RP = 16 * COLS / 256;                      // rows of m per thread
+    constexpr int CAP = COLS * 8;                            // bf16 columns of u per row the LDS holds
+    const int nlast = min(n0 + COLS, N) - 1;
+    const int t_lo = lora_target(lo, n0), nt = lora_target(lo, nlast) - t_lo + 1;      // nt <= 4 (host: targets <= 4)
+    const int RC = min(lo.r, CAP / nt / 8 * 8), Wd = nt * RC;
+    const int col = threadIdx.x % COLS, m0 = (threadIdx.x / COLS) * RP, n = n0 + col;
+    const bool nok = n < N;
+    const bf16_t* brow = lo.B + (size_t)(nok ? n : 0) * lo.r;
+    const bf16_t* urow = ub + (nok ? lora_target(lo, n) - t_lo : 0) * RC;
+    float acc[RP];
+#pragma unroll
+    for (int i = 0; i < RP; ++i) acc[i] = 0.f;
+    for (int jc = 0; jc < lo.r; jc += RC) {
+        const int rc = min(RC, lo.r - jc);                   // a multiple of 8
+        if (jc) __syncthreads();                             // the previous chunk has been read
+        for (int idx = threadIdx.x; idx < M * nt * rc; idx += 256) {
+            const int m = idx / (nt * rc), c = idx % (nt * rc), tt = c / rc, j = c % rc;
+            float s = 0.f;
+            for (int k = 0; k < lo.Su; ++k) s += lo.upart[((size_t)k * M + m) * lo.R + (t_lo + tt) * lo.r + jc + j];     // split order: fixed
+            ub[m * Wd + tt * RC + j] = f32_to_bf16(lo.scale * s);
+        }
+        __syncthreads();
+        if (!nok) continue;
+        for (int j0 = 0; j0 < rc; j0 += 8) {
+            float bf[8];
+            unpack8(*reinterpret_cast<const u32x4*>(brow + jc + j0), bf);
+#pragma unroll
+            for (int i = 0; i < RP; ++i) {
+                if (m0 + i >= M) continue;
+                float uf[8];
+                unpack8(*reinterpret_cast<const u32x4*>(urow + (m0 + i) * Wd + j0), uf);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[i] = __builtin_fmaf(uf[e], bf[e], acc[i]);
+            }
+        }
+    }
+    if (!nok) return;
+#pragma unroll
+    for (int i = 0; i < RP; ++i)
+        if (m0 + i < M) slice[(size_t)(m0 + i) * N + n] = acc[i];
+}
+
+// grid (column blocks, S + 1): slices 0 .. S - 1 are gemv_kernel's, slice S the adapter term
+__global__ __launch_bounds__(256) void gemv_lora_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
+                                                        float* __restrict__ part, int M, int N, int K, int cps, int S, GemvLora lo) {
+    __shared__ float red[4][16][GV_COLS];
+    if ((int)blockIdx.y == S) gemv_lora_slice<GV_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GV_COLS, (bf16_t*)&red[0][0][0]);
+    else gemv_tile(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
 }
 
 struct GemvEpi {
@@ -370,6 +453,61 @@ extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, vo
     return vlr_check_launch("vlr_gemv_bf16");
 }
 
+// ---- the adapter entry points.  Workspace: one more fp32 slice than the adapter-free call; u scratch: the split-K partials of x A^T
+extern "C" long vlr_gemv_lora_u_bytes(int M, int K, int r_total) { return vlr_gemv_workspace_bytes(M, r_total, K); }
+extern "C" long vlr_gemv_lora_workspace_bytes(int M, int N, int K, int r_total) {
+    if (M < 1 || N < 1 || K < 8 || r_total < 8 || r_total % 8) return 0;
+    const int s = gemv_splits(N, K), s4 = gemv_splits(N, K, 2 * GV_COLS);       // bf16 and packed (GW_COLS = 128) split counts
+    return (long)((s > s4 ? s : s4) + 1) * (M > 16 ? 16 : M) * N * 4;
+}
+// checks the adapter arguments, launches step 1 (x A^T partials -> u) and fills `lo`
+static int gemv_lora_prepare(const char* fn, const void* X, int ldx, const void* A, const void* B, int r, int targets, const int* outs,
+                             float scale, void* u, int M, int N, int K, hipStream_t st, GemvLora* lo) {
+    VLR_REQUIRE(A && B && u, "%s: null adapter argument (A, B and the u scratch are needed; pass A = B = NULL for no adapter)", fn);
+    VLR_REQUIRE(r >= 8 && r % 8 == 0, "%s: LoRA rank %d must be a positive multiple of 8", fn, r);
+    VLR_REQUIRE(targets >= 1 && targets <= 4, "%s: targets %d outside 1 .. 4", fn, targets);
+    VLR_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)u) & 15) == 0, "%s: A, B and u must be 16-byte aligned", fn);
+    int edge[5] = {0, N, N, N, N};
+    if (outs) {
+        for (int t = 0; t < targets; ++t) {
+            VLR_REQUIRE(outs[t] >= 1, "%s: target %d has %d rows", fn, t, outs[t]);
+            edge[t + 1] = edge[t] + outs[t];
+        }
+        VLR_REQUIRE(edge[targets] == N, "%s: the targets' rows sum to %d, N is %d", fn, edge[targets], N);
+    } else {
+        VLR_REQUIRE(N % targets == 0, "%s: N %d is not a multiple of targets %d (pass the row split)", fn, N, targets);
+        for (int t = 0; t < targets; ++t) edge[t + 1] = edge[t] + N / targets;
+    }
+    for (int t = targets; t < 4; ++t) edge[t + 1] = N;
+    const int R = targets * r, Su = gemv_splits(R, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + Su - 1) / Su;
+    hipLaunchKernelGGL(gemv_kernel, dim3((R + GV_COLS - 1) / GV_COLS, Su), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)A,
+                       (float*)u, M, R, K, cps);
+    *lo = GemvLora{(const float*)u, (const bf16_t*)B, Su, r, R, targets, edge[1], edge[2], edge[3], scale};      // edge[targets] = N: no row beyond it
+    return VLR_OK;
+}
+
+extern "C" int vlr_gemv_bf16_lora(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
+                                  int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
+                                  int M, int N, int K, void* workspace, const void* A, const void* B, int r, int targets, const int* outs,
+                                  float scale, void* u, vlr_stream_t st) {
+    if (!A && !B)      // not adapted: the adapter-free call itself
+        return vlr_gemv_bf16(mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K, workspace, st);
+    const int rc = gemv_check("vlr_gemv_bf16_lora", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim,
+                              max_pos, M, N, K, workspace);
+    if (rc != VLR_OK) return rc;
+    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "vlr_gemv_bf16_lora: W must be non-null and 16-byte aligned");
+    GemvLora lo;
+    const int rl = gemv_lora_prepare("vlr_gemv_bf16_lora", X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
+    if (rl != VLR_OK) return rl;
+    const int S = gemv_splits(N, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    hipLaunchKernelGGL(gemv_lora_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S + 1), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
+                       (float*)workspace, M, N, K, cps, S, lo);
+    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch("vlr_gemv_bf16_lora");
+}
+
 // ---- the skinny GEMM over packed int4 weights.  A workgroup owns 128 output columns (two halves of 64) and one K slice.  Lane (r, g)
 // of a 32-k step holds the X fragment A[m = r][k = 8 g + j] and, per half h, ONE 16-byte load of qweight row k / 8: the words of columns
 // n0 + 64 h + 4 r + t, t = 0 .. 3.  MFMA n tile (h, t) is therefore the 16 columns {n0 + 64 h + 4 r + t}: the tiles interleave, every load
@@ -378,13 +516,11 @@ extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, vo
 constexpr int GW_COLS = 128;
 
 template <bool PER_STEP>
-__global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
-                                                      const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
-                                                      float* __restrict__ part, int M, int N, int K, int gsz, int cps) {
-    __shared__ float red[4][16][GW_COLS];
+__device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
+                                             const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC, float* __restrict__ part,
+                                             int M, int N, int K, int gsz, int cps, int n0, int split, float (*red)[16][GW_COLS]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * GW_COLS, split = blockIdx.y;
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
     const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
     const bool mok = r < M;
@@ -459,6 +595,35 @@ __global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__
     }
 }
 
+template <bool PER_STEP>
+__global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
+                                                      const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
+                                                      float* __restrict__ part, int M, int N, int K, int gsz, int cps) {
+    __shared__ float red[4][16][GW_COLS];
+    gemv_w4_tile<PER_STEP>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
+}
+
+// the packed product with the adapter term as slice S (gemv_lora_kernel's scheme; the adapter operands are bf16 here too)
+template <bool PER_STEP>
+__global__ __launch_bounds__(256) void gemv_w4_lora_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
+                                                           const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
+                                                           float* __restrict__ part, int M, int N, int K, int gsz, int cps, int S,
+                                                           GemvLora lo) {
+    __shared__ float red[4][16][GW_COLS];
+    if ((int)blockIdx.y == S) gemv_lora_slice<GW_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GW_COLS, (bf16_t*)&red[0][0][0]);
+    else gemv_w4_tile<PER_STEP>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
+}
+
+static int gemv_w4_check(const char* fn, const void* qweight, const void* qzeros, const void* scales, int group_size, int N, int K) {
+    VLR_REQUIRE(qweight && qzeros && scales, "%s: null packed weights", fn);
+    VLR_REQUIRE(N % 8 == 0, "%s: N = %d must be a multiple of 8 (qzeros packs 8 columns per word)", fn, N);
+    VLR_REQUIRE(group_size == K || (group_size >= 32 && group_size % 32 == 0 && K % group_size == 0),
+                "%s: group_size %d must be K (%d) or a multiple of 32 that divides it", fn, group_size, K);
+    VLR_REQUIRE(((uintptr_t)qweight & 15) == 0 && ((uintptr_t)scales & 7) == 0 && ((uintptr_t)qzeros & 3) == 0,
+                "%s: qweight must be 16-byte, scales 8-byte, qzeros 4-byte aligned", fn);
+    return VLR_OK;
+}
+
 extern "C" long vlr_gemv_w4_workspace_bytes(int M, int N, int K) {
     if (M < 1 || N < 1 || K < 8) return 0;
     return (long)gemv_splits(N, K, GW_COLS) * (M > 16 ? 16 : M) * N * 4;
@@ -471,12 +636,8 @@ extern "C" int vlr_gemv_w4(int mode, const void* X, int ldx, const void* qweight
     const int rc = gemv_check("vlr_gemv_w4", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M,
                               N, K, workspace);
     if (rc != VLR_OK) return rc;
-    VLR_REQUIRE(qweight && qzeros && scales, "vlr_gemv_w4: null packed weights");
-    VLR_REQUIRE(N % 8 == 0, "vlr_gemv_w4: N = %d must be a multiple of 8 (qzeros packs 8 columns per word)", N);
-    VLR_REQUIRE(group_size == K || (group_size >= 32 && group_size % 32 == 0 && K % group_size == 0),
-                "vlr_gemv_w4: group_size %d must be K (%d) or a multiple of 32 that divides it", group_size, K);
-    VLR_REQUIRE(((uintptr_t)qweight & 15) == 0 && ((uintptr_t)scales & 7) == 0 && ((uintptr_t)qzeros & 3) == 0,
-                "vlr_gemv_w4: qweight must be 16-byte, scales 8-byte, qzeros 4-byte aligned");
+    const int rq = gemv_w4_check("vlr_gemv_w4", qweight, qzeros, scales, group_size, N, K);
+    if (rq != VLR_OK) return rq;
     const int S = gemv_splits(N, K, GW_COLS);
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
     const dim3 grid((N + GW_COLS - 1) / GW_COLS, S);
@@ -489,6 +650,34 @@ extern "C" int vlr_gemv_w4(int mode, const void* X, int ldx, const void* qweight
                            (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps);
     gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
     return vlr_check_launch("vlr_gemv_w4");
+}
+
+extern "C" int vlr_gemv_w4_lora(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
+                                void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t,
+                                const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace,
+                                const void* A, const void* B, int r, int targets, const int* outs, float scale, void* u, vlr_stream_t st) {
+    if (!A && !B)
+        return vlr_gemv_w4(mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
+                           head_dim, max_pos, M, N, K, workspace, st);
+    const int rc = gemv_check("vlr_gemv_w4_lora", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos,
+                              M, N, K, workspace);
+    if (rc != VLR_OK) return rc;
+    const int rq = gemv_w4_check("vlr_gemv_w4_lora", qweight, qzeros, scales, group_size, N, K);
+    if (rq != VLR_OK) return rq;
+    GemvLora lo;
+    const int rl = gemv_lora_prepare("vlr_gemv_w4_lora", X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
+    if (rl != VLR_OK) return rl;
+    const int S = gemv_splits(N, K, GW_COLS);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    const dim3 grid((N + GW_COLS - 1) / GW_COLS, S + 1);
+    if (group_size == K || group_size % GV_CHUNK == 0)
+        hipLaunchKernelGGL(gemv_w4_lora_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
+                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps, S, lo);
+    else
+        hipLaunchKernelGGL(gemv_w4_lora_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
+                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps, S, lo);
+    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch("vlr_gemv_w4_lora");
 }
 
 extern "C" int vlr_kv_cache_write(const void* k, const void* v, int ld, void* k_cache, void* v_cache, int batch, int S, int kv_heads,

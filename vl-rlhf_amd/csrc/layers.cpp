@@ -77,16 +77,25 @@ extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_w
 // ---- one decoder layer for one new token per sequence against its KV cache (vlr_decoder_layer_fwd_ex's arithmetic at M = batch rows,
 // the key side read from the cache).  The skinny GEMMs take at most 16 rows: larger batches run them in 16-row groups.
 // W: the bf16 matrix, or (q != NULL) the packed int4 linear of a GPTQ base (vlr_gemv_w4)
+// ad != NULL with ad->A: the live adapter of the projection (vlr_gemv_*_lora)
+struct GemvAdapter { const void* A; const void* B; int r, targets; const int* outs; float scale; void* u; };
 static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_w4_linear* q, void* Y, int ldy, size_t ysz, const void* bias,
                      const void* res, int ldr, size_t rsz, const int* pos, const vlr_llama_cfg* cfg, int rope_cols, int M, int N, int K,
-                     void* ws, hipStream_t st) {
+                     void* ws, hipStream_t st, const GemvAdapter* ad = nullptr) {
     for (int m0 = 0; m0 < M; m0 += 16) {
         const int mr = M - m0 < 16 ? M - m0 : 16;
         const void* x = (const char*)X + (size_t)m0 * ldx * 2;
         void* y = (char*)Y + (size_t)m0 * ldy * ysz;
         const void* r = res ? (const char*)res + (size_t)m0 * ldr * rsz : nullptr;
         const int* p = pos ? pos + m0 : nullptr;
-        if (q)
+        if (ad && ad->A && q)
+            CHECK(vlr_gemv_w4_lora(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
+                                   cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets,
+                                   ad->outs, ad->scale, ad->u, st));
+        else if (ad && ad->A)
+            CHECK(vlr_gemv_bf16_lora(mode, x, ldx, W, y, ldy, bias, r, ldr, p, cfg->rope_cos, cfg->rope_sin, rope_cols, cfg->head_dim,
+                                     cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets, ad->outs, ad->scale, ad->u, st));
+        else if (q)
             CHECK(vlr_gemv_w4(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
                               cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, st));
         else
@@ -96,9 +105,11 @@ static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_
     return VLR_OK;
 }
 // q4 == NULL: the four projections are the bf16 matrices of `w`; else the packed linears of q4 (w gives the norms and the bias)
+// lw != NULL: the live adapters of the layer (lws: their u scratch)
 static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
                         const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache, const int* key_mask,
-                        int batch, int cap, int len, hipStream_t st) {
+                        int batch, int cap, int len, hipStream_t st, const vlr_lora_weights* lw = nullptr,
+                        const vlr_decode_lora_ws* lws = nullptr) {
     VLR_REQUIRE(cfg && w && ws && x_inout && pos && k_cache && v_cache && key_mask, "%s: null argument", fn);
     VLR_REQUIRE(ws->xn && ws->rstd && ws->qkv && ws->attn && ws->act && ws->gemv_ws && ws->attn_ws, "%s: null scratch buffer", fn);
     VLR_REQUIRE(cfg->head_dim == 128, "%s: head_dim %d unsupported (the decode kernels take head_dim 128)", fn, cfg->head_dim);
@@ -114,6 +125,27 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     long need = bytes(mb, N, H);
     const long shapes[3] = {bytes(mb, H, Nq), bytes(mb, 2 * I, H), bytes(mb, H, I)};
     for (long b : shapes) need = b > need ? b : need;
+    GemvAdapter a_qkv{}, a_o{}, a_gu{}, a_down{};
+    const int o_qkv[3] = {Nq, Nkv, Nkv};
+    if (lw) {
+        VLR_REQUIRE(lws && lws->u, "%s: null adapter scratch", fn);
+        VLR_REQUIRE(lw->r > 0 && lw->r % 8 == 0, "%s: LoRA rank must be a positive multiple of 8, got %d", fn, lw->r);
+        VLR_REQUIRE(lw->a_qkv && lw->b_qkv && lw->a_o && lw->b_o && lw->a_gu && lw->b_gu && (!lw->a_down == !lw->b_down), "%s: null adapter pointer", fn);
+        VLR_REQUIRE(lw->qkv_targets == 0 || lw->qkv_targets == 1 || lw->qkv_targets == 3, "%s: qkv_targets must be 1 or 3, got %d", fn, lw->qkv_targets);
+        const int r = lw->r, nq = lw->qkv_targets == 1 ? 1 : 3;
+        a_qkv = GemvAdapter{lw->a_qkv, lw->b_qkv, r, nq, nq == 1 ? nullptr : o_qkv, lw->scale, lws->u};
+        a_o = GemvAdapter{lw->a_o, lw->b_o, r, 1, nullptr, lw->scale, lws->u};
+        a_gu = GemvAdapter{lw->a_gu, lw->b_gu, r, 2, nullptr, lw->scale, lws->u};
+        a_down = GemvAdapter{lw->a_down, lw->b_down, r, 1, nullptr, lw->scale, lws->u};
+        const long lshapes[4] = {vlr_gemv_lora_workspace_bytes(mb, N, H, nq * r), vlr_gemv_lora_workspace_bytes(mb, H, Nq, r),
+                                 vlr_gemv_lora_workspace_bytes(mb, 2 * I, H, 2 * r), lw->a_down ? vlr_gemv_lora_workspace_bytes(mb, H, I, r) : 0};
+        for (long b : lshapes) need = b > need ? b : need;
+        long need_u = 0;
+        const long ushapes[4] = {vlr_gemv_lora_u_bytes(mb, H, nq * r), vlr_gemv_lora_u_bytes(mb, Nq, r), vlr_gemv_lora_u_bytes(mb, H, 2 * r),
+                                 lw->a_down ? vlr_gemv_lora_u_bytes(mb, I, r) : 0};
+        for (long b : ushapes) need_u = b > need_u ? b : need_u;
+        VLR_REQUIRE(lws->u_bytes >= need_u, "%s: the adapter scratch u has %ld bytes, %ld needed", fn, lws->u_bytes, need_u);
+    }
     VLR_REQUIRE(ws->gemv_ws_bytes >= need, "%s: gemv_ws has %ld bytes, %ld needed", fn, ws->gemv_ws_bytes, need);
     const long need_a = vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
     VLR_REQUIRE(ws->attn_ws_bytes >= need_a, "%s: attn_ws has %ld bytes, %ld needed", fn, ws->attn_ws_bytes, need_a);
@@ -122,17 +154,17 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     const int mode_res = rf ? VLR_GEMV_F32RES : VLR_GEMV_BF16;
     CHECK(norm_fwd(rf, x_inout, w->ln1, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
     CHECK(gemv_rows(VLR_GEMV_QKV_ROPE, ws->xn, H, w->wqkv, q4 ? &q4->qkv : nullptr, ws->qkv, N, 2, w->bqkv, nullptr, 0, 0, pos, cfg, Nq + Nkv,
-                    batch, N, H, ws->gemv_ws, st));
+                    batch, N, H, ws->gemv_ws, st, &a_qkv));
     CHECK(vlr_kv_cache_write(off(ws->qkv, Nq), off(ws->qkv, (size_t)Nq + Nkv), N, k_cache, v_cache, batch, 1, kvh, cfg->head_dim, cap, len, st));
     CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim, cap,
                               len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
     CHECK(gemv_rows(mode_res, ws->attn, Nq, w->wo, q4 ? &q4->o : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H,
-                    Nq, ws->gemv_ws, st));
+                    Nq, ws->gemv_ws, st, &a_o));
     CHECK(norm_fwd(rf, x_inout, w->ln2, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
     CHECK(gemv_rows(VLR_GEMV_SWIGLU, ws->xn, H, w->wgu, q4 ? &q4->gu : nullptr, ws->act, I, 2, nullptr, nullptr, 0, 0, nullptr, cfg, 0, batch,
-                    2 * I, H, ws->gemv_ws, st));
+                    2 * I, H, ws->gemv_ws, st, &a_gu));
     CHECK(gemv_rows(mode_res, ws->act, I, w->wdown, q4 ? &q4->down : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch,
-                    H, I, ws->gemv_ws, st));
+                    H, I, ws->gemv_ws, st, &a_down));
     return VLR_OK;
 }
 extern "C" int vlr_decoder_layer_decode(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_decode_ws* ws, void* x_inout,
@@ -145,6 +177,22 @@ extern "C" int vlr_decoder_layer_decode_w4(const vlr_llama_cfg* cfg, const vlr_l
                                            const int* key_mask, int batch, int cap, int len, vlr_stream_t st) {
     VLR_REQUIRE(q4, "vlr_decoder_layer_decode_w4: null packed weights");
     return layer_decode("vlr_decoder_layer_decode_w4", cfg, w, q4, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st);
+}
+
+extern "C" int vlr_decoder_layer_decode_lora(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lora,
+                                             const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws, void* x_inout, const int* pos,
+                                             void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len, vlr_stream_t st) {
+    VLR_REQUIRE(lora, "vlr_decoder_layer_decode_lora: null adapters");
+    return layer_decode("vlr_decoder_layer_decode_lora", cfg, w, nullptr, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st, lora,
+                        lws);
+}
+extern "C" int vlr_decoder_layer_decode_w4_lora(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
+                                                const vlr_lora_weights* lora, const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws,
+                                                void* x_inout, const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch,
+                                                int cap, int len, vlr_stream_t st) {
+    VLR_REQUIRE(q4 && lora, "vlr_decoder_layer_decode_w4_lora: null packed weights or adapters");
+    return layer_decode("vlr_decoder_layer_decode_w4_lora", cfg, w, q4, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st, lora,
+                        lws);
 }
 
 double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip: rounds vlr_gemm_bf16_tn_pair saves over two launches on the compute CUs of the moment

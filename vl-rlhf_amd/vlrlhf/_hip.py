@@ -51,6 +51,10 @@ class DecodeWs(C.Structure):      # vlr_decode_ws: scratch of vlr_decoder_layer_
                 ("attn_ws_bytes", L)]
 
 
+class DecodeLoraWs(C.Structure):      # vlr_decode_lora_ws: the adapter scratch of vlr_decoder_layer_decode_lora / _w4_lora
+    _fields_ = [("u", P), ("u_bytes", L)]
+
+
 class W4Linear(C.Structure):      # vlr_w4_linear: one GPTQ int4 linear, packed (include/vlr.h "GPTQ int4 base weights")
     _fields_ = [("qweight", P), ("qzeros", P), ("scales", P), ("group_size", I)]
 
@@ -171,6 +175,12 @@ _SIGS = {
     "vlr_gptq_dequant_bf16": [P, P, P, P, I, I, I, P],
     "vlr_gemv_w4": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P],
     "vlr_decoder_layer_decode_w4": [P, P, P, P, P, P, P, P, P, I, I, I, P],
+    # decoding with live LoRA adapters (include/vlr.h "decoding with LIVE LoRA adapters"): the adapter-free signatures + A, B, r, targets,
+    # outs (host int array or None), scale, u scratch
+    "vlr_gemv_bf16_lora": [I, P, I, P, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, I, P, F, P, P],
+    "vlr_gemv_w4_lora": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, I, P, F, P, P],
+    "vlr_decoder_layer_decode_lora": [P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "vlr_decoder_layer_decode_w4_lora": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
 }
 GEMV_BF16, GEMV_F32, GEMV_F32RES, GEMV_QKV_ROPE, GEMV_SWIGLU = range(5)      # vlr_gemv_bf16 modes
 _INT_HELPERS = {
@@ -200,6 +210,7 @@ _INT_HELPERS = {
 
 
 _LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes"]      # (int, int, int) -> long
+_LONG_HELPERS_N = {"vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3}      # name -> number of int arguments, -> long
 
 
 class VlrError(RuntimeError):
@@ -230,6 +241,12 @@ def lib():
             fn = getattr(l, name)
             fn.restype = C.c_long
             fn.argtypes = [I, I, I]
+        for name, n in _LONG_HELPERS_N.items():
+            if os.environ.get("VLR_LIB") and not hasattr(l, name):
+                continue
+            fn = getattr(l, name)
+            fn.restype = C.c_long
+            fn.argtypes = [I] * n
         for name, sig in _SIGS.items():
             if os.environ.get("VLR_LIB") and not hasattr(l, name):      # A/B against an older build of the library: newer entries may be absent
                 continue
@@ -247,7 +264,7 @@ def lib():
 
 
 def exported_symbols():
-    return list(_SIGS) + list(_INT_HELPERS) + ["vlr_last_error", "vlr_comm_library", "vlr_lmhead_workspace_bytes", "vlr_lora_mask_bytes", "vlr_dropout_bits_kt_bytes"] + _LONG_HELPERS
+    return list(_SIGS) + list(_INT_HELPERS) + ["vlr_last_error", "vlr_comm_library", "vlr_lmhead_workspace_bytes", "vlr_lora_mask_bytes", "vlr_dropout_bits_kt_bytes"] + _LONG_HELPERS + list(_LONG_HELPERS_N)
 
 
 def ptr(t):

@@ -896,7 +896,8 @@ class VLDPOTrainer(VLTrainerLoop):
             eos = getattr(self.tokenizer, "eod_id", None)
         if eos is not None:
             kw["eos_token_id"] = eos
-        policy_output = model.generate(**kw)
+        # merge_lora=False: sampling inside training must not clone the policy - the adapters run live in the prefill and in every decode step
+        policy_output = model.generate(merge_lora=False, **kw)
         if "reference_output" in batch:
             reference_output = batch["reference_output"]
         elif self.ref_model is None:

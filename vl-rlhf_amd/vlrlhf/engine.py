@@ -923,7 +923,7 @@ class LlavaHipEngine:
                       0, self.hd, self.max_pos, mr, N, K, ws)
 
     def _decode_ws(self, B, cap):
-        key = ("decode_ws", B, cap)
+        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0)
         d = self._ws.get(key)
         if d is None:
             self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
@@ -932,6 +932,13 @@ class LlavaHipEngine:
             gb = max(int(_hip.lib().vlr_gemv_workspace_bytes(mb, n, k)) for n, k in shapes)
             if self.packed is not None:      # the packed skinny GEMM splits K differently
                 gb = max([gb] + [int(_hip.lib().vlr_gemv_w4_workspace_bytes(mb, n, k)) for n, k in shapes[:4]])
+            ub = 0
+            if self.lora is not None:        # live adapters (decode_step on the policy): one more partial slice, and the x A^T partials
+                r = self.lora["r"]
+                nq = self.lora_layout.qkv_targets
+                rt = (nq * r, r, 2 * r, r)
+                gb = max([gb] + [int(_hip.lib().vlr_gemv_lora_workspace_bytes(mb, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
+                ub = max(int(_hip.lib().vlr_gemv_lora_u_bytes(mb, k, t)) for (n, k), t in zip(shapes[:4], rt))
             ab = int(_hip.lib().vlr_attn_decode_workspace_bytes(B, self.nh, cap))
             d = dict(xn=torch.empty(B, self.H, dtype=BF16, device=self.dev), rstd=torch.empty(B, dtype=torch.float32, device=self.dev),
                      qkv=torch.empty(B, self.Nqkv, dtype=BF16, device=self.dev), attn=torch.empty(B, self.Nq, dtype=BF16, device=self.dev),
@@ -940,16 +947,26 @@ class LlavaHipEngine:
                      xe=torch.empty(B, self.H, dtype=BF16, device=self.dev), hidden=torch.empty(B, self.H, dtype=BF16, device=self.dev))
             d["struct"] = _hip.DecodeWs(d["xn"].data_ptr(), d["rstd"].data_ptr(), d["qkv"].data_ptr(), d["attn"].data_ptr(),
                                         d["act"].data_ptr(), d["gemv"].data_ptr(), gb, d["attn_ws"].data_ptr(), ab)
+            if ub:
+                d["u"] = torch.empty(ub, dtype=torch.uint8, device=self.dev)
+                d["lora_struct"] = _hip.DecodeLoraWs(d["u"].data_ptr(), ub)
             self._ws[key] = d
         return d
 
-    def decode_step(self, ws: WeightSet, tokens, cache: KVCache):
+    def decode_step(self, ws: WeightSet, tokens, cache: KVCache, lora=None):
         """One new token per sequence against the cache (transformers LlamaModel.forward with a DynamicCache, one query row):
         embedding row gather -> L x vlr_decoder_layer_decode -> final RMSNorm -> lm-head (skinny GEMM, fp32 out).
-        tokens [B] (ids appended at column cache.len) -> logits fp32 [B][V]; the cache advances by one column."""
+        tokens [B] (ids appended at column cache.len) -> logits fp32 [B][V]; the cache advances by one column.
+        lora (None: forward_hidden's rule - the adapters are live when `ws` is the policy and they are active; False: never): live
+        adapters run vlr_decoder_layer_decode_lora / _w4_lora, un-merged; everything else makes the adapter-free calls."""
         if not self.supports_kv_cache:
             raise ValueError(f"{type(self).__name__} has no KV-cache decoding")
         B, H = cache.B, self.H
+        use_lora = self.lora is not None and self.lora_active and ws is self.policy
+        if lora is not None:
+            if lora and not use_lora:
+                raise ValueError("decode_step(lora=True): live adapters need the policy weights and active adapters")
+            use_lora = bool(lora)
         d = self._decode_ws(B, cache.cap)
         tok = tokens.to(device=self.dev, dtype=torch.int32).contiguous()
         length = cache.open_column()
@@ -964,8 +981,16 @@ class LlavaHipEngine:
                 v = ws.v
                 w = _hip.LayerWeights(v[f"l{l}.ln1"].data_ptr(), None, None, v[f"l{l}.ln2"].data_ptr(), None, None,
                                       v[f"l{l}.bqkv"].data_ptr() if f"l{l}.bqkv" in v else None)
+                if use_lora:
+                    _hip.call("vlr_decoder_layer_decode_w4_lora", self.llama_cfg, w, self.layer_weights_w4(l), self._lora_structs(l, train=False)[0],
+                              d["struct"], d["lora_struct"], x, cache.pos, cache.k[l], cache.v[l], cache.key_mask, B, cache.cap, length)
+                    continue
                 _hip.call("vlr_decoder_layer_decode_w4", self.llama_cfg, w, self.layer_weights_w4(l), d["struct"], x, cache.pos, cache.k[l],
                           cache.v[l], cache.key_mask, B, cache.cap, length)
+                continue
+            if use_lora:
+                _hip.call("vlr_decoder_layer_decode_lora", self.llama_cfg, self.layer_weights(ws, l), self._lora_structs(l, train=False)[0],
+                          d["struct"], d["lora_struct"], x, cache.pos, cache.k[l], cache.v[l], cache.key_mask, B, cache.cap, length)
                 continue
             _hip.call("vlr_decoder_layer_decode", self.llama_cfg, self.layer_weights(ws, l), d["struct"], x, cache.pos, cache.k[l],
                       cache.v[l], cache.key_mask, B, cache.cap, length)

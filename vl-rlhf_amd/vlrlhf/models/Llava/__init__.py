@@ -453,7 +453,8 @@ class LlavaForRL(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_length=None, max_new_tokens=None, do_sample=False, temperature=1.0,
-                 top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True, **img):
+                 top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True,
+                 merge_lora=True, **img):
         """What the reference trainer's `get_batch_samples` calls (base/trainer.py:310-360: `model.generate(input_ids, attention_mask,
         max_length, do_sample=True, pad_token_id, **img_input_dict)`, transformers GenerationMixin defaults: temperature 1, top_k 50,
         top_p 1, use_cache True).  Prompts are LEFT-padded (trl's collator; the merge of the reference end-aligns such rows) and padded
@@ -463,8 +464,14 @@ class LlavaForRL(nn.Module):
         use_cache=True (engines with supports_kv_cache: LLaVA-1.5, LLaVA-Next): ONE prefill of the prompt fills a per-layer K / V cache
         (engine.forward_hidden(kv_cache=...)), then every new token is one decode step (engine.decode_step: skinny GEMMs and
         split-KV attention over the cache).  The first token's logits are those of the re-forward loop bit for bit (same prefill, same
-        lm-head call); later ones differ by the decode kernels' rounding.  With active LoRA adapters both run on the merged weights
-        (computed once per call).  use_cache=False, or an engine without the cache (Qwen-VL, InternLM-XComposer2): every new token
+        lm-head call); later ones differ by the decode kernels' rounding.  With active LoRA adapters:
+          merge_lora=True (default, bf16 base): prefill and decode run on the merged weights W + (alpha/r) B A, a second copy of the
+            policy computed once per call (peft merge_and_unload);
+          merge_lora=False: nothing is merged or cloned - the prefill applies the adapters as every training forward does and each decode
+            step runs them live (engine.decode_step -> vlr_decoder_layer_decode_lora), which is what sampling from the policy inside a
+            training loop needs; the first token's logits are then those of use_cache=False bit for bit;
+          a packed GPTQ base (q_lora) always takes the live path, whatever merge_lora says: nothing can be merged into packed weights.
+        With the adapters disabled (disable_adapter()) or absent the plain weights are decoded.  use_cache=False, or an engine without the cache (Qwen-VL, InternLM-XComposer2): every new token
         re-runs the forward of the whole sequence (the vision features of the batch are cached by the engine), the running batch
         left-padded to a multiple of 32 tokens so that the engine sees a new shape every 32 steps, not every step."""
         if generation_config is not None:
@@ -491,12 +498,10 @@ class LlavaForRL(nn.Module):
         self.eval()
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         lm_head = self.weights.v["lm_head"]
-        # (a packed GPTQ base cannot take the adapters folded in, which is how the cached path applies them: with ACTIVE adapters it
-        # generates through the re-forward loop, whose layer passes add them; adapters off, or none, decode from the packed weights)
-        unmergeable = self.is_packed and self.weights is self.engine.policy and self.engine.lora is not None and self.engine.lora_active
-        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128 and not unmergeable:
+        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
             try:
-                return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img)
+                return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img,
+                                             self.cached_lora_route(merge_lora))
             finally:
                 self.train(was_training)
         try:
@@ -536,9 +541,18 @@ class LlavaForRL(nn.Module):
         _hip.call("vlr_gemm_bf16", 0, h_last, lm_head, logits, None, None, rows, self.engine.V, H, H, H, self.engine.V, 0, 0, 0, 1)
         return logits[:B]
 
-    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img):
+    def cached_lora_route(self, merge_lora=True):
+        """how generate's KV-cache path treats the adapters: "plain" (none, disabled, or a weight set other than the policy), "merged"
+        (folded into a clone of the policy once per call) or "live" (un-merged in the prefill and in every decode step: merge_lora=False,
+        and always over a packed GPTQ base, into which nothing can be merged)"""
+        eng = self.engine
+        if not (self.weights is eng.policy and eng.lora is not None and eng.lora_active):
+            return "plain"
+        return "merged" if (merge_lora and not self.is_packed) else "live"
+
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route):
         """generate's KV-cache path: the prefill is the first iteration of the re-forward loop (same padded input, same lm-head
-        call) with the K / V rows kept; each further token is one engine.decode_step."""
+        call) with the K / V rows kept; each further token is one engine.decode_step.  route: cached_lora_route()."""
         eng, dev = self.engine, self.engine.dev
         B, T = ids.shape
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
@@ -547,7 +561,7 @@ class LlavaForRL(nn.Module):
         ws = self.weights
         if ws is eng.policy:
             eng.wait_optimizer()
-            if eng.lora is not None and eng.lora_active:
+            if route == "merged":
                 ws = eng.merged_weights()          # peft merge: the adapters folded in once for the whole call
         Tp = (T + 31) // 32 * 32
         if Tp != T:                   # left padding: masked out, and the merged rows stay end-aligned
