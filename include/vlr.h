@@ -623,6 +623,40 @@ int vlr_decoder_layer_decode_w4_lora(const vlr_llama_cfg* cfg, const vlr_layer_w
                                      const int* pos, void* k_cache, void* v_cache, const int* key_mask, int batch, int cap, int len,
                                      vlr_stream_t stream);
 
+/* ---- decoding several samples of one prompt over a SHARED prompt cache (generate(num_return_sequences = n)).  Additive entry points:
+ *      vlr_abi_version() does not move.
+ *
+ * The key side of sample p * fanout + j is two segments:
+ *   prompt  k_prompt, v_prompt [prompts][kv_heads][prompt_cap][128] bf16 and prompt_mask [prompts][prompt_cap] int32 (0 = padded key;
+ *           prompts are left-padded) - what the prefill writes through vlr_kv_cache_write; the first prompt_len columns are filled.
+ *           Shared by the `fanout` samples of prompt p.
+ *   tail    k_tail, v_tail [prompts * fanout][kv_heads][tail_cap][128]: the sample's own new tokens.  Columns 0 .. tail_len - 1 are all
+ *           attended (no mask); tail_len counts the new token's own column.
+ * Columns >= prompt_len of the prompt segment and >= tail_len of a tail are never read.
+ *
+ * vlr_attn_decode_shared - vlr_attn_decode_gqa for prompts * fanout query rows (q, o as there).  A workgroup owns (prompt, kv head, prompt
+ *   key chunk) and all fanout * heads / kv_heads query rows of that prompt, in tiles of 16 (any fanout >= 1): a prompt K/V chunk is read
+ *   from HBM once per call, not once per sample.  Both products run on the matrix pipe; the probabilities are rounded to bf16 for P.V
+ *   (csrc/decode.hip).  The tails run the kernel of vlr_attn_decode_gqa; one kernel folds prompt chunks, then tail chunks, in order: no
+ *   atomics, two calls give the same bits.  heads / kv_heads in {1, 2, 4, 8}; head_dim 128; 1 <= prompt_len <= prompt_cap;
+ *   1 <= tail_len <= tail_cap; fanout >= 1.  workspace: vlr_attn_decode_shared_workspace_bytes(...) bytes.
+ * vlr_decoder_layer_decode_shared - vlr_decoder_layer_decode (q4 == NULL, lora == NULL), _w4 (q4), _lora (lora, lws) or _w4_lora (both)
+ *   at batch = prompts * fanout rows over the shared cache: the new token's K/V column is written to the tails at column tail_len - 1,
+ *   attention is vlr_attn_decode_shared, every GEMM call is that of the per-sequence entry points.  ws->attn_ws must hold
+ *   vlr_attn_decode_shared_workspace_bytes(prompts, fanout, heads, prompt_cap, tail_cap) bytes. */
+typedef struct {
+    void* k_prompt; void* v_prompt; const int* prompt_mask;   /* this layer's */
+    int prompts, prompt_cap, prompt_len;
+    void* k_tail; void* v_tail;
+    int fanout, tail_cap, tail_len;                           /* columns attended, the new one included */
+} vlr_kv_shared;
+long vlr_attn_decode_shared_workspace_bytes(int prompts, int fanout, int heads, int prompt_cap, int tail_cap);
+int vlr_attn_decode_shared(const void* q, int ldq, const vlr_kv_shared* kv, void* o, int ldo, void* workspace, int heads, int kv_heads,
+                           int head_dim, float scale, vlr_stream_t stream);
+int vlr_decoder_layer_decode_shared(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
+                                    const vlr_lora_weights* lora, const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws, void* x_inout,
+                                    const int* pos, const vlr_kv_shared* kv, vlr_stream_t stream);
+
 /* ---- data-parallel gradient exchange on RCCL over xGMI (replaces accelerate MULTI_GPU / torch DDP's NCCL all-reduce:
  *      /root/reference accelerate_config/ddp.yaml:1-14; the reference itself never calls a collective).  One process per
  *      GPU, one communicator per process.  RCCL is dlopen'ed at run time (the copy already mapped into the process,

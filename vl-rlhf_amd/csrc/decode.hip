@@ -20,6 +20,11 @@
 //   attn_decode_kernel   flash-decoding: a workgroup owns (sequence, kv head, key chunk) and all heads / kv_heads query heads of the
 //                        group, so a grouped K/V chunk is read once; partials (max, sum, fp32 accumulator) go to a workspace and
 //                        attn_decode_combine_kernel folds them in chunk order.
+//   attn_shared_prompt_kernel  the same for the `fanout` samples of one prompt (num_return_sequences): a workgroup owns (prompt, kv head,
+//                        prompt key chunk) and ALL fanout * heads / kv_heads query rows of that prompt, so a prompt K/V chunk is read
+//                        from HBM once per step and not once per sample.  Both products run on v_mfma_f32_16x16x32_bf16 (see the
+//                        kernel); the samples' own tails go through attn_decode_kernel and attn_shared_combine_kernel folds prompt
+//                        chunks, then tail chunks, in order.
 #include "../../include/vlr.h"
 #include "common.h"
 #include "gptq.h"
@@ -266,6 +271,7 @@ static int attn_decode_chunk(int B, int kvh, int len) {
 }
 
 // grid (chunk, kv head, sequence), 256 threads.  Scores in the log2 domain (scale * log2 e folded into q . k).
+// key_mask == nullptr (the tail segment of vlr_attn_decode_shared): all `len` columns are attended.
 template <int G>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ kc,
                                                           const bf16_t* __restrict__ vc, const int* __restrict__ key_mask,
@@ -278,7 +284,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     const int j0 = c * C;
     const bf16_t* kbase = kc + ((size_t)b * kvh + hk) * cap * AD_HD;
     const bf16_t* vbase = vc + ((size_t)b * kvh + hk) * cap * AD_HD;
-    const int* km = key_mask + (size_t)b * cap;
+    const int* km = key_mask ? key_mask + (size_t)b * cap : nullptr;      // null: every column below len is attended
     float qf[G][8];
 #pragma unroll
     for (int g = 0; g < G; ++g) unpack8(*reinterpret_cast<const u32x4*>(q + (size_t)b * ldq + (size_t)(hk * G + g) * AD_HD + d0), qf[g]);
@@ -295,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
             float kf[8];
             unpack8(kr[u], kf);
             const int i = i0 + 16 * u, j = j0 + i;
-            const bool valid = j < len && km[j] != 0;
+            const bool valid = j < len && (!km || km[j] != 0);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 float s = 0.f;
@@ -726,4 +732,215 @@ extern "C" int vlr_attn_decode_gqa(const void* q, int ldq, const void* k_cache, 
     hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(heads, batch), dim3(AD_HD), 0, st, (const float*)workspace, (bf16_t*)o, ldo, heads,
                        kv_heads, nchunks);
     return vlr_check_launch("vlr_attn_decode_gqa");
+}
+
+// ---- decode attention over a SHARED prompt (generate(num_return_sequences = n): the n samples of a prompt attend the same prompt keys).
+// Key side of sample p * fanout + j: the prompt segment of prompt p (k, v [prompts][kv_heads][prompt_cap][128], left-padded, masked by
+// prompt_mask) followed by the sample's own tail (k, v [prompts * fanout][kv_heads][tail_cap][128], every column below tail_len attended).
+//
+// attn_shared_prompt_kernel<KT>: grid (chunk, kv head, prompt), 256 threads, chunk C = 64 KT keys.  The workgroup owns all R = fanout * G
+// query rows (row j * G + g = sample j, head g of the group) and walks them in tiles of 16; rows beyond R are zero queries and are never
+// written.  What is read from HBM is read once per chunk, whatever R is:
+//   K   wave w holds the B fragments of its KT key tiles (16 keys x 128 dims: four 16-byte loads per lane, as gemv_tile's W operand) in
+//       registers across all row tiles.  Q . K^T: v_mfma_f32_16x16x32_bf16, A = the tile's 16 query rows (16-byte loads of q), fp32
+//       scores in the log2 domain, masked keys (and keys >= prompt_len, which are never loaded) set to -inf, as attn_decode_kernel has it.
+//   V   P . V contracts over the key, and V is [key][dim]: the MFMA's B fragment wants 8 consecutive KEYS of one dim per lane.  The chunk
+//       is therefore transposed ONCE through LDS (vt [dim][key]: 16-byte global loads of two key rows, 4-byte LDS stores of one dim's
+//       key pair), and each wave lifts the B fragments of its 32 output dims - all C keys - into registers, where they stay across the
+//       row tiles.  Masked keys and keys >= prompt_len are stored as zeros and never loaded, so their content cannot reach the output.
+//   P   is ROUNDED TO bf16 for the second MFMA (the one source of error attn_decode_kernel does not have: 2^-9 relative per probability);
+//       the chunk's `sum` is taken over the rounded values, so the weights the output is normalised by are the weights that were applied.
+// Every wave owns 32 output dims over all keys of the chunk: no cross-wave reduction of the accumulator.  A chunk whose keys are all
+// masked writes (max = -inf, sum = 0) and returns.  Partials: the record format of attn_decode_kernel, [prompt][kv head][chunk][R].
+template <int KT>
+__global__ __launch_bounds__(256) void attn_shared_prompt_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ kp,
+                                                                 const bf16_t* __restrict__ vp, const int* __restrict__ mask,
+                                                                 float* __restrict__ ws, int kvh, int G, int fanout, int cap, int len,
+                                                                 int nchunks, float sl2) {
+    constexpr int C = 64 * KT, VS = C + 8, SS = C + 4;       // VS: bf16 row stride of vt / pb (rows stay 16-byte aligned), SS: of sc
+    __shared__ __attribute__((aligned(16))) bf16_t vt[AD_HD * VS];
+    __shared__ __attribute__((aligned(16))) bf16_t pb[16 * VS];
+    __shared__ float sc[16][SS];
+    const int c = blockIdx.x, hk = blockIdx.y, p = blockIdx.z;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+    const int j0 = c * C, R = fanout * G;
+    const bf16_t* kbase = kp + ((size_t)p * kvh + hk) * cap * AD_HD;
+    const bf16_t* vbase = vp + ((size_t)p * kvh + hk) * cap * AD_HD;
+    const int* km = mask + (size_t)p * cap;
+    float* rec = ws + (((size_t)p * kvh + hk) * nchunks + c) * R * AD_REC;
+    bool mine = false;
+    for (int i = threadIdx.x; i < C; i += 256) mine |= j0 + i < len && km[j0 + i] != 0;
+    if (!__syncthreads_or(mine)) {
+        for (int rr = threadIdx.x; rr < R; rr += 256) { rec[(size_t)rr * AD_REC] = -INFINITY; rec[(size_t)rr * AD_REC + 1] = 0.f; }
+        return;
+    }
+    // ---- V chunk -> vt [dim][key].  64 consecutive work items = 16 key pairs x 4 dim groups of 8: the 4-byte stores of a wave then
+    // fall on 32 banks, two lanes each
+    uint32_t* vt32 = reinterpret_cast<uint32_t*>(vt);
+    for (int idx = threadIdx.x; idx < C * 8; idx += 256) {
+        const int blk = idx >> 6, l = idx & 63;
+        const int kpi = (blk >> 2) * 16 + (l >> 2), dg = (blk & 3) * 4 + (l & 3);
+        const int ja = j0 + 2 * kpi, jb = ja + 1;
+        const bool oka = ja < len && km[ja] != 0, okb = jb < len && km[jb] != 0;
+        const u32x4 z{0u, 0u, 0u, 0u};
+        const u32x4 a = oka ? *reinterpret_cast<const u32x4*>(vbase + (size_t)ja * AD_HD + dg * 8) : z;
+        const u32x4 b = okb ? *reinterpret_cast<const u32x4*>(vbase + (size_t)jb * AD_HD + dg * 8) : z;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            vt32[(dg * 8 + 2 * e) * (VS / 2) + kpi] = (a[e] & 0xffffu) | (b[e] << 16);
+            vt32[(dg * 8 + 2 * e + 1) * (VS / 2) + kpi] = (a[e] >> 16) | (b[e] & 0xffff0000u);
+        }
+    }
+    // ---- K fragments of this wave's key tiles: lane (r, g) holds B[k = 8 g + j][n = r] = K[key 16 tile + r][dim 32 u + 8 g + j]
+    const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+    bf16x8 kf[KT][4];
+    bool kvalid[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        const int j = j0 + (wv * KT + t) * 16 + r;
+        const bool inr = j < len;
+        kvalid[t] = inr && km[j] != 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) kf[t][u] = inr ? load8(kbase + (size_t)j * AD_HD + u * 32 + g * 8) : zero;
+    }
+    __syncthreads();
+    // V fragments: B[k = 8 g + j][n = r] = V[key 32 ks + 8 g + j][dim 32 wv + 16 nt + r]
+    bf16x8 vf[C / 32][2];
+#pragma unroll
+    for (int ks = 0; ks < C / 32; ++ks)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) vf[ks][nt] = load8(vt + (32 * wv + 16 * nt + r) * VS + ks * 32 + 8 * g);
+    for (int t0 = 0; t0 < R; t0 += 16) {
+        // ---- scores of 16 query rows: A[m = r][k = 8 g + j] = q[row t0 + r][dim 32 u + 8 g + j]; D[m = 4 g + i][n = r]
+        const int rr = t0 + r;
+        const bool qok = rr < R;
+        const bf16_t* qrow = q + ((size_t)p * fanout + (qok ? rr / G : 0)) * ldq + (size_t)(hk * G + (qok ? rr % G : 0)) * AD_HD;
+        bf16x8 qa[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) qa[u] = qok ? load8(qrow + u * 32 + g * 8) : zero;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            f32x4 s{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[u], kf[t][u], s, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sc[4 * g + i][(wv * KT + t) * 16 + r] = kvalid[t] ? s[i] * sl2 : -INFINITY;
+        }
+        __syncthreads();      // also: every wave has left the previous tile's P . V, pb may be rewritten
+        // ---- chunk softmax statistics: wave wv owns rows 4 wv .. 4 wv + 3; P -> bf16
+        for (int rw = 4 * wv; rw < 4 * wv + 4; ++rw) {
+            float x[KT], mx = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < KT; ++e) { x[e] = sc[rw][lane + 64 * e]; mx = fmaxf(mx, x[e]); }
+            mx = wave_max(mx);
+            float l = 0.f;
+#pragma unroll
+            for (int e = 0; e < KT; ++e) {
+                const bf16_t pr = f32_to_bf16(mx == -INFINITY ? 0.f : exp2f(x[e] - mx));
+                pb[rw * VS + lane + 64 * e] = pr;
+                l += bf16_to_f32(pr);
+            }
+            l = wave_sum(l);
+            if (lane == 0 && t0 + rw < R) { rec[(size_t)(t0 + rw) * AD_REC] = mx; rec[(size_t)(t0 + rw) * AD_REC + 1] = l; }
+        }
+        __syncthreads();
+        // ---- P . V: A[m = r][k = 8 g + j] = P[row r][key 32 ks + 8 g + j]; D[m = 4 g + i][n = r] = O[row 4 g + i][dim 32 wv + 16 nt + r]
+        f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int ks = 0; ks < C / 32; ++ks) {
+            const bf16x8 pa = load8(pb + r * VS + ks * 32 + 8 * g);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) o[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf[ks][nt], o[nt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (t0 + 4 * g + i < R) rec[(size_t)(t0 + 4 * g + i) * AD_REC + 4 + 32 * wv + 16 * nt + r] = o[nt][i];
+    }
+}
+
+// grid (heads, prompts * fanout), 128 threads = one per feature: the prompt's chunks in order, then the sample's tail chunks in order
+__global__ __launch_bounds__(128) void attn_shared_combine_kernel(const float* __restrict__ wsp, const float* __restrict__ wst,
+                                                                  bf16_t* __restrict__ o, int ldo, int heads, int kvh, int fanout, int ncp,
+                                                                  int nct) {
+    const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+    const int G = heads / kvh, hk = h / G, g = h % G, p = b / fanout, R = fanout * G, rr = (b % fanout) * G + g;
+    const float* pbase = wsp + ((size_t)p * kvh + hk) * ncp * R * AD_REC + (size_t)rr * AD_REC;
+    const float* tbase = wst + ((size_t)b * kvh + hk) * nct * G * AD_REC + (size_t)g * AD_REC;
+    const size_t ps = (size_t)R * AD_REC, ts = (size_t)G * AD_REC;
+    float mx = -INFINITY;
+    for (int c = 0; c < ncp; ++c) mx = fmaxf(mx, pbase[c * ps]);
+    for (int c = 0; c < nct; ++c) mx = fmaxf(mx, tbase[c * ts]);
+    float l = 0.f, acc = 0.f;
+    if (mx != -INFINITY)
+        for (int c = 0; c < ncp + nct; ++c) {
+            const float* rc = c < ncp ? pbase + c * ps : tbase + (c - ncp) * ts;
+            const float m = rc[0];
+            if (m == -INFINITY) continue;
+            const float w = exp2f(m - mx);
+            l += w * rc[1];
+            acc += w * rc[4 + d];
+        }
+    o[(size_t)b * ldo + (size_t)h * AD_HD + d] = f32_to_bf16(l > 0.f ? acc / l : 0.f);
+}
+
+// prompt chunk: 128 keys, 64 while that leaves the chip short of workgroups
+static int attn_shared_chunk(int prompts, int kvh, int len) { return (long)prompts * kvh * ((len + 127) / 128) < AD_TARGET_WGS ? 64 : 128; }
+static long attn_shared_prompt_floats(int prompts, int fanout, int heads, int prompt_cap) {
+    return (long)prompts * fanout * heads * ((prompt_cap + 63) / 64) * AD_REC;
+}
+
+extern "C" long vlr_attn_decode_shared_workspace_bytes(int prompts, int fanout, int heads, int prompt_cap, int tail_cap) {
+    if (prompts < 1 || fanout < 1 || heads < 1 || prompt_cap < 1 || tail_cap < 1) return 0;
+    return attn_shared_prompt_floats(prompts, fanout, heads, prompt_cap) * 4 + vlr_attn_decode_workspace_bytes(prompts * fanout, heads, tail_cap);
+}
+
+extern "C" int vlr_attn_decode_shared(const void* q, int ldq, const vlr_kv_shared* kv, void* o, int ldo, void* workspace, int heads,
+                                      int kv_heads, int head_dim, float scale, vlr_stream_t st) {
+    VLR_REQUIRE(q && kv && o && workspace, "vlr_attn_decode_shared: null argument");
+    VLR_REQUIRE(kv->k_prompt && kv->v_prompt && kv->prompt_mask && kv->k_tail && kv->v_tail, "vlr_attn_decode_shared: null cache pointer");
+    VLR_REQUIRE(head_dim == AD_HD, "vlr_attn_decode_shared: head_dim %d unsupported (the decode kernels take head_dim 128)", head_dim);
+    VLR_REQUIRE(kv_heads >= 1 && heads >= 1 && heads % kv_heads == 0, "vlr_attn_decode_shared: heads %d is not a multiple of kv_heads %d",
+                heads, kv_heads);
+    const int G = heads / kv_heads;
+    VLR_REQUIRE(G == 1 || G == 2 || G == 4 || G == 8, "vlr_attn_decode_shared: heads / kv_heads = %d (1, 2, 4 or 8 supported)", G);
+    VLR_REQUIRE(kv->prompts >= 1, "vlr_attn_decode_shared: prompts %d", kv->prompts);
+    VLR_REQUIRE(kv->fanout >= 1, "vlr_attn_decode_shared: fanout %d must be at least 1", kv->fanout);
+    VLR_REQUIRE(kv->prompt_len >= 1 && kv->prompt_len <= kv->prompt_cap, "vlr_attn_decode_shared: prompt_len %d outside 1 .. prompt_cap %d",
+                kv->prompt_len, kv->prompt_cap);
+    VLR_REQUIRE(kv->tail_len >= 1 && kv->tail_len <= kv->tail_cap, "vlr_attn_decode_shared: tail_len %d outside 1 .. tail_cap %d",
+                kv->tail_len, kv->tail_cap);
+    VLR_REQUIRE(ldq % 8 == 0 && ldq >= heads * head_dim && ldo >= heads * head_dim && ((uintptr_t)q & 15) == 0,
+                "vlr_attn_decode_shared: ldq %d / ldo %d too small, ldq not a multiple of 8 or q not 16-byte aligned", ldq, ldo);
+    VLR_REQUIRE((((uintptr_t)kv->k_prompt | (uintptr_t)kv->v_prompt | (uintptr_t)kv->k_tail | (uintptr_t)kv->v_tail) & 15) == 0,
+                "vlr_attn_decode_shared: cache pointers must be 16-byte aligned");
+    const int P = kv->prompts, n = kv->fanout, B = P * n;
+    const float sl2 = scale * 1.4426950408889634f;
+    float* wsp = (float*)workspace;
+    float* wst = wsp + attn_shared_prompt_floats(P, n, heads, kv->prompt_cap);
+    const int Cp = attn_shared_chunk(P, kv_heads, kv->prompt_len), ncp = (kv->prompt_len + Cp - 1) / Cp;
+    const dim3 gp(ncp, kv_heads, P);
+    if (Cp == 64)
+        hipLaunchKernelGGL(attn_shared_prompt_kernel<1>, gp, dim3(256), 0, st, (const bf16_t*)q, ldq, (const bf16_t*)kv->k_prompt,
+                           (const bf16_t*)kv->v_prompt, kv->prompt_mask, wsp, kv_heads, G, n, kv->prompt_cap, kv->prompt_len, ncp, sl2);
+    else
+        hipLaunchKernelGGL(attn_shared_prompt_kernel<2>, gp, dim3(256), 0, st, (const bf16_t*)q, ldq, (const bf16_t*)kv->k_prompt,
+                           (const bf16_t*)kv->v_prompt, kv->prompt_mask, wsp, kv_heads, G, n, kv->prompt_cap, kv->prompt_len, ncp, sl2);
+    // the samples' own tails: the grouped kernel with the tail as the cache and no mask
+    const int Ct = attn_decode_chunk(B, kv_heads, kv->tail_len), nct = (kv->tail_len + Ct - 1) / Ct;
+    const dim3 gt(nct, kv_heads, B);
+#define AD_LAUNCH(GG)                                                                                                               \
+    hipLaunchKernelGGL(attn_decode_kernel<GG>, gt, dim3(256), 0, st, (const bf16_t*)q, ldq, (const bf16_t*)kv->k_tail,            \
+                       (const bf16_t*)kv->v_tail, (const int*)nullptr, wst, kv_heads, kv->tail_cap, kv->tail_len, Ct, nct, sl2)
+    switch (G) {
+        case 1: AD_LAUNCH(1); break;
+        case 2: AD_LAUNCH(2); break;
+        case 4: AD_LAUNCH(4); break;
+        default: AD_LAUNCH(8); break;
+    }
+#undef AD_LAUNCH
+    hipLaunchKernelGGL(attn_shared_combine_kernel, dim3(heads, B), dim3(AD_HD), 0, st, (const float*)wsp, (const float*)wst, (bf16_t*)o, ldo,
+                       heads, kv_heads, n, ncp, nct);
+    return vlr_check_launch("vlr_attn_decode_shared");
 }

@@ -109,8 +109,22 @@ static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_
 static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
                         const vlr_decode_ws* ws, void* x_inout, const int* pos, void* k_cache, void* v_cache, const int* key_mask,
                         int batch, int cap, int len, hipStream_t st, const vlr_lora_weights* lw = nullptr,
-                        const vlr_decode_lora_ws* lws = nullptr) {
-    VLR_REQUIRE(cfg && w && ws && x_inout && pos && k_cache && v_cache && key_mask, "%s: null argument", fn);
+                        const vlr_decode_lora_ws* lws = nullptr, const vlr_kv_shared* sh = nullptr) {
+    VLR_REQUIRE(cfg && w && ws && x_inout && pos && (sh || (k_cache && v_cache && key_mask)), "%s: null argument", fn);
+    if (sh) {      // the shared prompt cache: batch = prompts * fanout rows, the new column is column tail_len - 1 of the tails
+        VLR_REQUIRE(sh->k_prompt && sh->v_prompt && sh->prompt_mask && sh->k_tail && sh->v_tail, "%s: null cache pointer", fn);
+        VLR_REQUIRE(sh->prompts >= 1, "%s: prompts %d", fn, sh->prompts);
+        VLR_REQUIRE(sh->fanout >= 1, "%s: fanout %d must be at least 1", fn, sh->fanout);
+        VLR_REQUIRE(sh->prompt_len >= 1 && sh->prompt_len <= sh->prompt_cap, "%s: prompt_len %d outside 1 .. prompt_cap %d", fn,
+                    sh->prompt_len, sh->prompt_cap);
+        VLR_REQUIRE(sh->tail_len >= 1 && sh->tail_len <= sh->tail_cap, "%s: tail_len %d outside 1 .. tail_cap %d", fn, sh->tail_len,
+                    sh->tail_cap);
+        batch = sh->prompts * sh->fanout;
+        cap = sh->tail_cap;
+        len = sh->tail_len - 1;
+        k_cache = sh->k_tail;
+        v_cache = sh->v_tail;
+    }
     VLR_REQUIRE(ws->xn && ws->rstd && ws->qkv && ws->attn && ws->act && ws->gemv_ws && ws->attn_ws, "%s: null scratch buffer", fn);
     VLR_REQUIRE(cfg->head_dim == 128, "%s: head_dim %d unsupported (the decode kernels take head_dim 128)", fn, cfg->head_dim);
     VLR_REQUIRE(batch >= 1, "%s: batch %d", fn, batch);
@@ -147,7 +161,8 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
         VLR_REQUIRE(lws->u_bytes >= need_u, "%s: the adapter scratch u has %ld bytes, %ld needed", fn, lws->u_bytes, need_u);
     }
     VLR_REQUIRE(ws->gemv_ws_bytes >= need, "%s: gemv_ws has %ld bytes, %ld needed", fn, ws->gemv_ws_bytes, need);
-    const long need_a = vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
+    const long need_a = sh ? vlr_attn_decode_shared_workspace_bytes(sh->prompts, sh->fanout, cfg->heads, sh->prompt_cap, sh->tail_cap)
+                           : vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
     VLR_REQUIRE(ws->attn_ws_bytes >= need_a, "%s: attn_ws has %ld bytes, %ld needed", fn, ws->attn_ws_bytes, need_a);
     const int rf = cfg->resid_f32;
     const size_t xs = rf ? 4 : 2;
@@ -156,8 +171,12 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     CHECK(gemv_rows(VLR_GEMV_QKV_ROPE, ws->xn, H, w->wqkv, q4 ? &q4->qkv : nullptr, ws->qkv, N, 2, w->bqkv, nullptr, 0, 0, pos, cfg, Nq + Nkv,
                     batch, N, H, ws->gemv_ws, st, &a_qkv));
     CHECK(vlr_kv_cache_write(off(ws->qkv, Nq), off(ws->qkv, (size_t)Nq + Nkv), N, k_cache, v_cache, batch, 1, kvh, cfg->head_dim, cap, len, st));
-    CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim, cap,
-                              len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    if (sh)
+        CHECK(vlr_attn_decode_shared(ws->qkv, N, sh, ws->attn, Nq, ws->attn_ws, cfg->heads, kvh, cfg->head_dim,
+                                     1.0f / sqrtf((float)cfg->head_dim), st));
+    else
+        CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim,
+                                  cap, len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
     CHECK(gemv_rows(mode_res, ws->attn, Nq, w->wo, q4 ? &q4->o : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H,
                     Nq, ws->gemv_ws, st, &a_o));
     CHECK(norm_fwd(rf, x_inout, w->ln2, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
@@ -193,6 +212,13 @@ extern "C" int vlr_decoder_layer_decode_w4_lora(const vlr_llama_cfg* cfg, const 
     VLR_REQUIRE(q4 && lora, "vlr_decoder_layer_decode_w4_lora: null packed weights or adapters");
     return layer_decode("vlr_decoder_layer_decode_w4_lora", cfg, w, q4, ws, x_inout, pos, k_cache, v_cache, key_mask, batch, cap, len, st, lora,
                         lws);
+}
+// the four routes above over a shared prompt cache (num_return_sequences): q4 and lora pick the route, kv replaces the per-sequence cache
+extern "C" int vlr_decoder_layer_decode_shared(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_weights_w4* q4,
+                                               const vlr_lora_weights* lora, const vlr_decode_ws* ws, const vlr_decode_lora_ws* lws,
+                                               void* x_inout, const int* pos, const vlr_kv_shared* kv, vlr_stream_t st) {
+    VLR_REQUIRE(kv, "vlr_decoder_layer_decode_shared: null cache description");
+    return layer_decode("vlr_decoder_layer_decode_shared", cfg, w, q4, ws, x_inout, pos, nullptr, nullptr, nullptr, 0, 0, 0, st, lora, lws, kv);
 }
 
 double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip: rounds vlr_gemm_bf16_tn_pair saves over two launches on the compute CUs of the moment

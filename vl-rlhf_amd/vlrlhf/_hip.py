@@ -63,6 +63,11 @@ class LayerWeightsW4(C.Structure):      # vlr_layer_weights_w4: the four fused p
     _fields_ = [(n, W4Linear) for n in ("qkv", "o", "gu", "down")]
 
 
+class KvShared(C.Structure):      # vlr_kv_shared: one layer's shared prompt segment and the per-sample tails (num_return_sequences)
+    _fields_ = [("k_prompt", P), ("v_prompt", P), ("prompt_mask", P), ("prompts", I), ("prompt_cap", I), ("prompt_len", I),
+                ("k_tail", P), ("v_tail", P), ("fanout", I), ("tail_cap", I), ("tail_len", I)]
+
+
 class VitCfg(C.Structure):
     _fields_ = [("hidden", I), ("mlp", I), ("heads", I), ("head_dim", I), ("ln_eps", F), ("act", I), ("head_dim_pad", I), ("attn_scale", F)]
 
@@ -181,6 +186,9 @@ _SIGS = {
     "vlr_gemv_w4_lora": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, I, P, F, P, P],
     "vlr_decoder_layer_decode_lora": [P, P, P, P, P, P, P, P, P, P, I, I, I, P],
     "vlr_decoder_layer_decode_w4_lora": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    # several samples per prompt over a shared prompt cache (include/vlr.h "SHARED prompt cache")
+    "vlr_attn_decode_shared": [P, I, P, P, I, P, I, I, I, F, P],
+    "vlr_decoder_layer_decode_shared": [P, P, P, P, P, P, P, P, P, P],
 }
 GEMV_BF16, GEMV_F32, GEMV_F32RES, GEMV_QKV_ROPE, GEMV_SWIGLU = range(5)      # vlr_gemv_bf16 modes
 _INT_HELPERS = {
@@ -210,7 +218,7 @@ _INT_HELPERS = {
 
 
 _LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes"]      # (int, int, int) -> long
-_LONG_HELPERS_N = {"vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3}      # name -> number of int arguments, -> long
+_LONG_HELPERS_N = {"vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5}      # name -> number of int arguments, -> long
 
 
 class VlrError(RuntimeError):

@@ -391,6 +391,65 @@ class KVCache:
         self.pos += 1
 
 
+class SharedPromptKVCache:
+    """K / V cache of `generate(num_return_sequences=n)`: the `fanout` = n samples of a prompt share ONE copy of the prompt's K / V.
+
+    prompt   a KVCache(new_tokens=0) of the P prompts, filled by the unchanged prefill (forward_hidden(kv_cache=cache.prompt)); never
+             written again.
+    tail     k_tail, v_tail [L][P*n][kv_heads][new_tokens][head_dim] bf16: the samples' own new tokens, one column per decode step.  Row
+             p*n + j is sample j of prompt p (the order of repeat_interleave).  Every tail column below `tail_len` is attended - finished
+             rows keep receiving pad tokens, as in KVCache - so the tail has no mask.
+    pos      [P*n] int32: each sample's NEXT position = the prompt's next position repeated n times, then + 1 per step.
+    `begin()` is called once after the prefill; open_column() / advance() bracket a decode step as KVCache's do."""
+
+    def __init__(self, layers, prompts, fanout, kv_heads, head_dim, new_tokens, device="cuda"):
+        if int(fanout) < 1:
+            raise ValueError(f"SharedPromptKVCache: fanout {fanout} must be at least 1")
+        self.prompt = KVCache(layers, prompts, kv_heads, head_dim, 0, device)
+        self.L, self.P, self.fanout, self.B = int(layers), int(prompts), int(fanout), int(prompts) * int(fanout)
+        self.kv_heads, self.head_dim, self.new_tokens = int(kv_heads), int(head_dim), int(new_tokens)
+        self.device = torch.device(device)
+        self.tail_cap = self.new_tokens
+        self.tail_len = 0
+        self.k_tail = self.v_tail = self.pos = None
+
+    @property
+    def cap(self):
+        """columns a sample can attend: the prompt's capacity plus its own tail's"""
+        return self.prompt.cap + self.tail_cap
+
+    @property
+    def len(self):
+        return self.prompt.len + self.tail_len
+
+    def nbytes(self):
+        """bytes of K / V held (prompt once, tails per sample)"""
+        return 2 * 2 * self.L * self.kv_heads * self.head_dim * (self.P * self.prompt.cap + self.B * self.tail_cap)
+
+    def begin(self, alloc=True):
+        """after the prefill: empty tails, and every sample starts at its prompt's next position"""
+        if self.prompt.len < 1:
+            raise ValueError("SharedPromptKVCache.begin: the prompt segment is empty (run the prefill first)")
+        self.tail_len = 0
+        self.pos = self.prompt.pos.repeat_interleave(self.fanout).contiguous()
+        if alloc:
+            shape = (self.L, self.B, self.kv_heads, max(self.tail_cap, 1), self.head_dim)
+            self.k_tail = torch.empty(shape, dtype=BF16, device=self.device)
+            self.v_tail = torch.empty(shape, dtype=BF16, device=self.device)
+
+    def open_column(self):
+        """-> the tail column the coming decode step writes (attended by construction: the tail carries no mask)"""
+        if self.pos is None:
+            raise ValueError("SharedPromptKVCache: begin() has not been called")
+        if self.tail_len >= self.tail_cap:
+            raise ValueError(f"KV cache full: {self.tail_len} of {self.tail_cap} tail columns filled")
+        return self.tail_len
+
+    def advance(self):
+        self.tail_len += 1
+        self.pos += 1
+
+
 class LlavaHipEngine:
     supports_resid_f32 = True      # False: the subclass adds to the residual stream with bf16 primitives
     supports_ckpt = True           # False: the backward cannot re-run a layer's forward (read per pass by forward_hidden: checkpointing is ignored)
@@ -922,8 +981,13 @@ class LlavaHipEngine:
             _hip.call("vlr_gemv_bf16", mode, X[m0:m0 + mr], X.shape[1], W, Y[m0:m0 + mr], Y.shape[1], None, None, 0, None, None, None,
                       0, self.hd, self.max_pos, mr, N, K, ws)
 
-    def _decode_ws(self, B, cap):
-        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0)
+    def new_shared_kv_cache(self, prompts, fanout, new_tokens) -> SharedPromptKVCache:
+        """an empty shared-prompt cache: prefill `cache.prompt` (forward_hidden(kv_cache=cache.prompt)), then cache.begin()"""
+        return SharedPromptKVCache(self.L, prompts, fanout, self.nkv, self.hd, new_tokens, self.dev)
+
+    def _decode_ws(self, B, cap, shared=None):
+        """shared: (prompts, fanout, prompt_cap, tail_cap) of a SharedPromptKVCache - sizes the attention workspace for it"""
+        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0, shared)
         d = self._ws.get(key)
         if d is None:
             self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
@@ -939,7 +1003,10 @@ class LlavaHipEngine:
                 rt = (nq * r, r, 2 * r, r)
                 gb = max([gb] + [int(_hip.lib().vlr_gemv_lora_workspace_bytes(mb, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
                 ub = max(int(_hip.lib().vlr_gemv_lora_u_bytes(mb, k, t)) for (n, k), t in zip(shapes[:4], rt))
-            ab = int(_hip.lib().vlr_attn_decode_workspace_bytes(B, self.nh, cap))
+            if shared is not None:
+                ab = int(_hip.lib().vlr_attn_decode_shared_workspace_bytes(shared[0], shared[1], self.nh, shared[2], shared[3]))
+            else:
+                ab = int(_hip.lib().vlr_attn_decode_workspace_bytes(B, self.nh, cap))
             d = dict(xn=torch.empty(B, self.H, dtype=BF16, device=self.dev), rstd=torch.empty(B, dtype=torch.float32, device=self.dev),
                      qkv=torch.empty(B, self.Nqkv, dtype=BF16, device=self.dev), attn=torch.empty(B, self.Nq, dtype=BF16, device=self.dev),
                      act=torch.empty(B, self.I, dtype=BF16, device=self.dev), gemv=torch.empty(gb, dtype=torch.uint8, device=self.dev),
@@ -958,7 +1025,9 @@ class LlavaHipEngine:
         embedding row gather -> L x vlr_decoder_layer_decode -> final RMSNorm -> lm-head (skinny GEMM, fp32 out).
         tokens [B] (ids appended at column cache.len) -> logits fp32 [B][V]; the cache advances by one column.
         lora (None: forward_hidden's rule - the adapters are live when `ws` is the policy and they are active; False: never): live
-        adapters run vlr_decoder_layer_decode_lora / _w4_lora, un-merged; everything else makes the adapter-free calls."""
+        adapters run vlr_decoder_layer_decode_lora / _w4_lora, un-merged; everything else makes the adapter-free calls.
+        cache: a KVCache, or a SharedPromptKVCache (B = prompts * fanout rows: every layer is one vlr_decoder_layer_decode_shared, which
+        takes the same three weight routes)."""
         if not self.supports_kv_cache:
             raise ValueError(f"{type(self).__name__} has no KV-cache decoding")
         B, H = cache.B, self.H
@@ -967,7 +1036,11 @@ class LlavaHipEngine:
             if lora and not use_lora:
                 raise ValueError("decode_step(lora=True): live adapters need the policy weights and active adapters")
             use_lora = bool(lora)
-        d = self._decode_ws(B, cache.cap)
+        shared = isinstance(cache, SharedPromptKVCache)
+        if shared:
+            d = self._decode_ws(B, cache.cap, (cache.P, cache.fanout, cache.prompt.cap, cache.tail_cap))
+        else:
+            d = self._decode_ws(B, cache.cap)
         tok = tokens.to(device=self.dev, dtype=torch.int32).contiguous()
         length = cache.open_column()
         x = d["x"]
@@ -977,6 +1050,20 @@ class LlavaHipEngine:
         else:
             _hip.call("vlr_gather_rows", ws.v["embed"], tok, x, B, H)
         for l in range(self.L):
+            if shared:
+                pr = cache.prompt
+                kv = _hip.KvShared(pr.k[l].data_ptr(), pr.v[l].data_ptr(), pr.key_mask.data_ptr(), cache.P, pr.cap, pr.len,
+                                   cache.k_tail[l].data_ptr(), cache.v_tail[l].data_ptr(), cache.fanout, cache.tail_cap, length + 1)
+                if self.packed is not None:
+                    v = ws.v
+                    w = _hip.LayerWeights(v[f"l{l}.ln1"].data_ptr(), None, None, v[f"l{l}.ln2"].data_ptr(), None, None,
+                                          v[f"l{l}.bqkv"].data_ptr() if f"l{l}.bqkv" in v else None)
+                    q4 = self.layer_weights_w4(l)
+                else:
+                    w, q4 = self.layer_weights(ws, l), None
+                _hip.call("vlr_decoder_layer_decode_shared", self.llama_cfg, w, q4, self._lora_structs(l, train=False)[0] if use_lora else None,
+                          d["struct"], d["lora_struct"] if use_lora else None, x, cache.pos, kv)
+                continue
             if self.packed is not None:      # the projections stream their 4-bit form: nothing is dequantised to HBM
                 v = ws.v
                 w = _hip.LayerWeights(v[f"l{l}.ln1"].data_ptr(), None, None, v[f"l{l}.ln2"].data_ptr(), None, None,

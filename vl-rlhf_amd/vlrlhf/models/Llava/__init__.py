@@ -454,7 +454,7 @@ class LlavaForRL(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, max_length=None, max_new_tokens=None, do_sample=False, temperature=1.0,
                  top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True,
-                 merge_lora=True, **img):
+                 merge_lora=True, num_return_sequences=1, **img):
         """What the reference trainer's `get_batch_samples` calls (base/trainer.py:310-360: `model.generate(input_ids, attention_mask,
         max_length, do_sample=True, pad_token_id, **img_input_dict)`, transformers GenerationMixin defaults: temperature 1, top_k 50,
         top_p 1, use_cache True).  Prompts are LEFT-padded (trl's collator; the merge of the reference end-aligns such rows) and padded
@@ -473,11 +473,30 @@ class LlavaForRL(nn.Module):
           a packed GPTQ base (q_lora) always takes the live path, whatever merge_lora says: nothing can be merged into packed weights.
         With the adapters disabled (disable_adapter()) or absent the plain weights are decoded.  use_cache=False, or an engine without the cache (Qwen-VL, InternLM-XComposer2): every new token
         re-runs the forward of the whole sequence (the vision features of the batch are cached by the engine), the running batch
-        left-padded to a multiple of 32 tokens so that the engine sees a new shape every 32 steps, not every step."""
+        left-padded to a multiple of 32 tokens so that the engine sees a new shape every 32 steps, not every step.
+
+        num_return_sequences = n (also read from generation_config, like do_sample): n samples per prompt; the result has P * n rows, row
+        p * n + j being sample j of prompt p (the order of transformers' repeat_interleave expansion).  n > 1 needs do_sample=True
+        (transformers refuses greedy search with several return sequences: ValueError).  n == 1 is the code path above, unchanged.
+          n > 1 on the KV-cache path (use_cache=True, supports_kv_cache, head_dim 128; all three adapter routes): the P prompts are
+            prefilled ONCE into a SharedPromptKVCache, the first logits are repeated n times, and every further token is one decode step
+            of P * n rows over the shared prompt K / V plus each sample's own tail (engine.decode_step -> vlr_decoder_layer_decode_shared):
+            one prefill, one copy of the prompt's K / V, one read of it per token;
+          n > 1 otherwise (use_cache=False, Qwen-VL, InternLM-XComposer2, other head dims): ids, mask and every image input are expanded
+            by repeat_interleave(n) and the loop above runs on P * n rows - nothing is shared."""
         if generation_config is not None:
             max_new_tokens = max_new_tokens if max_new_tokens is not None else getattr(generation_config, "max_new_tokens", None)
             do_sample = bool(getattr(generation_config, "do_sample", do_sample))
             use_cache = bool(getattr(generation_config, "use_cache", use_cache))
+            nrs = getattr(generation_config, "num_return_sequences", None)
+            if nrs is not None and num_return_sequences == 1:
+                num_return_sequences = nrs
+        fanout = int(num_return_sequences)
+        if fanout < 1:
+            raise ValueError(f"num_return_sequences has to be a positive integer, got {num_return_sequences}")
+        if fanout > 1 and not do_sample:
+            raise ValueError(f"Greedy methods without beam search do not support num_return_sequences different than 1 (got {fanout}): "
+                             "pass do_sample=True")
         if input_ids is None:
             raise ValueError("generate needs input_ids")
         dev = self.engine.dev
@@ -496,14 +515,18 @@ class LlavaForRL(nn.Module):
         img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
         was_training = self.training
         self.eval()
-        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         lm_head = self.weights.v["lm_head"]
         if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
             try:
                 return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img,
-                                             self.cached_lora_route(merge_lora))
+                                             self.cached_lora_route(merge_lora), **({"fanout": fanout} if fanout > 1 else {}))
             finally:
                 self.train(was_training)
+        if fanout > 1:      # no shared cache on this route: the transformers expansion, sample j of prompt p at row p * n + j
+            ids, mask = ids.repeat_interleave(fanout, 0), mask.repeat_interleave(fanout, 0)
+            img = {k: self._expand_rows(v, B, fanout) for k, v in img.items()}
+            B = B * fanout
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         try:
             while ids.shape[1] < limit and bool(unfinished.any()):
                 T = ids.shape[1]
@@ -528,6 +551,15 @@ class LlavaForRL(nn.Module):
             self.train(was_training)
         return ids
 
+    @staticmethod
+    def _expand_rows(v, B, n):
+        """an image input of B prompts -> B * n rows in repeat_interleave order (tensors and per-prompt lists; anything else as it is)"""
+        if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+            return v.repeat_interleave(n, 0)
+        if isinstance(v, (list, tuple)) and len(v) == B:
+            return type(v)(x for x in v for _ in range(n))
+        return v
+
     def _last_logits(self, c, B, lm_head):
         """fp32 logits [B][V] of the last attended merged row of every sequence (vlr_gemm_bf16 on at least 8 rows)"""
         dev, H = self.engine.dev, self.engine.H
@@ -550,14 +582,16 @@ class LlavaForRL(nn.Module):
             return "plain"
         return "merged" if (merge_lora and not self.is_packed) else "live"
 
-    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route):
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, fanout=1):
         """generate's KV-cache path: the prefill is the first iteration of the re-forward loop (same padded input, same lm-head
-        call) with the K / V rows kept; each further token is one engine.decode_step.  route: cached_lora_route()."""
+        call) with the K / V rows kept; each further token is one engine.decode_step.  route: cached_lora_route().
+        fanout > 1 (num_return_sequences): the prefill fills the prompt segment of a SharedPromptKVCache, its logits are repeated
+        `fanout` times and the B * fanout samples decode over the shared prompt K / V."""
         eng, dev = self.engine, self.engine.dev
         B, T = ids.shape
-        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        unfinished = torch.ones(B * fanout, dtype=torch.bool, device=dev)
         if T >= limit:
-            return ids
+            return ids.repeat_interleave(fanout, 0) if fanout > 1 else ids
         ws = self.weights
         if ws is eng.policy:
             eng.wait_optimizer()
@@ -574,12 +608,16 @@ class LlavaForRL(nn.Module):
             raise ValueError("generate on the MI355X path needs pixel_values")
         if eng.anyres and img.get("image_sizes") is None:
             raise ValueError("LLaVA-Next generate needs image_sizes (reference LlavaNext/__init__.py:216-222)")
-        cache = eng.new_kv_cache(B, limit - T)
+        cache = eng.new_kv_cache(B, limit - T) if fanout == 1 else eng.new_shared_kv_cache(B, fanout, limit - T)
         c = eng.forward_hidden(ws, run_ids, run_mask, None, pv, image_dup=int(getattr(pv, "_vlr_dup", 1)), save=False,
                                tag="policy_ng" if self.weights is eng.policy else "ref", image_sizes=img.get("image_sizes"),
-                               kv_cache=cache)
+                               kv_cache=cache if fanout == 1 else cache.prompt)
         logits = self._last_logits(c, B, ws.v["lm_head"])
         out = [ids]
+        if fanout > 1:
+            cache.begin()
+            logits = logits.repeat_interleave(fanout, 0)
+            out = [ids.repeat_interleave(fanout, 0)]
         n = T
         while True:
             if do_sample:
