@@ -279,6 +279,17 @@ int vlr_merge_fwd_f32(const int* src, const long* input_ids, const void* embed_t
                       int Bn, int T, int S, int H, vlr_stream_t stream);
 int vlr_merge_bwd(const void* dmerged, const int* src, const int* inv_map, const long* input_ids, void* dfeats,
                   void* dembed_table, int Bn, int T, int S, int H, int n_feat_rows, int dup, vlr_stream_t stream);
+/* NEFTune embedding noise (transformers.trainer_utils.neftune_post_forward_hook: E += U(-m, m), m = alpha / sqrt(T * H), on the output
+ * of the input embedding in training mode), in place on the merged x [Bn * S][H] - bf16, or fp32 when x_f32.  Additive entry: the ABI
+ * version does not move.  Rows with src[b * S + s] = t >= 0 are text rows (t = the pre-merge token position, the merge's convention):
+ * x[c] += n(b * T + t, c).  Image-feature rows and zero rows (src < 0) are neither read nor written - the reference replaces the
+ * placeholder rows by image features after the hook ran.  H % 8 == 0.
+ *   n: word c % 4 of the Philox4x32-10 block with counter (c / 4, b * T + t, call, pass) and key (low, high half of `key`); its top 24
+ *   bits r -> h = r - 8388607.5 (exact), n = h * scale rounded to fp32 once, x + n rounded to fp32 once (no fused multiply-add) and,
+ *   for a bf16 x, rounded to nearest-even once more.  scale = m * 2^-23 computed by the caller in fp32, in [0, 1): |n| < m, n != 0
+ *   (unless scale is 0), symmetric.  The value depends on (key, call, pass, b * T + t, c) only: a host replay is bit-exact. */
+int vlr_neftune_add(void* x, int x_f32, const int* src, int Bn, int T, int S, int H, float scale, uint64_t key, uint32_t call,
+                    uint32_t pass, vlr_stream_t stream);
 
 /* ---- log-probabilities (VLDPOTrainer.get_batch_logps, base/trainer.py:148-188) ------------------------------- */
 int vlr_build_rows(const long* labels, const unsigned char* shared_mask, int Bn, int S, int label_pad, int* rows,

@@ -247,6 +247,63 @@ __global__ __launch_bounds__(256) void merge_gather_f32_kernel(const int* __rest
         *reinterpret_cast<f32x4*>(out + pos * H + c + 4) = hi;
     }
 }
+// ------------------------------------------------------------------------------------------------------------
+// NEFTune (transformers.trainer_utils.neftune_post_forward_hook): uniform noise on the TEXT rows of the merged embeddings, in place.
+// Counter-based: Philox4x32-10 (Salmon et al., SC'11) with counter = (column / 4, pre-merge token index b*T + t, call, pass) and the two
+// halves of `key` as its key, so a value depends on nothing but those - not on the launch geometry, not on the merged layout.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+// word -> noise: the top 24 bits r give h = r - (2^23 - 1/2) (exact in fp32: a half-integer below 2^23), n = h * scale rounded once.
+// scale = m 2^-23, so |n| < m, n is never 0 and the 2^24 values are symmetric about 0.  The sum x + n is a second, separate rounding:
+// contraction is switched off for the two operators below.  (Not __fmul_rn / __fadd_rn: hipcc's headers define them as the plain
+// operators under the default contraction mode, and the pair comes out as one v_fma_f32.)
+__device__ __forceinline__ float neftune_add1(float x, uint32_t w, float scale) {
+#pragma clang fp contract(off)
+    const float h = (float)(w >> 8) - 8388607.5f;
+    const float n = h * scale;
+    return x + n;
+}
+// one workgroup per merged row, one lane per 8 columns (two Philox blocks), 16-byte accesses as merge_gather_kernel
+template <bool F32>
+__global__ __launch_bounds__(256) void neftune_add_kernel(void* __restrict__ xv, const int* __restrict__ src, int T, int S, int H,
+                                                          float scale, uint32_t k0, uint32_t k1, uint32_t call, uint32_t pass) {
+    const size_t pos = blockIdx.x;         // b*S + s
+    const int sv = src[pos];
+    if (sv < 0) return;                    // image-feature rows and SRC_ZERO rows: neither read nor written
+    const uint32_t tok = (uint32_t)(pos / S) * (uint32_t)T + (uint32_t)sv;
+    for (int c = threadIdx.x * 8; c < H; c += 256 * 8) {
+        uint32_t w[8];
+        philox4x32_10((uint32_t)c >> 2, tok, call, pass, k0, k1, w);
+        philox4x32_10(((uint32_t)c >> 2) + 1u, tok, call, pass, k0, k1, w + 4);
+        float v[8];
+        if (F32) {
+            float* x = reinterpret_cast<float*>(xv) + pos * H + c;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(x), hi = *reinterpret_cast<const f32x4*>(x + 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = neftune_add1(lo[i], w[i], scale), v[4 + i] = neftune_add1(hi[i], w[4 + i], scale);
+            *reinterpret_cast<f32x4*>(x) = f32x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<f32x4*>(x + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        } else {
+            bf16_t* x = reinterpret_cast<bf16_t*>(xv) + pos * H + c;
+            unpack8(*reinterpret_cast<const u32x4*>(x), v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = neftune_add1(v[i], w[i], scale);
+            *reinterpret_cast<u32x4*>(x) = pack8(v);           // the fp32 sum rounded to nearest-even once
+        }
+    }
+}
 // d_feats[f] = sum over the `dup` positions that consumed feature row f
 __global__ __launch_bounds__(256) void merge_bwd_feats_kernel(const bf16_t* __restrict__ dmerged,
                                                               const int* __restrict__ inv_map, bf16_t* __restrict__ dfeats,
@@ -672,6 +729,19 @@ extern "C" int vlr_merge_fwd_f32(const int* src, const long* input_ids, const vo
     hipLaunchKernelGGL(merge_gather_f32_kernel, dim3(Bn * S), dim3(256), 0, st, src, input_ids, (const bf16_t*)embed_table, feats,
                        feats_f32, out, T, S, H);
     return vlr_check_launch("vlr_merge_fwd_f32");
+}
+extern "C" int vlr_neftune_add(void* x, int x_f32, const int* src, int Bn, int T, int S, int H, float scale, uint64_t key, uint32_t call,
+                               uint32_t pass, hipStream_t st) {
+    VLR_REQUIRE(x && src, "vlr_neftune_add: null argument");
+    VLR_REQUIRE(Bn > 0 && T > 0 && S > 0 && H > 0 && H % 8 == 0 && (long)Bn * S <= 0x7fffffffL && (long)Bn * T <= 0x7fffffffL,
+                "vlr_neftune_add: bad shape Bn=%d T=%d S=%d H=%d (H %% 8 == 0)", Bn, T, S, H);
+    VLR_REQUIRE(scale >= 0.f && scale < 1.f, "vlr_neftune_add: scale = m * 2^-23 must lie in [0, 1), got %g", (double)scale);
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    if (x_f32)
+        hipLaunchKernelGGL(neftune_add_kernel<true>, dim3(Bn * S), dim3(256), 0, st, x, src, T, S, H, scale, k0, k1, call, pass);
+    else
+        hipLaunchKernelGGL(neftune_add_kernel<false>, dim3(Bn * S), dim3(256), 0, st, x, src, T, S, H, scale, k0, k1, call, pass);
+    return vlr_check_launch("vlr_neftune_add");
 }
 extern "C" int vlr_merge_bwd(const void* dmerged, const int* src, const int* inv_map, const long* input_ids,
                              void* dfeats, void* dembed_table, int Bn, int T, int S, int H, int n_feat_rows, int dup,

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("VLR_LIB") or os.path.join(os.path.dirname(_HERE), "li
 
 _lib = None
 
-P, I, L, F, U64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64
+P, I, L, F, U64, U32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_uint32
 
 
 class LlamaCfg(C.Structure):
@@ -119,6 +119,7 @@ _SIGS = {
     "vlr_merge_fwd": [P, P, P, P, P, I, I, I, I, P],
     "vlr_merge_bwd": [P, P, P, P, P, P, I, I, I, I, I, I, P],
     "vlr_merge_fwd_f32": [P, P, P, P, I, P, I, I, I, I, P],
+    "vlr_neftune_add": [P, I, P, I, I, I, I, F, U64, U32, U32, P],
     "vlr_build_rows": [P, P, I, I, I, P, P, P, P],
     "vlr_logp_rows": [P, P, P, I, I, L, P, P, P],
     "vlr_dlogits_rows": [P, P, P, P, I, P, I, I, I, L, P, L, P],

@@ -106,9 +106,34 @@ class VLTrainerLoop:
     A subclass provides `compute_loss(model, inputs)`, `prediction_step(model, inputs)` and the attributes model / args / train_dataset /
     eval_dataset / data_collator / accelerator / state / log_history / callbacks / is_peft_model / _stored_metrics."""
 
+    # ------------------------------------------------------------------------------------------ NEFTune
+    neftune_noise_alpha = None
+
+    def _init_neftune(self, model, args, alpha=None):
+        """transformers Trainer.__init__ (`self.neftune_noise_alpha = args.neftune_noise_alpha`) / trl SFTTrainer (the constructor
+        argument wins): remembers alpha; a model that cannot apply the noise (no HIP engine behind it) is refused here, not at step 1."""
+        if alpha is None:
+            alpha = getattr(args, "neftune_noise_alpha", None)
+        if alpha is not None and not hasattr(getattr(model, "engine", None), "set_neftune"):
+            raise NotImplementedError("neftune_noise_alpha (NEFTune embedding noise) needs a model wrapper on the HIP engine "
+                                      "(engine.set_neftune); this one has none")
+        self.neftune_noise_alpha = None if alpha is None else float(alpha)
+
+    def _activate_neftune(self):
+        """transformers Trainer._activate_neftune: noise on the input embeddings of the training passes from here on.  Key = args.seed
+        (low word) and the data-parallel rank (high word); the engine's call counter goes on from where it stands (resume)."""
+        if self.neftune_noise_alpha is not None:
+            seed = getattr(self.args, "seed", None)
+            self.model.engine.set_neftune(self.neftune_noise_alpha, seed=42 if seed is None else int(seed), rank=_rank())
+
+    def _deactivate_neftune(self):
+        """transformers Trainer._deactivate_neftune (end of train()): what runs after training sees clean embeddings"""
+        if self.neftune_noise_alpha is not None:
+            self.model.engine.set_neftune(None)
+
     # hooks of the loop a subclass may fill (VLDPOTrainer: the reference pre-pass and pipelining, the sampled eval table)
     def _before_train(self):
-        pass
+        self._activate_neftune()
 
     def prefetch_reference(self, inputs):
         return inputs
@@ -261,7 +286,7 @@ class VLTrainerLoop:
     def save_checkpoint(self, step: int, micro: int, epoch: int, window_len: int = 0):
         """HF Trainer._save_checkpoint for this path: `output_dir/checkpoint-<step>/` with the weights (adapters under LoRA),
         the optimizer state (fp32 master / m / v + step), trainer_state.json (step counters, log history, the dropout call counters
-        that seed the counter-based masks, world size / accumulation steps the counters were taken under); rotated to
+        that seed the counter-based masks and the call counter of the NEFTune noise, world size / accumulation steps the counters were taken under); rotated to
         `save_total_limit`.  Rank 0 writes (every rank holds identical state under DDP)."""
         import json
         import os
@@ -285,6 +310,7 @@ class VLTrainerLoop:
         with open(os.path.join(tmp, "trainer_state.json"), "w") as f:
             json.dump(dict(global_step=step, micro_step=micro, epoch=epoch, opt_step=eng.opt_step, log_history=self.log_history,
                            world_size=_world(), lora_calls=getattr(eng, "_lora_calls", 0), plora_calls=getattr(eng, "_plora_calls", 0),
+                           neftune_calls=getattr(eng, "_neftune_calls", 0),
                            gradient_accumulation_steps=max(1, int(getattr(self.args, "gradient_accumulation_steps", 1) or 1)),
                            per_device_train_batch_size=int(getattr(self.args, "per_device_train_batch_size", 4))), f, indent=1)
         shutil.rmtree(path, ignore_errors=True)
@@ -322,10 +348,19 @@ class VLTrainerLoop:
             eng._lora_calls = int(state.get("lora_calls", 0))
         if hasattr(eng, "_plora_calls"):
             eng._plora_calls = int(state.get("plora_calls", 0))
+        if hasattr(eng, "_neftune_calls"):
+            eng._neftune_calls = int(state.get("neftune_calls", 0))
         self.log_history = list(state.get("log_history", []))
         return state
 
     def train(self, resume_from_checkpoint=None):
+        """the step loop; NEFTune (neftune_noise_alpha) is on from _before_train to the return, as in transformers Trainer.train"""
+        try:
+            return self._train(resume_from_checkpoint)
+        finally:
+            self._deactivate_neftune()
+
+    def _train(self, resume_from_checkpoint=None):
         a = self.args
         eng = self.model.engine
         ga = max(1, int(getattr(a, "gradient_accumulation_steps", 1) or 1))
@@ -475,6 +510,7 @@ class VLDPOTrainer(VLTrainerLoop):
                 raise ValueError("peft_config given but the model wrapper has no apply_lora()")
             model.apply_lora(peft_config)
         self.is_peft_model = bool(getattr(model, "is_peft_model", False))
+        self._init_neftune(model, args)          # transformers Trainer: args.neftune_noise_alpha (the policy's training passes only)
         self.processor = processor
         self.tokenizer = processor.tokenizer if processor is not None else None
         self.model = model
@@ -771,6 +807,7 @@ class VLDPOTrainer(VLTrainerLoop):
         if self.precompute_ref_log_probs and not self._precomputed_train_ref_log_probs:
             self.precompute_reference_log_probs(self.train_dataset)
             self._precomputed_train_ref_log_probs = True
+        super()._before_train()
 
     def _before_evaluate(self, ds, explicit: bool):
         if self.precompute_ref_log_probs and not self._precomputed_eval_ref_log_probs and not explicit:
@@ -949,8 +986,7 @@ class VLSFTTrainer(VLTrainerLoop):
         # argument order = reference base/trainer.py:574-601
         if model is None:
             raise ValueError("VLSFTTrainer needs a model")
-        if neftune_noise_alpha is not None:
-            raise NotImplementedError("neftune_noise_alpha (NEFTune embedding noise) is not on the MI355X SFT path")
+        self._init_neftune(model, args, neftune_noise_alpha)
         if peft_config is not None:          # trl SFTTrainer.__init__: model = get_peft_model(model, peft_config)
             if not hasattr(model, "apply_lora"):
                 raise ValueError("peft_config given but the model wrapper has no apply_lora()")

@@ -83,6 +83,7 @@ class TrainingArguments:
     dataloader_prefetch: int = 2             # batches collated ahead on the background thread (base/loader.py); 0 = inline
     remove_unused_columns: bool = False
     local_rank: int = 0
+    neftune_noise_alpha: Optional[float] = None      # transformers.TrainingArguments: NEFTune noise on the input embeddings while training
 
 
 def _parse(*classes, argv=None):

@@ -23,6 +23,13 @@ def _align(n, a=8):
     return (n + a - 1) // a * a
 
 
+def neftune_scale(alpha, T, H):
+    """NEFTune magnitude m = alpha / sqrt(T * H) (transformers neftune_post_forward_hook: T = width of the input_ids the forward was
+    handed) and the multiplier m * 2^-23 of include/vlr.h vlr_neftune_add, both rounded to fp32 once, as Python floats"""
+    m = float(torch.tensor(float(alpha) / math.sqrt(float(T) * float(H)), dtype=torch.float32))
+    return m, float(torch.tensor(m * 2.0 ** -23, dtype=torch.float32))
+
+
 def qkv_row_perm(nh, nkv, hd):
     """InternLM2 stores the rows of its fused grouped-query wqkv per K/V head as [q_0..q_{g-1} | k | v]: the permutation that re-orders
     them to q | k | v blocks (engine row i = checkpoint row perm[i])"""
@@ -511,6 +518,9 @@ class LlavaHipEngine:
         self.lora = None                         # dict(r, scale, dropout) once enable_lora() ran
         self.lora_active = True                  # False inside LlavaForRL.disable_adapter() (reference pass)
         self.training = True                     # lora_dropout only in training mode
+        self.neftune = None                      # dict(alpha, key) between set_neftune(alpha, ...) and set_neftune(None)
+        self._neftune_calls = 0                  # noisy passes so far: the `call` word of the noise counter (checkpointed)
+        self.last_neftune = None                 # (key, call, pass, T, scale) of the last noisy pass (tests replay the noise from it)
         self._norm_ws = torch.empty(_hip.helper("vlr_rmsnorm_bwd_workspace_bytes", self.H), dtype=torch.uint8, device=self.dev)
         self._colsum_ws = torch.empty(_hip.helper("vlr_colsum_workspace_bytes", max(self.H, self.Nqkv, 8)), dtype=torch.uint8, device=self.dev)
         self._sq_ws = torch.empty(_hip.helper("vlr_grad_sqnorm_workspace_bytes"), dtype=torch.uint8, device=self.dev)
@@ -687,6 +697,25 @@ class LlavaHipEngine:
                               out, inn, r, r, inn, inn, inn, 0, 0, 0, sc)
                     row += out
         return ws
+
+    # ------------------------------------------------------------------------------------------------ NEFTune
+    def set_neftune(self, alpha, seed=42, rank=0):
+        """transformers Trainer._activate_neftune / _deactivate_neftune: alpha = neftune_noise_alpha switches the embedding noise of
+        the training passes on (forward_hidden: policy weights, a pass that will be back-propagated), None switches it off.  The
+        noise key is `seed` in the low word and the data-parallel `rank` in the high word, so ranks draw different noise; the call
+        counter is NOT reset - a resumed run (checkpointed counter) continues the stream."""
+        if alpha is None:
+            self.neftune = None
+            return
+        alpha = float(alpha)
+        if not (math.isfinite(alpha) and alpha >= 0.0):
+            raise ValueError(f"neftune_noise_alpha must be a finite number >= 0, got {alpha}")
+        self.neftune = dict(alpha=alpha, key=(int(seed) & 0xFFFFFFFF) | ((int(rank) & 0xFFFFFFFF) << 32))
+
+    def _neftune_add(self, x0, src, Bn, T, S, nf):
+        """x0 [Bn*S, H] (merged embeddings, either stream type) += the noise of nf = (key, call, pass, T, scale) on its text rows"""
+        key, call, npass, _, scale = nf
+        _hip.call("vlr_neftune_add", x0, int(x0.dtype == torch.float32), src, Bn, T, S, self.H, scale, key, call, npass)
 
     # ------------------------------------------------------------------------------------------------ workspaces
     def _buf(self, key, shape, dtype=BF16, zero=False):
@@ -938,6 +967,17 @@ class LlavaHipEngine:
         else:
             x0 = self._buf((tag, "x0", Bn, S), (M, self.H))
             _hip.call("vlr_merge_fwd", src, ids, ws.v["embed"], feats, x0, Bn, T, S, self.H)
+        # NEFTune: noise on the text rows of a TRAINING pass only (the condition of training-mode dropout: policy weights, a pass that
+        # will be back-propagated).  Reference passes - a separate reference model, the adapter-off pass, precomputed or prefetched
+        # reference log-probs - evaluation and generation never come here.  One draw per pass: under gradient checkpointing the
+        # recompute reads this x0 (ctx["x0"]).  NO path rebuilds x0 today; ctx["neftune"] (the draw's key - nothing but the tests reads
+        # it) is what such a path would have to reuse instead of bumping the counter.
+        nf = None
+        if self.neftune is not None and ws is self.policy and save:
+            self._neftune_calls += 1
+            nf = (self.neftune["key"], self._neftune_calls & 0xFFFFFFFF, 0, T, neftune_scale(self.neftune["alpha"], T, self.H)[1])
+            self._neftune_add(x0, src, Bn, T, S, nf)
+            self.last_neftune = nf
         x = x0
         acts = []
         use_lora = self.lora is not None and self.lora_active and ws is self.policy
@@ -967,7 +1007,7 @@ class LlavaHipEngine:
         return dict(ws=ws, Bn=Bn, T=T, S=S, M=M, ids=ids, src=src, inv=inv, mask=mask, labels=mlabels, pos=pos,
                     img_map=img_map.bool(), hidden=hidden, rstd_f=rstd_f, x_last=x, x0=x0, acts=acts if save else None,
                     vit_feat=vit_feat, feats=feats, proj_z=z, proj_h=h, image_dup=image_dup, n_rows=n_rows, n_feat=n_feat,
-                    pack=pack, tag=tag, lora_seed=lora_seed, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
+                    pack=pack, tag=tag, lora_seed=lora_seed, neftune=nf, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
                     embed=dict(pos=e["pos"], mask=e["mask"], extra=e.get("extra"), tag=tag, img_map=e["img_map"], plora_seed=e.get("plora_seed"), grad_pass=bool(save)))
 
     # ------------------------------------------------------------------------------------------------ decoding
