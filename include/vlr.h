@@ -392,6 +392,27 @@ int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, 
 int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                              const void* x_in, const int* pos, const int* key_mask, int batch, int S,
                              int keep_for_backward, vlr_stream_t stream);
+/* Row-compact no-grad layer (additive entry point: vlr_abi_version() does not move).  A DPO batch is [chosen ; rejected] and the two
+ * sequences of a pair share their prompt (and image): attention is causal and every other operator of the layer is row-wise, so in
+ * every layer the rejected sequence's prompt rows repeat the chosen sequence's.  The caller keeps Mc <= batch * S rows:
+ *   compact_rows [Mc]         int32, ascending: the dense row (b * S + s) each kept row stands at;
+ *   dense_src    [batch * S]  int32: for every dense row the kept row that holds its value (a dropped row names its twin), < Mc;
+ *   pos_compact  [Mc]         the positions of the kept rows.
+ * x_in and every tensor of `a` hold Mc rows, except a->lse, which stays [batch][heads][align64(S)].  qkv_dense [batch * S][Nq + 2 Nkv]
+ * and attn_dense [batch * S][Nq] are scratch: the q|k|v rows are expanded through dense_src, vlr_attn_fwd_gqa runs on the dense
+ * layout with the dense key_mask exactly as in vlr_decoder_layer_fwd_ex, and its rows are compacted again through compact_rows.
+ * keep_for_backward = 0 semantics (a->gu is not written).
+ * tail_rows: how many of the LAST dense rows are kept (the compact rows Mc - tail_rows .. Mc - 1 are the dense rows
+ * batch * S - tail_rows .. batch * S - 1).  The residual projections of the dense pass run their last vlr_gemm_peel_rows(batch * S, hidden)
+ * rows on the 128x128 split-K kernel, whose fp32 sums are formed in another order than the persistent kernel's; when these rows lie
+ * inside the kept tail the compact pass peels exactly them, every row is computed by the kernel the dense pass computes it in, and
+ * the kept rows of x_out equal vlr_decoder_layer_fwd_ex's bit for bit.  Otherwise the launches split as their own row count suggests
+ * and rows near the end may differ in their fp32 summation order. */
+int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a, const void* x_in,
+                                  const int* pos_compact, const int* dense_src, const int* compact_rows, int Mc, int tail_rows,
+                                  void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S, vlr_stream_t stream);
+/* rows the plain GEMM launch of [M x N] (vlr_gemm_bf16, vlr_gemm_bf16_f32res) hands to the 128x128 split-K kernel: its last rows; 0: none */
+int vlr_gemm_peel_rows(int M, int N);
 int vlr_decoder_layer_bwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g,
                           int accumulate, const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const void* x_in,
                           const void* dx_out, void* dx_in, const int* pos, const int* key_mask, int batch, int S,

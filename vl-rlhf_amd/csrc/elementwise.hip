@@ -628,8 +628,21 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restri
                                                           bf16_t* __restrict__ dst, int R, int H) {
     const int r = blockIdx.x;
     const size_t s = (size_t)rows[r] * H;
-    for (int c = threadIdx.x * 8; c < H; c += 256 * 8)
-        *reinterpret_cast<u32x4*>(dst + (size_t)r * H + c) = *reinterpret_cast<const u32x4*>(src + s + c);
+    // four 16-byte loads in flight per thread before the first store: rows wider than one pass of the workgroup (the 12288-wide q|k|v
+    // rows of the row-compact reference pass, fp32 residual rows) would otherwise wait for each load in turn
+    for (int c0 = threadIdx.x * 8; c0 < H; c0 += 4 * 256 * 8) {
+        u32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 256 * 8;
+            if (c < H) v[j] = *reinterpret_cast<const u32x4*>(src + s + c);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 256 * 8;
+            if (c < H) *reinterpret_cast<u32x4*>(dst + (size_t)r * H + c) = v[j];
+        }
+    }
 }
 __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16_t* __restrict__ src, const int* __restrict__ rows,
                                                            bf16_t* __restrict__ dst, int R, int H) {

@@ -681,6 +681,27 @@ static int choose_peel(int M, int N, int tn, int K = 0, hipStream_t stream = nul
     return peel;
 }
 
+// rows the plain [M x N] launch (gemm_impl_ex) gives to the 128x128 kernel: its last tile rows, split along K there - the rows of a
+// batch whose fp32 sums are formed in another order than in the persistent kernel.  0: none
+extern "C" int vlr_gemm_peel_rows(int M, int N) {
+    if (M <= 0 || N <= 0) return 0;
+    const int tm256 = (M + 255) / 256;
+    const int peel = choose_peel(M, N, (N + 255) / 256);
+    return peel ? M - (tm256 - peel) * 256 : 0;
+}
+// >= 0: the next plain launches of this thread give exactly their LAST t_peel_rows rows to the 128x128 kernel (0: none) instead of what
+// choose_peel picks for their own M - the row-compact layer pass (layers.cpp) keeps every row in the kernel the dense pass computes
+// it in, so that both passes round alike
+static thread_local int t_peel_rows = -1;
+int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
+                               hipStream_t st) {
+    t_peel_rows = peel_rows;
+    const int rc = f32 ? gemm_impl_ex(0, a, W, y, nullptr, res, M, N, K, K, K, N, N, 0, 0, 1, 1.0f, 1, st)       // = vlr_gemm_bf16_f32res
+                       : gemm_impl(0, a, W, y, nullptr, res, M, N, K, K, K, N, N, 0, 0, 0, 1.0f, st);            // = vlr_gemm_bf16
+    t_peel_rows = -1;
+    return rc;
+}
+
 extern "C" int vlr_gemm_bf16(int layout, const void* A, const void* B, void* C, const void* bias, const void* residual,
                              int M, int N, int K, int lda, int ldb, int ldc, int ldr, int act, int accumulate,
                              int out_f32, hipStream_t stream) {
@@ -820,9 +841,13 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     const int tm256 = (M + 255) / 256, tn256 = (N + 255) / 256;
     // (launches that take the per-tile kernel - bias, activation, accumulate, a bf16 residual - cannot use the stream-K tail: peel as before)
     const bool sk_elig = !bias && !accumulate && act == ACT_NONE && (out_f32 || !residual);
-    const int peel = choose_peel(M, N, tn256, sk_elig ? K : 0, stream);
+    int peel = choose_peel(M, N, tn256, sk_elig ? K : 0, stream);
+    int M1 = (tm256 - peel) * 256;
+    if (t_peel_rows >= 0) {       // the caller names the peeled rows (vlr_internal_gemm_res_peel)
+        peel = t_peel_rows > 0 && t_peel_rows < M;
+        M1 = M - t_peel_rows;
+    }
     if (peel) {
-        const int M1 = (tm256 - peel) * 256;
         GemmParams p1 = p, p2 = p;
         p1.M = M1;
         p2.M = M - M1;

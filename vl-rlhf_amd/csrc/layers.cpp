@@ -68,6 +68,44 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
     CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
     return VLR_OK;
 }
+// Row-compact no-grad layer (keep_for_backward = 0 semantics): the row-wise operators run on the Mc kept rows of a batch whose other rows
+// duplicate a kept one (the shared prompt of a DPO pair: causal attention makes the rejected sequence's prompt rows equal the chosen
+// sequence's in every layer).  Attention alone sees the dense [batch * S] layout, rebuilt by a row copy through dense_src and compacted
+// again through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
+int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
+                               hipStream_t st);      // gemm.hip: proj_res with the rows of the 128x128 kernel named by the caller
+extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                             const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
+                                             int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
+                                             int S, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && a && x_in && pos_compact && dense_src && compact_rows && qkv_dense && attn_dense,
+                "vlr_decoder_layer_fwd_compact: null argument");
+    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
+    VLR_REQUIRE(batch > 0 && S > 0 && Mc > 0 && Mc <= M, "vlr_decoder_layer_fwd_compact: %d compact rows of %d x %d dense rows", Mc, batch, S);
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    VLR_REQUIRE(tail_rows >= 0 && tail_rows <= Mc, "vlr_decoder_layer_fwd_compact: %d tail rows of %d compact rows", tail_rows, Mc);
+    const int rf = cfg->resid_f32;
+    // the two residual projections give their last tile rows to the 128x128 split-K kernel, which sums in another order than the
+    // persistent kernel: the rows the DENSE launch peels are peeled here too (they are the last rows of both layouts when they lie
+    // inside the kept tail), no others - each row is computed by the kernel the dense pass computes it in.  A dense peel that reaches
+    // into dropped rows cannot be reproduced: the launch then splits as its own row count suggests
+    const int dense_peel = vlr_gemm_peel_rows(M, H);
+    const int peel_rows = dense_peel <= tail_rows ? dense_peel : -1;
+    CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, Mc, H, cfg->rms_eps, st));
+    CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H,
+                                 cfg->head_dim, cfg->max_pos, st));
+    CHECK(vlr_gather_rows(a->qkv, dense_src, qkv_dense, M, N, st));              // dense row m = compact row dense_src[m]
+    CHECK(vlr_attn_fwd_gqa(qkv_dense, off(qkv_dense, Nq), off(qkv_dense, (size_t)Nq + Nkv), N, attn_dense, Nq, a->lse, key_mask, batch, S,
+                           cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    CHECK(vlr_gather_rows(attn_dense, compact_rows, a->attn, Mc, Nq, st));       // compact row j = dense row compact_rows[j]
+    CHECK(vlr_internal_gemm_res_peel(rf, a->attn, w->wo, a->x_mid, x_in, Mc, H, Nq, peel_rows, st));
+    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, Mc, H, cfg->rms_eps, st));
+    CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, Mc, I, H, H, 0, st));
+    CHECK(vlr_internal_gemm_res_peel(rf, a->act, w->wdown, a->x_out, a->x_mid, Mc, H, I, peel_rows, st));
+    return VLR_OK;
+}
 extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                                      const void* x_in, const int* pos, const int* key_mask, int batch, int S,
                                      vlr_stream_t st) {

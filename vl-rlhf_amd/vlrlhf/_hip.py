@@ -133,6 +133,7 @@ _SIGS = {
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],
     "vlr_decoder_layer_fwd_ex": [P, P, P, P, P, P, I, I, I, P],
+    "vlr_decoder_layer_fwd_compact": [P, P, P, P, P, P, P, I, I, P, P, P, I, I, P],
     "vlr_gemm_swiglu": [P, P, P, P, I, I, I, I, I, P],
     "vlr_gemm_swiglu_bwd": [P, P, P, P, I, I, I, P],
     "vlr_gemm_qkv_rope": [P, P, P, P, P, P, I, I, I, I, I, I, I, P],
@@ -198,6 +199,7 @@ _INT_HELPERS = {
     "vlr_colsum_workspace_bytes": [I],
     "vlr_grad_sqnorm_workspace_bytes": [],
     "vlr_abi_version": [],
+    "vlr_gemm_peel_rows": [I, I],
     "vlr_prof_enable": [I],
     "vlr_prof_collect": [P, I],
     "vlr_gemm_set_splitk_workspace": [P, L],

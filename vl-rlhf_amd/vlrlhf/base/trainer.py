@@ -758,12 +758,18 @@ class VLDPOTrainer(VLTrainerLoop):
         if self.ref_model is None:
             if not self.is_peft_model:
                 raise ValueError("no reference model and no precomputed reference log-probs in the batch")
-            with torch.no_grad(), self.null_ref_context():
+            with torch.no_grad(), self.null_ref_context(), self._reference_pass(self.model):
                 rc, rr, _, _ = self.concatenated_forward(self.model, batch)
             return rc, rr
-        with torch.no_grad():
+        with torch.no_grad(), self._reference_pass(self.ref_model):
             rc, rr, _, _ = self.concatenated_forward(self.ref_model, batch)
         return rc, rr
+
+    @staticmethod
+    def _reference_pass(owner):
+        """a reference forward reads nothing but its log-probs: models that can skip the duplicate prompt rows of each pair
+        (LlavaForRL.reference_pass) are told so for the duration of the call"""
+        return owner.reference_pass() if hasattr(owner, "reference_pass") else contextlib.nullcontext()
 
     def null_ref_context(self):
         """trl==0.8.1 DPOTrainer.null_ref_context: the peft policy with its adapters disabled is the reference model."""
@@ -890,13 +896,14 @@ class VLDPOTrainer(VLTrainerLoop):
         before the first optimizer step, so these are the initial weights."""
         with torch.no_grad():
             if self.ref_model is None:
-                with self.null_ref_context():
+                with self.null_ref_context(), self._reference_pass(self.model):
                     was_training = self.model.training
                     self.model.eval()
                     rc, rr, _, _ = self.concatenated_forward(self.model, padded_batch)
                     self.model.train(was_training)
             else:
-                rc, rr, _, _ = self.concatenated_forward(self.ref_model, padded_batch)
+                with self._reference_pass(self.ref_model):
+                    rc, rr, _, _ = self.concatenated_forward(self.ref_model, padded_batch)
         return rc, rr
 
     def precompute_reference_log_probs(self, dataset, batch_size: Optional[int] = None):

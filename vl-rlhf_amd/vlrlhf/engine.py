@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _hip, gptq
+from . import _hip, gptq, prefix_dedup
 
 BF16 = torch.bfloat16
 
@@ -462,6 +462,7 @@ class LlavaHipEngine:
     supports_ckpt = True           # False: the backward cannot re-run a layer's forward (read per pass by forward_hidden: checkpointing is ignored)
     proj_out_f32 = True            # with the fp32 stream the projector writes fp32 rows for the merge (False in a subclass: bf16)
     supports_kv_cache = True       # generate(use_cache=True): prefill into a KVCache + decode_step (vlr_decoder_layer_decode)
+    row_compact_layers = True      # the adapter-free no-grad layer is vlr_decoder_layer_fwd_ex: forward_hidden(prefix_dedup=True) may run its row-compact twin
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
         if not torch.cuda.is_available():
@@ -521,6 +522,11 @@ class LlavaHipEngine:
         self.neftune = None                      # dict(alpha, key) between set_neftune(alpha, ...) and set_neftune(None)
         self._neftune_calls = 0                  # noisy passes so far: the `call` word of the noise counter (checkpointed)
         self.last_neftune = None                 # (key, call, pass, T, scale) of the last noisy pass (tests replay the noise from it)
+        # the reference pass computes each DPO pair's shared prompt rows once (forward_hidden(prefix_dedup=True), prefix_dedup.py)
+        self.prefix_dedup = True                 # False: every pass is the dense one (the A/B switch)
+        self.prefix_dedup_min_share = 1.0 / 8    # taken when the shared rows are at least this share of the M dense rows: below it the row copies cost what the GEMMs save
+        self.prefix_dedup_passes = 0             # row-compact passes so far
+        self.last_prefix_dedup = None            # dict(P, Mc, M) of the last row-compact pass
         self._norm_ws = torch.empty(_hip.helper("vlr_rmsnorm_bwd_workspace_bytes", self.H), dtype=torch.uint8, device=self.dev)
         self._colsum_ws = torch.empty(_hip.helper("vlr_colsum_workspace_bytes", max(self.H, self.Nqkv, 8)), dtype=torch.uint8, device=self.dev)
         self._sq_ws = torch.empty(_hip.helper("vlr_grad_sqnorm_workspace_bytes"), dtype=torch.uint8, device=self.dev)
@@ -938,11 +944,58 @@ class LlavaHipEngine:
         return dict(S=S, M=M, src=src, mask=mask, pos=pos, labels=mlabels, img_map=img_map, inv=inv, feats=feats, vit_feat=vit_feat,
                     proj_z=z, proj_h=h, n_rows=n_rows, n_feat=n_feat, pack=pack)
 
+    def _prefix_plan(self, e, ids, Bn, meta):
+        """the row maps of a row-compact pass over this [chosen ; rejected] batch (prefix_dedup.py), or None when the shared prompt rows
+        are too few to pay for the row copies.  Cached on the batch (`meta`): one small D2H read per new batch."""
+        if meta is not None and "prefix_dedup" in meta:
+            plan = meta["prefix_dedup"]
+        else:
+            S, M = e["S"], e["M"]
+            src, mask, pos = (e[k].reshape(Bn, S) for k in ("src", "mask", "pos"))
+            P = prefix_dedup.shared_prefix_lengths(prefix_dedup.source_key(src, ids), mask, pos).tolist()
+            rows, dsrc = prefix_dedup.build_row_maps(P, S)
+            rows, dsrc = rows.to(self.dev), dsrc.to(self.dev)
+            # tail: the last dense rows, all kept (the rows past the last pair's shared prefix) - vlr_decoder_layer_fwd_compact
+            plan = dict(P=P, shared=sum(P), M=M, Mc=M - sum(P), tail=S - P[-1], compact_rows=rows, dense_src=dsrc,
+                        pos=pos.reshape(-1)[rows.long()].contiguous())
+            if meta is not None:
+                meta["prefix_dedup"] = plan
+        if plan["shared"] == 0 or plan["shared"] < self.prefix_dedup_min_share * plan["M"]:
+            return None
+        return plan
+
+    def _forward_layers_compact(self, ws, e, plan, x0, Bn, S, tag):
+        """the decoder layers and the final norm of a no-grad pass on the kept rows of `plan`; -> (hidden [M, H] dense, rstd_f, x_last)
+        The activation set is the pass's dense scratch set (its first Mc rows; lse keeps its dense shape); q|k|v and the attention
+        output also exist densely, for vlr_attn_fwd_gqa alone."""
+        M, Mc, H = plan["M"], plan["Mc"], self.H
+        rows, dsrc = plan["compact_rows"], plan["dense_src"]
+        w16 = 2 if x0.dtype == torch.float32 else 1                  # (row copy: fp32 rows = 2H 16-bit columns)
+        x = self._buf((tag, "dedup_x0", Bn, S), (M, H), x0.dtype)
+        _hip.call("vlr_gather_rows", x0, rows, x, Mc, H * w16)
+        qkv_d = self._buf((tag, "dedup_qkv", Bn, S), (M, self.Nqkv))
+        attn_d = self._buf((tag, "dedup_attn", Bn, S), (M, self.Nq))
+        for l in range(self.L):
+            a = self._layer_acts(tag + "/scratch", l % 2, Bn, S)
+            _hip.call("vlr_decoder_layer_fwd_compact", self.llama_cfg, self.layer_weights(ws, l, tag), a["struct"], x, plan["pos"], dsrc, rows,
+                      Mc, plan["tail"], qkv_d, attn_d, e["mask"], Bn, S)
+            x = a["x_out"]
+        hidden_c = self._buf((tag, "dedup_hidden", Bn, S), (M, H))
+        rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
+        self._norm_fwd(x, ws.v["norm"], hidden_c, rstd_f, Mc)
+        hidden = torch.empty(M, H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_gather_rows", hidden_c, dsrc, hidden, M, H)
+        self.prefix_dedup_passes += 1
+        self.last_prefix_dedup = dict(P=list(plan["P"]), Mc=Mc, M=M)
+        return hidden, rstd_f, x
+
     def forward_hidden(self, ws: WeightSet, input_ids, attention_mask, labels, pixel_values, image_dup=1, save=False,
-                       tag="ref", image_sizes=None, kv_cache: Optional[KVCache] = None):
+                       tag="ref", image_sizes=None, kv_cache: Optional[KVCache] = None, prefix_dedup_rows=False):
         """embed -> ViT -> projector -> merge -> decoder -> final RMSNorm.  Returns a context dict with the final
         hidden states [Bn*S, H] and the merged labels / mask / positions.  kv_cache (generate's prefill, no-grad, engines with
-        supports_kv_cache): each layer's post-RoPE K / V rows are copied into it right after the layer ran."""
+        supports_kv_cache): each layer's post-RoPE K / V rows are copied into it right after the layer ran.
+        prefix_dedup_rows (the trainer's reference passes): a no-grad pass over a [chosen ; rejected] batch (image_dup == 2) computes the
+        rows of each pair's shared prompt once (_prefix_plan) - the context keeps its dense contract, ctx["x_last"] alone is compact."""
         c = self.cfg
         if ws is self.policy:
             self.wait_optimizer()
@@ -986,7 +1039,13 @@ class LlavaHipEngine:
             self._lora_calls += 1
             lora_seed = (self.lora_seed << 40) + (self._lora_calls << 16)        # + 8*layer + target inside the library
         ckpt = bool(save and self.gradient_checkpointing and self.supports_ckpt)      # (layers composed in Python keep their activations)
-        for l in range(self.L):
+        plan = None
+        if (prefix_dedup_rows and self.prefix_dedup and self.row_compact_layers and not save and kv_cache is None and image_dup == 2
+                and not use_lora and Bn % 2 == 0):
+            plan = self._prefix_plan(e, ids, Bn, meta)
+        if plan is not None:
+            hidden, rstd_f, x = self._forward_layers_compact(ws, e, plan, x0, Bn, S, tag)
+        for l in range(self.L if plan is None else 0):
             if ckpt:
                 a = self._ckpt_acts(tag, l, Bn, S)
             else:
@@ -999,9 +1058,10 @@ class LlavaHipEngine:
                           Bn, S, self.nkv, self.hd, kv_cache.cap, 0)
             acts.append(a)
             x = a["x_out"]
-        hidden = torch.empty(M, self.H, dtype=BF16, device=self.dev)
-        rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
-        self._norm_fwd(x, ws.v["norm"], hidden, rstd_f, M)
+        if plan is None:
+            hidden = torch.empty(M, self.H, dtype=BF16, device=self.dev)
+            rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
+            self._norm_fwd(x, ws.v["norm"], hidden, rstd_f, M)
         if kv_cache is not None:
             kv_cache.start(mask.view(Bn, S))
         return dict(ws=ws, Bn=Bn, T=T, S=S, M=M, ids=ids, src=src, inv=inv, mask=mask, labels=mlabels, pos=pos,

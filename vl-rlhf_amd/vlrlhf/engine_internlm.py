@@ -33,6 +33,7 @@ PLORA_SEED_XOR = 0x2A5A5A5A5A
 
 class InternLMHipEngine(LlavaHipEngine):
     supports_kv_cache = False      # the PLoRA layers are composed per pass (image rows): generate re-runs the forward
+    row_compact_layers = False     # the row-compact reference pass (forward_hidden(prefix_dedup_rows=True)) is not wired to this engine: dense passes only
     vision_prefix = "vit.vision_tower."
 
     @property

@@ -96,6 +96,7 @@ class QwenVisionWeights:
 class QwenVLHipEngine(LlavaHipEngine):
     vision_prefix = "transformer.visual."
     supports_kv_cache = False      # generation inputs (image ids inside the text) not wired to the cache yet: generate re-runs the forward
+    row_compact_layers = False     # the row-compact reference pass (forward_hidden(prefix_dedup_rows=True)) is not wired to this engine: dense passes only
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
         c = dict(cfg, family="qwen_vl")

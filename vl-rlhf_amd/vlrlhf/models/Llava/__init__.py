@@ -388,6 +388,17 @@ class LlavaForRL(nn.Module):
         finally:
             self.engine.lora_active = prev
 
+    @contextlib.contextmanager
+    def reference_pass(self):
+        """the trainer's reference forwards run inside: a no-grad forward over a [chosen ; rejected] batch may then compute each pair's
+        shared prompt rows once (engine.forward_hidden(prefix_dedup_rows=True)); its log-probs are all anyone reads from such a pass"""
+        prev = getattr(self, "_reference_pass", False)
+        self._reference_pass = True
+        try:
+            yield
+        finally:
+            self._reference_pass = prev
+
     def lora_state_dict(self):
         self.engine.wait_optimizer()
         return self.engine.lora_state_dict()
@@ -687,7 +698,7 @@ class LlavaForRL(nn.Module):
         else:
             c = self.engine.forward_hidden(self.weights, input_ids, attention_mask, labels, pixel_values, image_dup=dup,
                                            save=False, tag="policy_ng" if self.weights is self.engine.policy else "ref",
-                                           image_sizes=image_sizes)
+                                           image_sizes=image_sizes, prefix_dedup_rows=bool(getattr(self, "_reference_pass", False)))
             hidden = c["hidden"]
         out_labels = c["labels"] if labels is not None else torch.full_like(c["mask"], -100, dtype=torch.long)
         if c.get("meta") is not None:

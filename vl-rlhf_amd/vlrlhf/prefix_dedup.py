@@ -1,0 +1,53 @@
+"""Row maps of the row-compact reference pass (LlavaHipEngine.forward_hidden(prefix_dedup=True)).
+
+A DPO batch is concatenated as [chosen 0..B-1 ; rejected 0..B-1].  The two sequences of pair i are `prompt + chosen` and
+`prompt + rejected` padded on the right, so their MERGED sequences (text tokens and image feature slots) agree on a prefix of P_i
+positions: same source, same attention mask, same position id.  Attention is causal and every other operator of a decoder layer works
+row by row, so in every layer the rejected sequence's first P_i rows repeat the chosen sequence's.  A no-grad pass keeps one copy:
+
+    compact_rows [M']   the kept dense rows (b * S + s), ascending: every chosen row, then the rows s >= P_i of every rejected sequence
+    dense_src    [M]    for every dense row the compact row that holds its value (a dropped row names its chosen twin)
+
+Pure tensor code: runs on CPU tensors (tests/test_prefix_dedup_host.py) and on the device tensors of the engine alike."""
+from typing import Sequence, Tuple
+
+import torch
+
+
+def source_key(src: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """What every merged position is built from, comparable across batch rows: src [Bn, S] is the merge map of vlr_merge_index
+    (>= 0: index of a text token in its own row of ids [Bn, T]; < 0: an image feature slot of the deduplicated feature table, or
+    the all-zero row).  -> int64 [Bn, S]: the token ID of a text slot (>= 0), the slot code itself otherwise (< 0)."""
+    s = src.long()
+    tok = torch.gather(ids.long(), 1, s.clamp(min=0))
+    return torch.where(s >= 0, tok, s)
+
+
+def shared_prefix_lengths(key: torch.Tensor, mask: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """P_i of the B pairs of a [chosen ; rejected] batch ([2B, S] each): the longest common prefix of the two merged sequences with
+    equal source key, mask and position.  0 <= P_i <= S (P_i = S: the pair's sequences are identical).  -> int64 [B]"""
+    if key.dim() != 2 or key.shape[0] % 2 or key.shape != mask.shape or key.shape != pos.shape:
+        raise ValueError(f"shared_prefix_lengths: [2B, S] tensors expected, got {tuple(key.shape)}, {tuple(mask.shape)}, {tuple(pos.shape)}")
+    B = key.shape[0] // 2
+    eq = (key[:B] == key[B:]) & (mask[:B] == mask[B:]) & (pos[:B] == pos[B:])
+    return eq.long().cumprod(dim=1).sum(dim=1)
+
+
+def build_row_maps(P: Sequence[int], S: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(compact_rows int32 [M - sum P], dense_src int32 [M]) of B = len(P) pairs of S merged positions, M = 2 B S; CPU tensors.
+    Invariants: compact_rows is strictly ascending and holds every chosen row; dense_src[compact_rows[j]] == j; the dropped row
+    (B + i) * S + s, s < P_i, maps to the compact row of the chosen row i * S + s."""
+    P = [int(p) for p in P]
+    B = len(P)
+    if B < 1 or S < 1 or any(p < 0 or p > S for p in P):
+        raise ValueError(f"build_row_maps: prefix lengths {P} outside 0 .. S = {S}")
+    s = torch.arange(S).unsqueeze(0)
+    keep = torch.ones(2 * B, S, dtype=torch.bool)
+    keep[B:] = s >= torch.tensor(P).unsqueeze(1)
+    flat = keep.reshape(-1)
+    compact_rows = torch.nonzero(flat).reshape(-1)
+    index = torch.cumsum(flat.long(), 0) - 1                   # compact index of a KEPT dense row
+    twin = torch.arange(2 * B * S).reshape(2 * B, S)
+    twin[B:] = torch.where(keep[B:], twin[B:], twin[:B])       # a dropped rejected row reads its chosen twin
+    dense_src = index[twin.reshape(-1)]
+    return compact_rows.int(), dense_src.int()
