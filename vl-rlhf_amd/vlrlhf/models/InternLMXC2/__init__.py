@@ -94,8 +94,12 @@ class InternLMXC2ForRL(LlavaForRL):
         self._vision_frozen = True
 
     def prepare_default_generation_kwargs(self, generation_config):
+        """reference :257-263.  Its KeywordsStoppingCriteria([92542], 2) ends a row at the end-of-turn id [UNUSED_TOKEN_145] and
+        overwrites that id with the pad id in place; here the row ends through stop_words_ids, the id stays in the output and
+        batch_decode(skip_special_tokens=True) removes it: the same text."""
         generation_config.do_sample = False
         generation_config.eos_token_id = 2
+        generation_config.stop_words_ids = [[92542]]
         return dict(generation_config=generation_config)
 
     ce_selects_by_mask = False     # reference :211-219 shifts without the attention mask: the label alone selects a row

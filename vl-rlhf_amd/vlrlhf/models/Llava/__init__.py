@@ -221,6 +221,27 @@ def sampling_filter(logits, temperature=1.0, top_k=50, top_p=1.0):
     return logits
 
 
+def stop_sequences(stop_words_ids, device):
+    """generation_config.stop_words_ids (a list of token-id lists; Qwen-VL's generation config, InternLM-XComposer2's end-of-turn id) ->
+    one 1-D id tensor per non-empty sequence on `device`, uploaded once per generate call"""
+    if not stop_words_ids:
+        return []
+    if isinstance(stop_words_ids[0], int):
+        raise ValueError(f"stop_words_ids must be a list of token-id lists, got {stop_words_ids}")
+    return [torch.tensor([int(x) for x in s], dtype=torch.long, device=device) for s in stop_words_ids if len(s)]
+
+
+def stop_hit(generated, stops):
+    """bool [B]: rows whose GENERATED tokens ([B, n], the prompt never counts) end with one of `stops`.  Tensor compares of the last k
+    columns on the device; nothing is read back."""
+    hit = torch.zeros(generated.shape[0], dtype=torch.bool, device=generated.device)
+    for s in stops:
+        k = s.numel()
+        if generated.shape[1] >= k:
+            hit = hit | (generated[:, -k:] == s).all(1)
+    return hit
+
+
 class LlavaForRL(nn.Module):
     engine_cls = LlavaHipEngine
 
@@ -494,7 +515,14 @@ class LlavaForRL(nn.Module):
             of P * n rows over the shared prompt K / V plus each sample's own tail (engine.decode_step -> vlr_decoder_layer_decode_shared):
             one prefill, one copy of the prompt's K / V, one read of it per token;
           n > 1 otherwise (use_cache=False, Qwen-VL, InternLM-XComposer2, other head dims): ids, mask and every image input are expanded
-            by repeat_interleave(n) and the loop above runs on P * n rows - nothing is shared."""
+            by repeat_interleave(n) and the loop above runs on P * n rows - nothing is shared.
+
+        Stop rules of a `generation_config` (each read with getattr(..., None); a call that passes none of them is unchanged):
+          eos_token_id (int or list; the keyword wins), pad_token_id (the keyword wins), and stop_words_ids, a list of token-id lists: a
+          row is finished once the tokens GENERATED in this call end with one of the sequences (the prompt never counts).  The stop
+          tokens stay in the output and later positions receive the pad id, as after an eos.  Both routes and every fan-out check it with
+          tensor compares of the last k generated tokens (stop_hit): no host synchronisation beyond the loop's `unfinished.any()`."""
+        stop_words = None
         if generation_config is not None:
             max_new_tokens = max_new_tokens if max_new_tokens is not None else getattr(generation_config, "max_new_tokens", None)
             do_sample = bool(getattr(generation_config, "do_sample", do_sample))
@@ -502,6 +530,11 @@ class LlavaForRL(nn.Module):
             nrs = getattr(generation_config, "num_return_sequences", None)
             if nrs is not None and num_return_sequences == 1:
                 num_return_sequences = nrs
+            if eos_token_id is None:                      # an explicit keyword wins
+                eos_token_id = getattr(generation_config, "eos_token_id", None)
+            if pad_token_id is None:
+                pad_token_id = getattr(generation_config, "pad_token_id", None)
+            stop_words = getattr(generation_config, "stop_words_ids", None)
         fanout = int(num_return_sequences)
         if fanout < 1:
             raise ValueError(f"num_return_sequences has to be a positive integer, got {num_return_sequences}")
@@ -523,14 +556,16 @@ class LlavaForRL(nn.Module):
         eos = eos_token_id if eos_token_id is not None else self.config.get("eos_token_id", 2)
         eos = set(eos) if isinstance(eos, (list, tuple)) else {int(eos)}
         pad = int(pad_token_id if pad_token_id is not None else 0)
+        stops = stop_sequences(stop_words, dev)
         img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
         was_training = self.training
         self.eval()
         lm_head = self.weights.v["lm_head"]
         if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
-            try:
+            try:        # (fanout / stops are passed only when set: a call without them is today's call, argument for argument)
                 return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img,
-                                             self.cached_lora_route(merge_lora), **({"fanout": fanout} if fanout > 1 else {}))
+                                             self.cached_lora_route(merge_lora), **({"fanout": fanout} if fanout > 1 else {}),
+                                             **({"stops": stops} if stops else {}))
             finally:
                 self.train(was_training)
         if fanout > 1:      # no shared cache on this route: the transformers expansion, sample j of prompt p at row p * n + j
@@ -558,6 +593,8 @@ class LlavaForRL(nn.Module):
                 mask = torch.cat([mask, torch.ones(B, 1, dtype=mask.dtype, device=dev)], 1)
                 for e in eos:
                     unfinished = unfinished & (nxt != e)
+                if stops:                     # the stop tokens stay in the row; from the next position on it receives the pad id
+                    unfinished = unfinished & ~stop_hit(ids[:, T0:], stops)
         finally:
             self.train(was_training)
         return ids
@@ -593,9 +630,10 @@ class LlavaForRL(nn.Module):
             return "plain"
         return "merged" if (merge_lora and not self.is_packed) else "live"
 
-    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, fanout=1):
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, fanout=1, stops=()):
         """generate's KV-cache path: the prefill is the first iteration of the re-forward loop (same padded input, same lm-head
         call) with the K / V rows kept; each further token is one engine.decode_step.  route: cached_lora_route().
+        stops: stop_sequences() of the generation config - a row whose generated tokens end with one is finished (stop_hit).
         fanout > 1 (num_return_sequences): the prefill fills the prompt segment of a SharedPromptKVCache, its logits are repeated
         `fanout` times and the B * fanout samples decode over the shared prompt K / V."""
         eng, dev = self.engine, self.engine.dev
@@ -630,6 +668,9 @@ class LlavaForRL(nn.Module):
             logits = logits.repeat_interleave(fanout, 0)
             out = [ids.repeat_interleave(fanout, 0)]
         n = T
+        if stops:
+            keep = max(s.numel() for s in stops)
+            tail = torch.empty(B * fanout, 0, dtype=torch.long, device=dev)
         while True:
             if do_sample:
                 nxt = torch.multinomial(sampling_filter(logits, temperature, top_k, top_p).softmax(-1), 1, generator=generator).squeeze(1)
@@ -640,6 +681,9 @@ class LlavaForRL(nn.Module):
             n += 1
             for e in eos:
                 unfinished = unfinished & (nxt != e)
+            if stops:                         # the last tokens GENERATED so far (never the prompt's) against every stop sequence
+                tail = torch.cat([tail, nxt[:, None]], 1)[:, -keep:]
+                unfinished = unfinished & ~stop_hit(tail, stops)
             if n >= limit or not bool(unfinished.any()):
                 break
             logits = eng.decode_step(ws, nxt, cache)

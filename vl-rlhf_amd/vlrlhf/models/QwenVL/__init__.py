@@ -132,6 +132,16 @@ class QwenVLForRL(LlavaForRL):
         generation_config.do_sample = False
         return dict(generation_config=generation_config)
 
+    def generate(self, input_ids=None, *args, pixel_values=None, **kw):
+        """LlavaForRL.generate; the image files named in the prompt ids are opened once per call, not once per re-forwarded token.
+        Only when every row names exactly one image (pixel rows == prompt rows), which is what the num_return_sequences expansion of
+        `pixel_values` assumes; any other batch keeps the forward's own lookup per token."""
+        if pixel_values is None and input_ids is not None:
+            px = self._pixels_from_ids(input_ids)
+            if px is not None and px.shape[0] == input_ids.shape[0]:
+                pixel_values = px
+        return LlavaForRL.generate(self, input_ids, *args, pixel_values=pixel_values, **kw)
+
     def prefetch_vision(self, img_input_dict):
         pv = img_input_dict.get("pixel_values")
         if pv is not None:
