@@ -335,6 +335,20 @@ int vlr_lmhead_ce_bwd(const void* hg, const void* w_lm, const int* tgt, const fl
                       void* workspace, float* logits_ws, void* dhg, void* dw_lm, int dw_accumulate, int R, int V, int H, int row_block,
                       vlr_stream_t stream);
 
+/* ---- reward-model head (reference base/model.py VLRewardModel: rm_head = nn.Linear(hidden, 1) on hidden_states[-1][:, -1, :]; additive
+ *      entry points, vlr_abi_version() does not move).  hidden [*][ldh] bf16 = the final hidden states, rows[i] the row of reward i,
+ *      w [H] bf16, b [1] bf16.  H % 8 == 0, H >= 8, ldh / ldd multiples of 8 (16-byte loads).  No atomics.
+ * vlr_rm_head_fwd: rewards[i] = dot(hidden[rows[i]], w) + b, accumulated and written in fp32 (never rounded to bf16).  One workgroup per
+ *      row with a fixed reduction order: a row's reward has the same bits for every n and from call to call.
+ * vlr_rm_head_bwd: dhidden[rows[i]] = bf16(d_rewards[i] * w) - no other row of dhidden is touched (the caller zeroes it), `rows` must
+ *      not repeat; dw[h] = sum_i d_rewards[i] * hidden[rows[i]][h] and db = sum_i d_rewards[i], both in fp32 in the order of i and
+ *      rounded once into the bf16 gradient buffers - with `accumulate` the old value is added in fp32 before that one rounding.
+ * The pair loss -logsigmoid(r_chosen - r_rejected) is vlr_dpo_loss(beta 1, label_smoothing 0, loss_type 0, reference_free 1). */
+int vlr_rm_head_fwd(const void* hidden, int ldh, const int* rows, const void* w, const void* b, float* rewards, int n, int H,
+                    vlr_stream_t stream);
+int vlr_rm_head_bwd(const void* hidden, int ldh, const int* rows, const void* w, const float* d_rewards, void* dhidden, int ldd,
+                    void* dw, void* db, int accumulate, int n, int H, vlr_stream_t stream);
+
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d
  * policy_{chosen,rejected}_logps with g = grad_losses or 1/len(losses) when NULL (trl: loss = losses.mean()). */

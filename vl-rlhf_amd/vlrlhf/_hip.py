@@ -129,6 +129,8 @@ _SIGS = {
     "vlr_ce_mean_fwd": [P, I, P, P, P],
     "vlr_lmhead_ce_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vlr_dpo_loss": [P, P, P, P, I, F, F, I, I, P, P, P, P, P, P, P, P],
+    "vlr_rm_head_fwd": [P, I, P, P, P, P, I, I, P],
+    "vlr_rm_head_bwd": [P, I, P, P, P, P, I, P, P, I, I, I, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],

@@ -1,4 +1,4 @@
-"""DPO and SFT collators (mirror of the reference src/vlrlhf/base/collator.py:8-94)."""
+"""DPO, SFT and reward-model collators (mirror of the reference src/vlrlhf/base/collator.py:8-111)."""
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
@@ -67,6 +67,36 @@ class VLSFTDataCollatorWithPadding:
             elif k == "labels":
                 pad = self.label_pad_token_id
             elif k == "attention_mask":
+                pad = 0
+            else:
+                raise ValueError(f"Unexpected key in batch '{k}'")
+            n = max(len(f[k]) for f in features)
+            t = torch.full((len(features), n), pad, dtype=torch.long)
+            for i, f in enumerate(features):
+                v = torch.as_tensor(f[k], dtype=torch.long)
+                t[i, : v.numel()] = v
+            out[k] = t
+        return out
+
+
+@dataclass
+class VLRMDataCollatorWithPadding:
+    r"""reference :96-111: right-pads input_ids_* -> pad_token_id and attention_mask_* -> 0 (torch pad_sequence(batch_first=True)), each
+    key to its own width; any other key raises.  Deliberate difference: `img_path` is passed through as a list - the reference's
+    tokenize_row drops it, so as shipped only a model that reads the path out of the text ever sees its image."""
+
+    pad_token_id: int
+    processor: Optional[Any] = None
+
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        out: Dict[str, Any] = {}
+        for k in features[0].keys():
+            if k == "img_path":
+                out[k] = [f[k] for f in features]
+                continue
+            if k.startswith("input_ids"):
+                pad = self.pad_token_id
+            elif k.startswith("attention_mask"):
                 pad = 0
             else:
                 raise ValueError(f"Unexpected key in batch '{k}'")

@@ -1,4 +1,4 @@
-"""VLDPOTrainer and VLSFTTrainer for MI355X - mirror of /root/reference/src/vlrlhf/base/trainer.py:33-360 plus the parts of
+"""VLDPOTrainer, VLSFTTrainer and VLRMTrainer for MI355X - mirror of /root/reference/src/vlrlhf/base/trainer.py:33-360 plus the parts of
 trl==0.8.1 `DPOTrainer` and transformers `Trainer` the reference inherits on the DPO path (not vendored there:
 constructor bookkeeping, tokenize_row / build_tokenized_answer, concatenated_inputs, compute_loss /
 get_batch_loss_metrics, the step loop, clip + AdamW + cosine schedule).
@@ -1067,6 +1067,157 @@ class VLSFTTrainer(VLTrainerLoop):
         if prediction_loss_only:
             return loss.detach(), None, None
         return loss.detach(), outputs.logits, outputs.labels
+
+
+class VLRMTrainer(VLTrainerLoop):
+    """Reward-model training - mirror of the reference src/vlrlhf/base/trainer.py:502-570 plus what it inherits from trl==0.8.1
+    `RewardTrainer` on this path: loss = -logsigmoid(r_chosen - r_rejected).mean() (compute_loss), eval accuracy = the share of pairs
+    whose chosen reward is not below the rejected one (compute_accuracy: argmax over [r_chosen, r_rejected], ties to the first).
+
+    The reference runs chosen and rejected as two forwards, each padded to its own width, and reads every reward at the last column of
+    its batch.  Here both halves are ONE concatenated pass (as VLDPOTrainer.concatenated_forward: right-padded to the wider half, images
+    shared through `_vlr_dup`), each sequence's reward read at the last column of ITS OWN half: under right padding and causal
+    key-masked attention that row does not depend on the columns behind it, so the values are those of the two passes.  The pair loss
+    is vlr_dpo_loss with beta 1 and reference_free (the two reference arrays are zeros).  Deliberate difference: `img_path` is kept by
+    tokenize_row and images reach the model as they do in DPO.  NEFTune stays off on this path."""
+
+    def __init__(
+        self,
+        model=None,
+        args=None,
+        data_collator: Any = None,
+        train_dataset=None,
+        eval_dataset=None,
+        processor=None,
+        model_init: Optional[Callable] = None,
+        compute_metrics: Optional[Callable] = None,
+        callbacks: Optional[List] = None,
+        optimizers: Tuple = (None, None),
+        preprocess_logits_for_metrics: Optional[Callable] = None,
+        max_length: Optional[int] = None,
+        peft_config: Optional[Dict] = None,
+    ):
+        # argument order = reference base/trainer.py:503-518
+        if model is None:
+            raise ValueError("VLRMTrainer needs a model")
+        if not hasattr(model, "reward_rows"):
+            raise ValueError("VLRMTrainer needs a reward model (vlrlhf.base.model.VLRewardModel)")
+        if peft_config is not None:          # trl RewardTrainer.__init__: model = get_peft_model(model, peft_config)
+            model.apply_lora(peft_config)
+        self.is_peft_model = bool(getattr(model, "is_peft_model", False))
+        self.processor = processor
+        self.tokenizer = processor.tokenizer if processor is not None else None
+        self.model = model
+        self.args = args
+        self.max_length = max_length
+        pad = getattr(data_collator, "pad_token_id", None)
+        if pad is None and self.tokenizer is not None:
+            pad = self.tokenizer.pad_token_id
+        self.padding_value = int(pad) if pad is not None else 0
+        self.callbacks = list(callbacks or [])
+        self.use_reward_data_collator = True
+        self._stored_metrics = defaultdict(lambda: defaultdict(list))
+        self.log_history: List[dict] = []
+        self.accelerator = _Accelerator(model)
+        self.data_collator = data_collator
+        self.train_dataset = self._tokenize_dataset(train_dataset)
+        self.eval_dataset = self._tokenize_dataset(eval_dataset)
+        self.state = _State()
+
+    # ------------------------------------------------------------------------------------------ tokenisation
+    def _tokenize_dataset(self, ds):
+        if ds is None:
+            return None
+        rows = list(ds)
+        if rows and "input_ids_chosen" not in rows[0]:
+            rows = [self.tokenize_row(dict(r)) for r in rows]
+        return rows
+
+    def tokenize_row(self, element):
+        """reference :550-570, plus `img_path`"""
+        prompt = self.processor.format_multimodal_prompt(element["prompt"], element["img_path"])
+        out = {}
+        for side in ("chosen", "rejected"):
+            conv = self.processor.make_single_turn_conv(prompt, element[side])
+            full = self.processor.process_batch_conv([conv])["full"]
+            out[f"input_ids_{side}"] = full["input_ids"][0][: self.max_length]
+            out[f"attention_mask_{side}"] = full["attention_mask"][0][: self.max_length]
+        out["img_path"] = element["img_path"]
+        return out
+
+    # ------------------------------------------------------------------------------------------ loss
+    def concatenated_inputs(self, batch) -> Dict[str, Any]:
+        """[chosen ; rejected] right-padded to the wider half, every image input doubled (`_vlr_dup = 2`: the frozen tower sees each
+        distinct image once), and `reward_cols`: the last TOKEN column of each sequence's own half.  Memoised on the batch."""
+        src = tuple(id(batch.get(k)) for k in ("input_ids_chosen", "input_ids_rejected", "attention_mask_chosen",
+                                               "attention_mask_rejected", "img_input_dict"))
+        cache = batch.get("_vlr_rm_concat")
+        if cache is not None and cache["src"] == src:
+            return cache["out"]
+        dev = self.accelerator.device
+        ic, ir = batch["input_ids_chosen"], batch["input_ids_rejected"]
+        if ic.shape[0] != ir.shape[0]:
+            raise ValueError(f"{ic.shape[0]} chosen rows but {ir.shape[0]} rejected rows")
+        n = max(ic.shape[1], ir.shape[1])
+        ids = torch.cat([pad_to_length(ic, n, self.padding_value), pad_to_length(ir, n, self.padding_value)], dim=0).to(dev)
+        mask = torch.cat([pad_to_length(batch["attention_mask_chosen"], n, 0), pad_to_length(batch["attention_mask_rejected"], n, 0)], dim=0).to(dev)
+        ids._vlr_meta = {}
+        img = {}
+        for k, v in (batch.get("img_input_dict") or {}).items():
+            if isinstance(v, torch.Tensor):
+                t = torch.cat([v, v], dim=0).to(dev)
+                t._vlr_dup = 2
+                img[k] = t
+            elif isinstance(v, list):
+                img[k] = v + v
+            else:
+                raise ValueError(f"Unsupported type {type(v)} for concatenation.")
+        B = ic.shape[0]
+        out = dict(input_ids=ids, attention_mask=mask, img=img, pairs=B,
+                   reward_cols=torch.tensor([ic.shape[1] - 1] * B + [ir.shape[1] - 1] * B, dtype=torch.int64))
+        batch["_vlr_rm_concat"] = dict(src=src, out=out)
+        return out
+
+    def concatenated_forward(self, model, batch):
+        """-> (rewards_chosen [B], rewards_rejected [B]) fp32 from one pass over [chosen ; rejected]"""
+        cb = self.concatenated_inputs(batch)
+        rewards = model(input_ids=cb["input_ids"], attention_mask=cb["attention_mask"], reward_cols=cb["reward_cols"], **cb["img"])[0]
+        rewards = rewards.squeeze(-1)
+        return rewards[: cb["pairs"]], rewards[cb["pairs"]:]
+
+    def pair_loss(self, rewards_chosen, rewards_rejected):
+        """-logsigmoid(r_chosen - r_rejected) per pair, forward and backward in vlr_dpo_loss (beta 1, reference_free)"""
+        zeros = torch.zeros_like(rewards_chosen)
+        losses, _, _ = _DpoLossFn.apply(rewards_chosen, rewards_rejected, zeros, zeros, 1.0, 0.0, 0, 1)
+        return losses
+
+    def compute_loss(self, model, inputs, return_outputs: bool = False):
+        """trl==0.8.1 RewardTrainer.compute_loss (no margin column in this pipeline)"""
+        rc, rr = self.concatenated_forward(model, inputs)
+        loss = self.pair_loss(rc, rr).mean()
+        if return_outputs:
+            return loss, {"rewards_chosen": rc, "rewards_rejected": rr}
+        return loss
+
+    def prediction_step(self, model, inputs, prediction_loss_only: bool = False, ignore_keys=None):
+        """trl RewardTrainer.prediction_step + compute_accuracy: every pair adds 1 to eval_accuracy when r_chosen >= r_rejected (numpy
+        argmax takes the first of two equal logits, so a tie counts as correct); -> (loss, logits [B, 2], labels = zeros)"""
+        with torch.no_grad():
+            loss, out = self.compute_loss(model, self._prepare_inputs(inputs), return_outputs=True)
+        rc, rr = out["rewards_chosen"].detach(), out["rewards_rejected"].detach()
+        self._stored_metrics["eval"]["eval_accuracy"].extend((rc >= rr).float().unbind(0))
+        if prediction_loss_only:
+            return loss.detach(), None, None
+        logits = torch.stack([rc, rr], dim=1).softmax(dim=1)
+        return loss.detach(), logits, torch.zeros(logits.shape[0], device=logits.device)
+
+    def load_checkpoint(self, path: str) -> dict:
+        state = super().load_checkpoint(path)
+        # the base wrapper's state dict does not hold the head.  With an optimizer state the head came back with the master copy
+        # (load_optimizer_state), under LoRA load_adapter read rm_head.bin; what is left is a checkpoint of the weights alone
+        if not self.is_peft_model and not os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):
+            self.model.load_rm_head(path)
+        return state
 
 
 class _State:

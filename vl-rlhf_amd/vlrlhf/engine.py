@@ -135,6 +135,12 @@ class ParamLayout:
                 e.append((f"l{l}.ln1", (H,), [(p + nm["ln1"], 0, H)]))
         if norms_decay:
             _norms()
+        # reward model (cfg["rm_head"]; reference base/model.py VLRewardModel: rm_head = nn.Linear(hidden, 1)): the weight closes the
+        # decay region, the bias the no-decay region - the clip, AdamW, the DDP tail bucket and the optimizer checkpoint cover both.
+        # Neither is part of the base model's checkpoint (no hf name): they travel in rm_head.bin
+        rm_head = bool(cfg.get("rm_head"))
+        if rm_head:
+            e.append(("rm_head.w", (H,), []))
         self.n_decay_entries = len(e)
         if not norms_decay:
             _norms()
@@ -151,6 +157,8 @@ class ParamLayout:
         if not (qwen or ilm):
             e.append(("proj.b2", (H,), [("multi_modal_projector.linear_2.bias", 0, H)]))
             e.append(("proj.b1", (H,), [("multi_modal_projector.linear_1.bias", 0, H)]))
+        if rm_head:
+            e.append(("rm_head.b", (1,), []))
         self.n_trainable_entries = len(e)
         if ilm:      # --freeze_vision_tower freezes the projector too (InternLMXC2/__init__.py:252-255): kept OUTSIDE the optimizer's range
             e.append(("proj.w2", (H, H), [("vision_proj.2.weight", 0, H)]))
@@ -247,6 +255,13 @@ class LoraLayout:
                 self.offset[f"l{l}.{k}"] = o
                 self.shape[f"l{l}.{k}"] = per[k]
                 o += _align(per[k][0] * per[k][1])
+        self.n_decay = o          # [n_decay, numel): stepped with weight decay 0 (the reward head's bias; empty without cfg["rm_head"])
+        if cfg.get("rm_head"):    # the reward head trains beside the adapters (peft modules_to_save=["rm_head"]): weight, then bias
+            self.offset["rm_head.w"], self.shape["rm_head.w"] = o, (H,)
+            o += _align(H)
+            self.n_decay = o
+            self.offset["rm_head.b"], self.shape["rm_head.b"] = o, (1,)
+            o += _align(1)
         self.numel = o
 
     def hf_names(self, prefix=None):
@@ -620,6 +635,8 @@ class LlavaHipEngine:
             if ".a_" in k:
                 bound = 1.0 / math.sqrt(t.shape[1])
                 t.copy_((torch.rand(t.shape, generator=gen, device=self.dev) * 2 - 1) * bound)
+            elif k.startswith("rm_head."):      # the head moves into the adapters' buffer with the values it has
+                t.copy_(self.policy.v[k])
         self.lora_seed = int(seed)
         self._lora_calls = 0
 
@@ -1270,6 +1287,51 @@ class LlavaHipEngine:
             self.reducer.bucket_ready("lm_head")
         return dhidden
 
+    # ------------------------------------------------------------------------------------------------ reward head
+    def rm_head_views(self):
+        """(weight [H], bias [1], d weight, d bias) of the reward head in the trainable buffers of the mode in use"""
+        if not self.cfg.get("rm_head"):
+            raise ValueError("this engine was built without cfg['rm_head']: it has no reward head")
+        if self.lora is not None:
+            return self.lv["rm_head.w"], self.lv["rm_head.b"], self.lgv["rm_head.w"], self.lgv["rm_head.b"]
+        return self.policy.v["rm_head.w"], self.policy.v["rm_head.b"], self.gv["rm_head.w"], self.gv["rm_head.b"]
+
+    def set_rm_head(self, weight, bias):
+        """loads the head (rm_head.bin: weight [1, H] or [H], bias [1]); the optimizer's master copy follows"""
+        w, b, _, _ = self.rm_head_views()
+        w.copy_(weight.reshape(-1).to(device=self.dev, dtype=BF16))
+        b.copy_(bias.reshape(-1).to(device=self.dev, dtype=BF16))
+        self._weights_version += 1
+        if self.master is not None:
+            self.init_optimizer()
+
+    def reward_forward(self, ctx, rows):
+        """rewards[i] = rm_head(hidden[rows[i]]) in fp32 (vlr_rm_head_fwd); rows: dense row indices b * S + column into the final hidden
+        states of `ctx`, one per sequence.  The lm-head never runs.  Returns (rewards [n] fp32, rw_ctx)."""
+        w, b, _, _ = self.rm_head_views()
+        rows = rows.to(device=self.dev, dtype=torch.int32).contiguous()
+        n = rows.numel()
+        rewards = torch.empty(n, dtype=torch.float32, device=self.dev)
+        _hip.call("vlr_rm_head_fwd", ctx["hidden"], self.H, rows, w, b, rewards, n, self.H)
+        return rewards, dict(ctx=ctx, rows=rows, n=n)
+
+    def reward_backward(self, lp, d_rewards):
+        """d rewards -> d hidden (dense [M,H], zero outside the reward rows) and the head's gradients (vlr_rm_head_bwd).  The lm-head
+        takes part in the reference's graph with a zero gradient (0.0 * mean(logits)): in a full fine-tune its gradient stays zero -
+        zeroed here on a fresh gradient buffer, as logps_backward does for R == 0."""
+        ctx = lp["ctx"]
+        w, _, gw, gb = self.rm_head_views()
+        acc = int(not self.grad_fresh)
+        dhidden = torch.zeros(ctx["M"], self.H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_rm_head_bwd", ctx["hidden"], self.H, lp["rows"], w, d_rewards.to(torch.float32).contiguous(), dhidden, self.H,
+                  gw, gb, acc, lp["n"], self.H)
+        if self.lora is None:
+            if not acc:
+                self.gv["lm_head"].zero_()
+            if self.reducer is not None:
+                self.reducer.bucket_ready("lm_head")
+        return dhidden
+
     def logits_mean(self, ctx, lo, hi):
         """mean over [lo:hi] sequences, all positions, all vocabulary entries of the logits = mean_rows(h . sum_v W_v)/V
         (the `logits/chosen|rejected` metrics of trl's get_batch_loss_metrics, never materialising [B,S,V])."""
@@ -1498,8 +1560,12 @@ class LlavaHipEngine:
             _hip.call("vlr_grad_sqnorm", self.lora_grads, n, float(max_grad_norm if max_grad_norm else 0.0),
                       float(grad_scale), 0.0, self._sq_ws, self.norm_out)
             self.opt_step += 1
-            _hip.call("vlr_adamw_step", self.master, self.m, self.v, self.lora_grads, self.lora_flat, n, float(lr),
-                      float(beta1), float(beta2), float(eps), float(weight_decay), self.opt_step, self.norm_out)
+            nd = self.lora_layout.n_decay
+            for lo, hi, wd in ((0, nd, weight_decay), (nd, n, 0.0)):      # (the no-decay tail is the reward head's bias, when there is one)
+                if hi <= lo:
+                    continue
+                _hip.call("vlr_adamw_step", self.master[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lora_grads[lo:hi], self.lora_flat[lo:hi],
+                          hi - lo, float(lr), float(beta1), float(beta2), float(eps), float(wd), self.opt_step, self.norm_out)
             self.grad_fresh = True
             return self.norm_out
         n = self.layout.n_opt

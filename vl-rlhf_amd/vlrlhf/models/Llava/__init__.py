@@ -13,9 +13,10 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, gptq
-from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.model import VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine import BF16, LlavaHipEngine, WeightSet
 from ...utils.common import flatten_list
 from ..utils import ModelCoreMapper
@@ -885,11 +886,40 @@ class LlavaSFTTRainer(VLSFTTrainer):          # sic: the reference's spelling (:
     ...
 
 
+class LlavaForRM(LlavaForRL):
+    """LlavaForRL whose engine carries the reward head in its trainable buffers (cfg["rm_head"]): the base model of LlavaRewardModel"""
+
+    def __init__(self, cfg: dict, **kw):
+        super().__init__(dict(cfg, rm_head=True), **kw)
+
+
+class LlavaRewardModel(VLRewardModel):
+    """reference Llava/__init__.py LlavaRewardModel: reward = rm_head at merged column T - 1 + images * (P - 1)"""
+    base_cls = LlavaForRM
+    image_count_key = "image_token"
+
+
+@dataclass
+class LlavaRMDataCollatorWithPadding(VLRMDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        padded = super().__call__(features)
+        ip = self.processor.image_processor if self.processor is not None else None
+        padded["img_input_dict"] = dict(pixel_values=load_pixel_values(padded["img_path"], ip))
+        return padded
+
+
+class LlavaRMTrainer(VLRMTrainer):
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=LlavaForRL,
     processor=LlavaProcessor,
     dpo_collator=LlavaDPODataCollatorWithPadding,
     dpo_trainer=LlavaDPOTrainer,
+    reward_model=LlavaRewardModel,
+    reward_collator=LlavaRMDataCollatorWithPadding,
+    reward_trainer=LlavaRMTrainer,
     sft_collator=LlavaSFTDataCollatorWithPadding,
     sft_trainer=LlavaSFTTRainer,
 )

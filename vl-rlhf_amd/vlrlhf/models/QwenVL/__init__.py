@@ -15,9 +15,10 @@ from typing import Any, Dict, List, Optional, Union
 import torch
 
 from ... import gptq
-from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.collator import VLDPODataCollatorWithPadding, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.model import VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine_qwen import QwenVLHipEngine
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
@@ -370,11 +371,40 @@ class QwenVLSFTTrainer(VLSFTTrainer):
     ...
 
 
+class QwenVLForRM(QwenVLForRL):
+    """QwenVLForRL whose engine carries the reward head in its trainable buffers (cfg["rm_head"]): the base model of QwenVLRewardModel"""
+
+    def __init__(self, cfg: dict, **kw):
+        super().__init__(dict(cfg, rm_head=True), **kw)
+
+
+class QwenVLRewardModel(VLRewardModel):
+    """reference QwenVL/__init__.py QwenVLRewardModel: the image slots are tokens of the text, so the reward column is T - 1 as it is"""
+    base_cls = QwenVLForRM
+    image_count_key = "image_start_id"
+
+
+@dataclass
+class QwenVLRMDataCollatorWithPadding(VLRMDataCollatorWithPadding):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        padded = super().__call__(features)
+        size = getattr(self.processor, "image_size", None) or 448
+        padded["img_input_dict"] = dict(pixel_values=load_qwen_pixel_values(flatten_list(padded["img_path"]), size))
+        return padded
+
+
+class QwenVLRMTrainer(VLRMTrainer):
+    ...
+
+
 core_mapper = ModelCoreMapper(
     model=QwenVLForRL,
     processor=QwenVLProcessor,
     dpo_collator=QwenVLDPODataCollatorWithPadding,
     dpo_trainer=QwenVLDPOTrainer,
+    reward_model=QwenVLRewardModel,
+    reward_collator=QwenVLRMDataCollatorWithPadding,
+    reward_trainer=QwenVLRMTrainer,
     sft_collator=QwenVLSFTDataCollatorWithPadding,
     sft_trainer=QwenVLSFTTrainer,
 )

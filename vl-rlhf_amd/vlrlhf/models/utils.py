@@ -1,5 +1,6 @@
 """Per-model registry record (mirror of /root/reference/src/vlrlhf/models/utils.py:18-31).  The DPO and SFT slots are filled by every
-model package; the PPO / reward slots stay in the record so a reference user finds the same twelve fields, and are None."""
+model package, the reward slots by LLaVA-1.5 and Qwen-VL; the PPO / value slots stay in the record so a reference user finds the same
+twelve fields, and are None."""
 from dataclasses import dataclass
 from typing import Any
 

@@ -67,6 +67,33 @@ class MyAutoSFTTrainer:
         return auto_core_mapper(_architecture(model_name_or_path)).sft_trainer(*args, **kwargs)
 
 
+RM_FAMILIES = ["Llava", "QwenVL"]      # LLaVA-Next's left-padded anyres merge and InternLM-XComposer2's PLoRA rows need their own reward-row rule
+
+
+def _reward_slot(architecture: str, slot: str):
+    nick = MODEL_NICKNAME_MAP[architecture]
+    got = getattr(auto_core_mapper(architecture), slot)
+    if got is None:
+        raise NotImplementedError(f"{nick}: the MI355X reward model covers {RM_FAMILIES} (LLaVA-1.5 and Qwen-VL) only")
+    return got
+
+
+class MyAutoRewardModel:
+    @classmethod
+    def from_pretrained(cls, model_name_or_path, *args, **kwargs):
+        return _reward_slot(_architecture(model_name_or_path), "reward_model").from_pretrained(model_name_or_path, *args, **kwargs)
+
+
+class MyAutoRMCollator:
+    def __new__(cls, model_name_or_path, pad_token_id=0, processor=None):
+        return _reward_slot(_architecture(model_name_or_path), "reward_collator")(pad_token_id, processor)
+
+
+class MyAutoRMTrainer:
+    def __new__(cls, model_name_or_path, *args, **kwargs):
+        return _reward_slot(_architecture(model_name_or_path), "reward_trainer")(*args, **kwargs)
+
+
 def auto_load_rlmodel(script_args, training_args, lora_args):
     """-> (model, ref_model=None, lora_config); vision tower frozen (reference :554-555; freeze_vision_tower=False raises).  With use_lora the LoraConfig of
     reference :559-571 is returned as a plain dict (peft itself is not needed: the trainer hands it to
