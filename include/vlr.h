@@ -349,6 +349,44 @@ int vlr_rm_head_fwd(const void* hidden, int ldh, const int* rows, const void* w,
 int vlr_rm_head_bwd(const void* hidden, int ldh, const int* rows, const void* w, const float* d_rewards, void* dhidden, int ldd,
                     void* dw, void* db, int accumulate, int n, int H, vlr_stream_t stream);
 
+/* ---- PPO (reference ppo.py / VLPPOTrainer, whose step is trl 0.8.1's PPOTrainer.step; additive entry points, vlr_abi_version() does
+ *      not move).  Every per-token tensor is compact [R] fp32 over the response rows of vlr_build_rows (the rows whose logits predict a
+ *      response token; the values are read on the same rows), seq_off [n + 1] delimits the n sequences.  No atomics: every reduction
+ *      runs in an order fixed by the sizes alone, two calls give the same bits.  exp is expf.
+ * vlr_ppo_advantages: kl_t = old_logp - ref_logp (kl_penalty 0 "kl"), |.| (1 "abs"), 0.5 (.)^2 (2 "mse"); reward_t = -kl_coef kl_t, the
+ *      last token of sequence s gets + scores[s]; whiten_rewards: rewards <- masked_whiten(rewards, shift_mean = False) over all R
+ *      tokens.  Per sequence, backwards: delta_t = r_t + gamma V_{t+1} - V_t (V past the end = 0), A_t = delta_t + gamma lam A_{t+1},
+ *      returns = A + V; then advantages <- masked_whiten(A) over all R tokens.  masked_whiten(x) = (x - mean) / sqrt(var + 1e-8) with
+ *      var = the biased variance x R / (R - 1); shift_mean = False adds the mean back.  kl_sums[s] = sum_t kl_t; stats[4] = {mean of
+ *      kl_sums over the sequences, mean non-score reward per token, mean and (R / (R - 1)) variance of A before whitening}.
+ *      R >= 2 (refused before any launch), 1 <= n <= R.  One workgroup of 1024 threads: wave per sequence for the rewards, thread
+ *      per sequence for the scan, thread-strided sums folded by xor butterflies and the 16 waves in order.
+ * vlr_ppo_loss: ratio = exp(logp - old_logp); pg = mean(max(-A ratio, -A clamp(ratio, 1 - cliprange, 1 + cliprange)));
+ *      vf = 0.5 mean(max((vpred - ret)^2, (clamp(vpred, V_old - cliprange_value, V_old + cliprange_value) - ret)^2));
+ *      loss = pg + vf_coef vf; means are sums over the R tokens / R.  dlogp / dvpred = upstream * d loss / d logp, d vpred exactly as
+ *      torch autograd differentiates that expression (clamp passes the gradient on its closed interval, max halves a tie), final on
+ *      return.  mean(ratio) > ratio_threshold: pg, vf, loss and every gradient are exactly 0, decided on the device.  The ratio bounds
+ *      are formed in double and rounded to fp32 once (torch.clamp with Python floats); V_old -+ cliprange_value in fp32.
+ *      stats[17] = {loss, pg, vf, approxkl = 0.5 mean((logp - old)^2), policykl = mean(old - logp), pg_clipfrac, vf_clipfrac (both
+ *      strict >), mean ratio, returns mean, returns var, vpred mean, vpred var, value error = mean((vpred - ret)^2), advantages mean,
+ *      old values mean, old values var, 1 when the ratio threshold tripped}; variances as masked_var (x R / (R - 1)).  R >= 2.
+ *      One workgroup of 1024 threads: the threshold needs the mean over all tokens before any gradient is written.
+ * vlr_v_head_bwd: the value head v_r = dot(hg[r], w) + b on ALL R gathered rows hg [R][H] bf16 (its forward is vlr_rm_head_fwd with
+ *      rows = 0..R-1, ldh = H).  dhg_inout[r] = bf16(float(dhg_inout[r]) + g_r w): added onto the lm-head backward's gathered d hg,
+ *      rows >= R untouched; dw[h] = sum_r g_r hg[r][h], db = sum_r g_r in fp32, rounded to bf16 once - with `accumulate` the old value
+ *      is added in fp32 before that rounding.  The rows are cut into ceil(R / max(8, ceil(R / 256))) chunks, one wave per chunk and
+ *      64 column groups, the chunk partials (fp32, in `workspace`: vlr_v_head_bwd_workspace_bytes(R, H)) are folded in chunk order by a
+ *      second kernel.  H % 8 == 0, H >= 8, R >= 1. */
+int vlr_ppo_advantages(const float* old_logp, const float* ref_logp, const float* values, const int* seq_off, const float* scores,
+                       float kl_coef, int kl_penalty, float gamma, float lam, int whiten_rewards, float* advantages, float* returns,
+                       float* kl_sums, float* stats, int R, int n, vlr_stream_t stream);
+int vlr_ppo_loss(const float* logp, const float* vpred, const float* old_logp, const float* old_values, const float* advantages,
+                 const float* returns, int R, double cliprange, double cliprange_value, float vf_coef, float ratio_threshold,
+                 float upstream, float* dlogp, float* dvpred, float* stats, vlr_stream_t stream);
+long vlr_v_head_bwd_workspace_bytes(int R, int H);
+int vlr_v_head_bwd(const void* hg, const void* w, const float* g, void* dhg_inout, void* dw, void* db, int accumulate, void* workspace,
+                   int R, int H, vlr_stream_t stream);
+
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d
  * policy_{chosen,rejected}_logps with g = grad_losses or 1/len(losses) when NULL (trl: loss = losses.mean()). */

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("VLR_LIB") or os.path.join(os.path.dirname(_HERE), "li
 
 _lib = None
 
-P, I, L, F, U64, U32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_uint32
+P, I, L, F, D, U64, U32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_uint64, C.c_uint32
 
 
 class LlamaCfg(C.Structure):
@@ -131,6 +131,10 @@ _SIGS = {
     "vlr_dpo_loss": [P, P, P, P, I, F, F, I, I, P, P, P, P, P, P, P, P],
     "vlr_rm_head_fwd": [P, I, P, P, P, P, I, I, P],
     "vlr_rm_head_bwd": [P, I, P, P, P, P, I, P, P, I, I, I, P],
+    # PPO (include/vlr.h "PPO"): rewards + GAE + whitening, the clipped loss with its gradients, the value head's backward
+    "vlr_ppo_advantages": [P, P, P, P, P, F, I, F, F, I, P, P, P, P, I, I, P],
+    "vlr_ppo_loss": [P, P, P, P, P, P, I, D, D, F, F, F, P, P, P, P],
+    "vlr_v_head_bwd": [P, P, P, P, P, P, I, P, I, I, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],
@@ -223,7 +227,7 @@ _INT_HELPERS = {
 
 
 _LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes"]      # (int, int, int) -> long
-_LONG_HELPERS_N = {"vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5}      # name -> number of int arguments, -> long
+_LONG_HELPERS_N = {"vlr_v_head_bwd_workspace_bytes": 2, "vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5}      # name -> number of int arguments, -> long
 
 
 class VlrError(RuntimeError):

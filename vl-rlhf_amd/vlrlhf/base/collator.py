@@ -107,3 +107,18 @@ class VLRMDataCollatorWithPadding:
                 t[i, : v.numel()] = v
             out[k] = t
         return out
+
+
+@dataclass
+class VLPPODataCollator:
+    r"""reference :114-126: no padding - every key becomes the LIST of the rows' values, `input_ids` / `attention_mask` as one LongTensor
+    per row (VLPPOTrainer.generate left-pads the queries itself).  The model packages add the image tensors."""
+
+    processor: Optional[Any] = None
+
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        batch: Dict[str, Any] = {}
+        for key in features[0].keys():
+            batch[key] = [torch.as_tensor(f[key], dtype=torch.long) if key in ("input_ids", "attention_mask") else f[key] for f in features]
+        return batch
+

@@ -9,6 +9,7 @@ reproduced: the per-micro-step `torch.cuda.empty_cache(); gc.collect()` (referen
 """
 import contextlib
 import copy
+import dataclasses
 import math
 import os
 import random
@@ -1218,6 +1219,501 @@ class VLRMTrainer(VLTrainerLoop):
         if not self.is_peft_model and not os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):
             self.model.load_rm_head(path)
         return state
+
+
+@dataclasses.dataclass
+class PPOConfig:
+    """the fields of trl==0.8.1 PPOConfig that the PPO step reads (same names, same defaults).  batch_size = the rows of one step(),
+    backward_batch_size = mini_batch_size * gradient_accumulation_steps = the rows of one optimizer step."""
+    learning_rate: float = 1.41e-5
+    batch_size: int = 128
+    mini_batch_size: int = 128
+    gradient_accumulation_steps: int = 1
+    ppo_epochs: int = 4
+    gamma: float = 1.0
+    lam: float = 0.95
+    cliprange: float = 0.2
+    cliprange_value: float = 0.2
+    vf_coef: float = 0.1
+    kl_penalty: str = "kl"
+    init_kl_coef: float = 0.2
+    adap_kl_ctrl: bool = True
+    target: float = 6.0
+    horizon: float = 10000.0
+    whiten_rewards: bool = False
+    ratio_threshold: float = 10.0
+    early_stopping: bool = False
+    target_kl: float = 1.0
+    max_grad_norm: Optional[float] = None
+    seed: int = 0
+    world_size: int = 1
+    # the reference's additions (src/vlrlhf/ppo.py PPOConfig) that this path reads
+    use_lora: bool = False
+    use_value_adapter: bool = False
+    gradient_checkpointing: bool = False
+    output_dir: Optional[str] = None
+    per_device_gamelog_size: int = 2
+    max_new_tokens: Optional[int] = None
+    max_length: Optional[int] = None
+    local_rank: int = -1
+    # not in the reference: a checkpoint every save_steps steps of train() (0: none) and the one to resume from
+    save_steps: int = 0
+    resume_from_checkpoint: Optional[str] = None
+
+    def __post_init__(self):
+        self.backward_batch_size = self.mini_batch_size * self.gradient_accumulation_steps
+        if self.batch_size <= 0 or self.mini_batch_size <= 0 or self.batch_size % self.backward_batch_size:
+            raise ValueError(f"batch_size ({self.batch_size}) must be a multiple of mini_batch_size * gradient_accumulation_steps "
+                             f"({self.backward_batch_size})")
+        if self.per_device_gamelog_size > self.batch_size:
+            raise ValueError("per_device_gamelog_size should be less than batch_size")
+        if self.use_value_adapter and not self.use_lora:
+            raise ValueError("You can only use value adapter with a Peft base model. Please set use_lora to True.")
+        if self.max_new_tokens is not None and self.max_length is not None:
+            raise ValueError("You can only use one of max_new_tokens and max_length")
+        if self.kl_penalty not in ("kl", "abs", "mse", "full"):
+            raise ValueError(f"kl_penalty must be one of 'kl', 'abs', 'mse', 'full', got {self.kl_penalty!r}")
+
+
+class AdaptiveKLController:
+    """trl AdaptiveKLController: e = clip(kl / target - 1, -0.2, 0.2); value *= 1 + e * n_steps / horizon"""
+
+    def __init__(self, init_kl_coef, target, horizon):
+        self.value, self.target, self.horizon = float(init_kl_coef), float(target), float(horizon)
+
+    def update(self, current, n_steps):
+        e = min(max(current / self.target - 1.0, -0.2), 0.2)
+        self.value *= 1.0 + e * n_steps / self.horizon
+
+
+class FixedKLController:
+    def __init__(self, kl_coef):
+        self.value = float(kl_coef)
+
+    def update(self, current, n_steps):
+        pass
+
+
+KL_PENALTY_IDS = {"kl": 0, "abs": 1, "mse": 2}
+
+
+class VLPPOTrainer:
+    """The PPO optimisation step - trl==0.8.1 PPOTrainer.step as the reference's VLPPOTrainer (base/trainer.py) drives it, restated in
+    include/vlr.h ("PPO") and run on the HIP engine: no-grad rollout passes of the policy (log-probs, values) and of the reference
+    (the adapters switched off under LoRA, else a frozen copy made when none is given), rewards + GAE + whitening in
+    vlr_ppo_advantages, then ppo_epochs x minibatches of forward, vlr_ppo_loss, backward and one Adam step per backward batch.
+
+    tokenize_row, generate, scoring by a separate reward model, step, the train() loop and checkpoint / resume (weights, optimizer, kl_coef,
+    the permutation generator and the row order) are here; the entry point is vlrlhf/ppo.py.
+
+    Deliberate differences from trl: the image inputs reach every forward of the step (trl's prepare_model_inputs drops them); the
+    entropy statistics are left out (they need a pass over the vocabulary and carry no gradient); rollout and reference passes run in
+    eval mode (no adapter dropout, no NEFTune noise); world_size > 1 is refused, since whitening and the KL mean are per process in trl
+    and nothing here settles what they should be across ranks."""
+
+    def __init__(self, config=None, model=None, ref_model=None, reward_model=None, processor=None, dataset=None, data_collator=None,
+                 generation_kwargs=None):
+        # argument order = the reference's VLPPOTrainer
+        if config is None or model is None:
+            raise ValueError("VLPPOTrainer needs a config and a model")
+        if not hasattr(model, "v_head"):
+            raise ValueError("VLPPOTrainer needs a model with a value head (vlrlhf.base.model.VLModelWithValueHead)")
+        if int(getattr(config, "world_size", 1) or 1) > 1 or _world() > 1:
+            raise NotImplementedError("PPO on more than one GPU: whitening and the KL mean are per process in trl and the MI355X path "
+                                      "does not settle what they are across ranks")
+        if config.kl_penalty == "full":
+            raise NotImplementedError("kl_penalty='full' needs the [R][V] logits of the policy and the reference; 'kl', 'abs' and 'mse' are built")
+        self.config, self.model, self.reward_model = config, model, reward_model
+        self.processor, self.dataset, self.data_collator = processor, dataset, data_collator
+        self.tokenizer = processor.tokenizer if processor is not None else None
+        self.generation_kwargs = dict(generation_kwargs or {})
+        self.is_peft_model = bool(getattr(model, "is_peft_model", False))
+        if ref_model is None and not self.is_peft_model:      # trl: create_reference_model(model) when none is given
+            ref_model = model.pretrained_model.create_reference_model()
+        self.ref_model = ref_model
+        self.kl_ctl = (AdaptiveKLController(config.init_kl_coef, config.target, config.horizon) if config.adap_kl_ctrl
+                       else FixedKLController(config.init_kl_coef))
+        self.accelerator = _Accelerator(model)
+        self._perm_gen = torch.Generator().manual_seed(int(config.seed))
+        pad = getattr(self.tokenizer, "pad_token_id", None)
+        self.padding_value = int(pad) if pad is not None else 0
+        self.state = _State()
+        self._stored_metrics = defaultdict(lambda: defaultdict(list))
+        self.log_history: List[dict] = []
+        self.time_phases = False      # tools/ppo_bench.py: HIP events around the rollout and the optimisation of step() -> last_timing
+        self.keep_rollout = False     # True: step() leaves its rollout tensors in last_rollout (diagnostics, the tests); off, nothing outlives the step
+        self.last_rollout = None
+        self.dataset = self._tokenize_dataset(dataset)
+        self._data_gen = torch.Generator().manual_seed(int(config.seed) + 1)      # the order of the rows, apart from the step's permutations
+        self._epoch_data_state = self._data_gen.get_state().tolist()
+        model.engine.init_optimizer()
+
+    # ------------------------------------------------------------------------------------------ data
+    def _tokenize_dataset(self, ds):
+        if ds is None:
+            return None
+        rows = list(ds)
+        if rows and "input_ids" not in rows[0]:
+            rows = [self.tokenize_row(dict(r)) for r in rows]
+        return rows
+
+    def tokenize_row(self, element):
+        """reference :416-426: the query with its image placeholder, as a single-turn conversation with an empty answer - the ids end
+        where the assistant begins.  No labels.  The image travels as `img_path` (the key the collators read; the reference's `image`
+        is accepted too)."""
+        image = element["img_path"] if "img_path" in element else element["image"]
+        query = self.processor.format_multimodal_prompt(element["query"], image)
+        conv = self.processor.make_single_turn_conv(query, "")
+        tokens = self.processor.process_batch_conv([conv])["full"]
+        tokens = {k: v[0] for k, v in tokens.items() if k != "labels"}
+        tokens["query"] = query
+        tokens["img_path"] = image
+        return tokens
+
+    def get_batches(self):
+        """one pass over the dataset: shuffled rows in batches of config.batch_size through the collator, the last partial batch dropped
+        (trl prepare_dataloader: shuffle=True, drop_last=True)"""
+        n, bs = len(self.dataset), self.config.batch_size
+        self._epoch_data_state = self._data_gen.get_state().tolist()      # a checkpoint restores the generator to where this pass began
+        order = torch.randperm(n, generator=self._data_gen).tolist()
+        for lo in range(0, n - bs + 1, bs):
+            yield self.data_collator([self.dataset[i] for i in order[lo:lo + bs]])
+
+    # ------------------------------------------------------------------------------------------ scoring
+    def compute_scores(self, queries_text, responses_text, img):
+        """the separate reward model on the rebuilt conversations -> scores [n] fp32.  Deliberate difference from the reference, which
+        left-pads and reads column -1: rows are right-padded and every row's reward is read at its own last token (reward_cols), the
+        path VLRewardModel's tests cover; the rows of a batch must carry the same number of images (VLRewardModel's rule)."""
+        if self.reward_model is None:
+            raise NotImplementedError("scoring needs a separate reward_model (VLRewardModel); a reward adapter on the policy's base is not "
+                                      "built on the MI355X path")
+        convs = [self.processor.make_single_turn_conv(q, r) for q, r in zip(queries_text, responses_text)]
+        full = self.processor.process_batch_conv(convs)["full"]
+        lens = [len(x) for x in full["input_ids"]]
+        T = max(lens)
+        ids = torch.full((len(lens), T), self.padding_value, dtype=torch.long)
+        mask = torch.zeros(len(lens), T, dtype=torch.long)
+        for i, (x, m) in enumerate(zip(full["input_ids"], full["attention_mask"])):
+            ids[i, :lens[i]] = torch.as_tensor(x, dtype=torch.long)
+            mask[i, :lens[i]] = torch.as_tensor(m, dtype=torch.long)
+        dev = self.reward_model.engine.dev
+        img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
+        return self.reward_model.score(ids.to(dev), mask.to(dev), reward_cols=torch.tensor([n - 1 for n in lens]), **img).float().cpu()
+
+    # ------------------------------------------------------------------------------------------ loop
+    IMAGE_KEYS = ("pixel_values",)      # what of a collated batch reaches the models as image input
+
+    def train(self, resume_from_checkpoint=None):
+        """reference :428-499: per batch - generate, decode, rebuild the conversations, score with the reward model, step, log (the
+        `log` seam; no wandb tables: the per_device_gamelog_size first rows are logged as text).  A batch whose scoring raises is
+        skipped.  config.save_steps > 0 writes a checkpoint every so many steps; resume_from_checkpoint continues one."""
+        resume = resume_from_checkpoint or getattr(self.config, "resume_from_checkpoint", None)
+        skip = 0
+        if resume:
+            skip = int(self.load_checkpoint(resume).get("batches_seen", 0))
+        self.batches_seen = 0
+        for batch in self.get_batches():
+            self.batches_seen += 1
+            if self.batches_seen <= skip:      # the rows a resumed run has already consumed (the row order is part of the checkpoint)
+                continue
+            queries = batch["input_ids"]
+            img = {k: batch[k] for k in self.IMAGE_KEYS if k in batch}
+            responses = self.generate(queries, return_prompt=False, **img)
+            batch["response"] = self.tokenizer.batch_decode(responses, skip_special_tokens=True)
+            try:
+                scores = self.compute_scores(batch["query"], batch["response"], img)
+            except NotImplementedError:
+                raise
+            except Exception as e:      # reference: warn, print the responses, skip the batch
+                print(f"[ppo] WARNING: error when computing reward score, skipping this batch: {e!r}\n{batch['response']}", flush=True)
+                self.skipped_batches = getattr(self, "skipped_batches", 0) + 1
+                continue
+            stats = self.step(queries, responses, [float(x) for x in scores], **img)
+            k = self.config.per_device_gamelog_size
+            game = [dict(query=self.processor.remove_image_placeholder(q), response=r, reward=float(s))
+                    for q, r, s in zip(batch["query"][:k], batch["response"][:k], scores[:k])]
+            self.log(dict(stats, game_log=game))
+            if self.config.save_steps and self.state.global_step % self.config.save_steps == 0:
+                self.save_checkpoint()
+        return self.log_history
+
+    def log(self, logs):
+        """the logging seam of the other trainers: one entry per step in log_history, printed on rank 0"""
+        logs = dict(logs, step=self.state.global_step)
+        self.log_history.append(logs)
+        if _rank() == 0:
+            print({k: (round(v, 6) if isinstance(v, float) else v) for k, v in logs.items() if k != "game_log"}, flush=True)
+        return logs
+
+    # ------------------------------------------------------------------------------------------ checkpoints
+    def save_checkpoint(self, path=None):
+        """`output_dir/checkpoint-<step>/`: the weights (adapter + value head under LoRA, else the checkpoint + v_head.bin), the optimizer
+        state (fp32 master / m / v + step), and trainer_state.json with the step counter, kl_coef, the states of the permutation and
+        row-order generators, the batches consumed and the log history.  A directory is complete or absent."""
+        import json
+        import shutil
+        from safetensors.torch import save_file
+        eng = self.model.engine
+        path = path or os.path.join(str(self.config.output_dir or "output"), f"checkpoint-{self.state.global_step}")
+        tmp = path + ".tmp"
+        shutil.rmtree(tmp, ignore_errors=True)
+        os.makedirs(tmp)
+        self.model.save_pretrained(tmp)
+        st = eng.optimizer_state()
+        if st is not None:
+            for k in ("master", "m", "v"):
+                save_file({k: st[k].detach().cpu()}, os.path.join(tmp, f"optimizer_{k}.safetensors"))
+        hist = [{k: v for k, v in h.items()} for h in self.log_history]
+        with open(os.path.join(tmp, "trainer_state.json"), "w") as f:
+            json.dump(dict(global_step=self.state.global_step, opt_step=eng.opt_step, kl_coef=float(self.kl_ctl.value),
+                           perm_generator=self._perm_gen.get_state().tolist(), data_generator_start=self._epoch_data_state,
+                           batches_seen=int(getattr(self, "batches_seen", 0)), lora_calls=getattr(eng, "_lora_calls", 0),
+                           batch_size=self.config.batch_size, log_history=hist), f)
+        shutil.rmtree(path, ignore_errors=True)
+        os.replace(tmp, path)
+        return path
+
+    def load_checkpoint(self, path):
+        """weights, optimizer, kl_coef, the permutation generator and the row order of a save_checkpoint directory -> its state dict"""
+        import json
+        from safetensors.torch import load_file
+        eng = self.model.engine
+        with open(os.path.join(path, "trainer_state.json")) as f:
+            state = json.load(f)
+        if int(state.get("batch_size", self.config.batch_size)) != self.config.batch_size:
+            raise ValueError(f"resume_from_checkpoint: {path} was written with batch_size={state['batch_size']}, this run has {self.config.batch_size}")
+        if self.is_peft_model:
+            self.model.load_adapter(path)
+        else:
+            sd = {}
+            for fn in sorted(os.listdir(path)):
+                if fn.startswith("model") and fn.endswith(".safetensors"):
+                    sd.update(load_file(os.path.join(path, fn)))
+            eng.policy.load_state_dict(sd)
+            self.model.load_v_head(path)
+        if os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):      # (the master copy carries the head too)
+            bufs = {k: load_file(os.path.join(path, f"optimizer_{k}.safetensors"))[k] for k in ("master", "m", "v")}
+            eng.load_optimizer_state(bufs["master"], bufs["m"], bufs["v"], state["opt_step"])
+        if hasattr(eng, "_lora_calls"):
+            eng._lora_calls = int(state.get("lora_calls", 0))
+        self.kl_ctl.value = float(state["kl_coef"])
+        self._perm_gen.set_state(torch.tensor(state["perm_generator"], dtype=torch.uint8))
+        self._data_gen.set_state(torch.tensor(state["data_generator_start"], dtype=torch.uint8))
+        self.state.global_step = int(state["global_step"])
+        self.log_history = list(state.get("log_history", []))
+        return state
+
+    # ------------------------------------------------------------------------------------------ batch
+    def _build_batch(self, queries, responses):
+        """[query ; response] right-padded; labels -100 except on the response tokens (every one counts, the first EOS included)"""
+        n = len(queries)
+        T = max(int(q.numel() + r.numel()) for q, r in zip(queries, responses))
+        ids = torch.full((n, T), self.padding_value, dtype=torch.long)
+        mask = torch.zeros(n, T, dtype=torch.long)
+        labels = torch.full((n, T), -100, dtype=torch.long)
+        for i, (q, r) in enumerate(zip(queries, responses)):
+            q, r = q.reshape(-1).cpu().long(), r.reshape(-1).cpu().long()
+            if r.numel() == 0:
+                raise ValueError(f"step: response {i} is empty")
+            L = q.numel() + r.numel()
+            ids[i, :L] = torch.cat([q, r])
+            mask[i, :L] = 1
+            labels[i, q.numel():L] = r
+        return ids, mask, labels
+
+    def _rows_images(self, ids, img, rows):
+        """the image inputs of the batch rows `rows` (in that order).  A tensor has one entry per IMAGE and is cut by the rows' image counts
+        (the ids name them: the model's image_count_key).  A list has one entry per image or one per row, told apart by its length; where
+        both lengths coincide while the rows carry unequal numbers of images the two readings differ, and the list is refused."""
+        if not img:
+            return {}
+        n = ids.shape[0]
+        tok = int(self.model.engine.cfg[self.model.image_count_key])
+        cnt = (ids == tok).sum(-1).tolist()
+        off = [0]
+        for c in cnt:
+            off.append(off[-1] + c)
+        total = off[-1]
+        by_image = [j for r in rows for j in range(off[r], off[r + 1])]
+        out = {}
+        for k, v in img.items():
+            if isinstance(v, torch.Tensor):
+                if len(v) != total:
+                    raise ValueError(f"step: image input {k!r} has {len(v)} entries for {n} rows carrying {total} images")
+                out[k] = v[torch.tensor(by_image, dtype=torch.long)].to(self.accelerator.device)
+                continue
+            if len(v) == total == n and any(c != 1 for c in cnt):
+                raise ValueError(f"step: image input {k!r} has {len(v)} entries, which is both the number of rows and of images while the rows "
+                                 f"carry {cnt} images: per row or per image cannot be told apart - pass a tensor, or one list per row")
+            if len(v) == total:
+                out[k] = [v[j] for j in by_image]
+            elif len(v) == n:
+                out[k] = [v[r] for r in rows]
+            else:
+                raise ValueError(f"step: image input {k!r} has {len(v)} entries for {n} rows carrying {total} images")
+        return out
+
+    def _reference_logps(self, ids, mask, labels, img):
+        """token log-probs [R] of the reference on the response rows, under no-grad"""
+        dev = self.accelerator.device
+        if self.ref_model is None:
+            with self.model.disable_adapter():
+                return self.model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
+        if hasattr(self.ref_model, "v_head"):
+            return self.ref_model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
+        out = self.ref_model(input_ids=ids.to(dev), attention_mask=mask.to(dev), labels=labels.to(dev), **img)
+        c = out.logits.c
+        return self.ref_model.engine.logps_forward(c, c["labels"], None, False, -100, reduce_seq=False)[1]["tok"]
+
+    # ------------------------------------------------------------------------------------------ sampling
+    @torch.no_grad()
+    def generate(self, queries, return_prompt: bool = False, generation_kwargs=None, **img):
+        """trl PPOTrainer.generate on a batch, as the reference's train() calls it: the queries (1-D id tensors) are LEFT-padded, the
+        model's own `generate` samples with the image inputs and `self.generation_kwargs` (updated by `generation_kwargs`), and each row
+        comes back without its prompt (unless return_prompt) and without what follows its first stop: an id of `eos_token_id`, or the last
+        token of a `stop_words_ids` sequence of the generation config - the rules `generate` itself ends a row by.  The stop stays in the
+        response (every response token counts in step(), the first EOS included).  Under LoRA the adapters run live (merge_lora=False)."""
+        from ..models.Llava import stop_sequences
+        kw = dict(self.generation_kwargs)
+        kw.update(generation_kwargs or {})
+        if self.is_peft_model:
+            kw.setdefault("merge_lora", False)
+        queries = [q.reshape(-1).cpu().long() for q in queries]
+        n, T0, dev = len(queries), max(int(q.numel()) for q in queries), self.accelerator.device
+        ids = torch.full((n, T0), self.padding_value, dtype=torch.long)
+        mask = torch.zeros(n, T0, dtype=torch.long)
+        for i, q in enumerate(queries):
+            ids[i, T0 - q.numel():] = q
+            mask[i, T0 - q.numel():] = 1
+        img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
+        out = self.model.generate(input_ids=ids.to(dev), attention_mask=mask.to(dev), **kw, **img)
+        gen = out[:, T0:].cpu()
+        gc = kw.get("generation_config")
+        eos = kw.get("eos_token_id")
+        if eos is None:
+            eos = getattr(gc, "eos_token_id", None)
+        if eos is None:
+            eos = self.model.config.get("eos_token_id", 2)
+        eos = set(eos) if isinstance(eos, (list, tuple)) else {int(eos)}
+        stops = [t.cpu().tolist() for t in stop_sequences(getattr(gc, "stop_words_ids", None), "cpu")]
+        responses = []
+        for i in range(n):
+            row, end = gen[i].tolist(), gen.shape[1]
+            for t, tok in enumerate(row):
+                if tok in eos or any(len(sq) <= t + 1 and row[t + 1 - len(sq): t + 1] == sq for sq in stops):
+                    end = t + 1
+                    break
+            r = gen[i, :end].clone()
+            responses.append(torch.cat([queries[i], r]) if return_prompt else r)
+        return responses
+
+    # ------------------------------------------------------------------------------------------ step
+    def step(self, queries, responses, scores, **img):
+        """one PPO optimisation step over config.batch_size (query, response, score) triples -> the stats dict under trl's key names.
+        `img`: the batch's image inputs as the model's forward takes them (pixel_values / img_path ...); they reach every pass."""
+        cfg, model, eng, dev = self.config, self.model, self.model.engine, self.accelerator.device
+        n = len(queries)
+        if not (n == len(responses) == len(scores)):
+            raise ValueError(f"step: {n} queries, {len(responses)} responses, {len(scores)} scores")
+        if n != cfg.batch_size:
+            raise ValueError(f"step: batch size {n} does not match config.batch_size {cfg.batch_size}")
+        ids, mask, labels = self._build_batch(queries, responses)
+        scores_t = torch.tensor([float(x) for x in scores], dtype=torch.float32)
+        mbs = cfg.mini_batch_size
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.time_phases else None
+        if ev:
+            ev[0].record()
+        # ---- rollout: no-grad, eval mode, in chunks of mini_batch_size rows
+        was_training = model.training
+        model.eval()
+        old_logp, old_values, ref_logp, lens = [], [], [], []
+        try:
+            with torch.no_grad():
+                for lo in range(0, n, mbs):
+                    rows = list(range(lo, min(lo + mbs, n)))
+                    i_, m_, l_, g_ = ids[rows], mask[rows], labels[rows], self._rows_images(ids, img, rows)
+                    lp, _, v = model(i_.to(dev), m_.to(dev), l_.to(dev), **g_)
+                    so = model.seq_off.tolist()
+                    lens += [so[j + 1] - so[j] for j in range(len(rows))]
+                    old_logp.append(lp.clone())
+                    old_values.append(v.clone())
+                    ref_logp.append(self._reference_logps(i_, m_, l_, g_).clone())
+        finally:
+            model.train(was_training)
+        old_logp, old_values, ref_logp = torch.cat(old_logp), torch.cat(old_values), torch.cat(ref_logp)
+        seq_off = [0]
+        for L in lens:
+            seq_off.append(seq_off[-1] + L)
+        R = seq_off[-1]
+        if R < 2:
+            raise ValueError(f"step: whitening needs at least 2 response tokens in the batch, got {R}")
+        # ---- rewards, advantages, returns
+        adv, ret = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+        kl_sums, astats = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(4, dtype=torch.float32, device=dev)
+        _hip.call("vlr_ppo_advantages", old_logp, ref_logp, old_values, torch.tensor(seq_off, dtype=torch.int32, device=dev), scores_t.to(dev),
+                  float(self.kl_ctl.value), KL_PENALTY_IDS[cfg.kl_penalty], float(cfg.gamma), float(cfg.lam), int(bool(cfg.whiten_rewards)),
+                  adv, ret, kl_sums, astats, R, n)
+        if ev:
+            ev[1].record()
+        # ---- optimisation (train mode for its passes; the caller's mode comes back afterwards)
+        model.train()
+        upstream = 1.0 / cfg.gradient_accumulation_steps
+        mb_stats = []
+        try:
+            for _ in range(cfg.ppo_epochs):
+                perm = torch.randperm(n, generator=self._perm_gen).tolist()
+                for b0 in range(0, n, cfg.backward_batch_size):
+                    eng.zero_grad()
+                    for m0 in range(b0, b0 + cfg.backward_batch_size, mbs):
+                        rows = perm[m0:m0 + mbs]
+                        tok_idx = torch.tensor([t for r in rows for t in range(seq_off[r], seq_off[r + 1])], dtype=torch.long, device=dev)
+                        Rm = tok_idx.numel()
+                        if Rm < 2:
+                            raise ValueError(f"step: a minibatch needs at least 2 response tokens, got {Rm}")
+                        logp, _, vpred = model(ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), **self._rows_images(ids, img, rows))
+                        dlogp, dvpred = torch.empty_like(logp), torch.empty_like(vpred)
+                        st = torch.empty(17, dtype=torch.float32, device=dev)
+                        _hip.call("vlr_ppo_loss", logp.detach(), vpred.detach(), old_logp[tok_idx], old_values[tok_idx], adv[tok_idx], ret[tok_idx],
+                                  Rm, float(cfg.cliprange), float(cfg.cliprange_value), float(cfg.vf_coef), float(cfg.ratio_threshold), upstream,
+                                  dlogp, dvpred, st)
+                        torch.autograd.backward([logp, vpred], [dlogp, dvpred])
+                        mb_stats.append(st)
+                    eng.optimizer_step(cfg.learning_rate, 0.9, 0.999, 1e-8, 0.0, cfg.max_grad_norm)
+                # trl decides early stopping once per epoch, on the policykl of the epoch's last minibatch, after its optimizer steps
+                # (_early_stop: policykl > 1.5 * target_kl -> zero_grad and no further epoch)
+                if cfg.early_stopping and float(mb_stats[-1][4]) > 1.5 * cfg.target_kl:
+                    eng.zero_grad()
+                    break
+        finally:
+            model.train(was_training)
+        if ev:
+            ev[2].record()
+            torch.cuda.synchronize()
+            self.last_timing = dict(rollout_ms=ev[0].elapsed_time(ev[1]), optimisation_ms=ev[1].elapsed_time(ev[2]))
+        # ---- stats (one device-to-host copy) and the KL controller
+        ms = torch.stack(mb_stats).mean(0).tolist()
+        a = astats.tolist()
+        kl_coef = float(self.kl_ctl.value)
+        qlen = [float(q.numel()) for q in queries]
+        rlen = [float(r.numel()) for r in responses]
+        stats = {
+            "objective/kl": a[0], "objective/kl_coef": kl_coef,
+            "ppo/loss/policy": ms[1], "ppo/loss/value": ms[2], "ppo/loss/total": ms[0],
+            "ppo/policy/approxkl": ms[3], "ppo/policy/policykl": ms[4], "ppo/policy/clipfrac": ms[5], "ppo/policy/advantages_mean": ms[13],
+            "ppo/policy/ratio": ms[7],
+            "ppo/returns/mean": ms[8], "ppo/returns/var": ms[9],
+            "ppo/val/vpred": ms[10], "ppo/val/error": ms[12], "ppo/val/clipfrac": ms[6], "ppo/val/mean": ms[14], "ppo/val/var": ms[15],
+            "ppo/mean_scores": float(scores_t.mean()), "ppo/std_scores": float(scores_t.std()) if n > 1 else float("nan"),
+            "ppo/mean_non_score_reward": a[1],
+            "tokens/queries_len_mean": sum(qlen) / n, "tokens/responses_len_mean": sum(rlen) / n,
+            "ppo/learning_rate": float(cfg.learning_rate),
+        }
+        self.kl_ctl.update(a[0], cfg.batch_size)
+        self.state.global_step += 1
+        if self.keep_rollout:
+            self.last_rollout = dict(old_logp=old_logp, old_values=old_values, ref_logp=ref_logp, seq_off=seq_off, advantages=adv, returns=ret,
+                                     kl_sums=kl_sums, minibatch_stats=mb_stats)
+        return stats
 
 
 class _State:

@@ -141,6 +141,13 @@ class ParamLayout:
         rm_head = bool(cfg.get("rm_head"))
         if rm_head:
             e.append(("rm_head.w", (H,), []))
+        # PPO value head (cfg["v_head"]; trl AutoModelForCausalLMWithValueHead: v_head.summary = nn.Linear(hidden, 1) on every position): placed
+        # exactly as the reward head is, weight in the decay region and bias outside it (PPO steps with weight decay 0 either way)
+        v_head = bool(cfg.get("v_head"))
+        if v_head and rm_head:
+            raise ValueError("cfg['rm_head'] and cfg['v_head'] on one engine: the reward model and the PPO policy are separate models")
+        if v_head:
+            e.append(("v_head.w", (H,), []))
         self.n_decay_entries = len(e)
         if not norms_decay:
             _norms()
@@ -159,6 +166,8 @@ class ParamLayout:
             e.append(("proj.b1", (H,), [("multi_modal_projector.linear_1.bias", 0, H)]))
         if rm_head:
             e.append(("rm_head.b", (1,), []))
+        if v_head:
+            e.append(("v_head.b", (1,), []))
         self.n_trainable_entries = len(e)
         if ilm:      # --freeze_vision_tower freezes the projector too (InternLMXC2/__init__.py:252-255): kept OUTSIDE the optimizer's range
             e.append(("proj.w2", (H, H), [("vision_proj.2.weight", 0, H)]))
@@ -261,6 +270,12 @@ class LoraLayout:
             o += _align(H)
             self.n_decay = o
             self.offset["rm_head.b"], self.shape["rm_head.b"] = o, (1,)
+            o += _align(1)
+        if cfg.get("v_head"):     # the PPO value head trains beside the adapters the same way (ParamLayout refuses both heads at once)
+            self.offset["v_head.w"], self.shape["v_head.w"] = o, (H,)
+            o += _align(H)
+            self.n_decay = o
+            self.offset["v_head.b"], self.shape["v_head.b"] = o, (1,)
             o += _align(1)
         self.numel = o
 
@@ -635,7 +650,7 @@ class LlavaHipEngine:
             if ".a_" in k:
                 bound = 1.0 / math.sqrt(t.shape[1])
                 t.copy_((torch.rand(t.shape, generator=gen, device=self.dev) * 2 - 1) * bound)
-            elif k.startswith("rm_head."):      # the head moves into the adapters' buffer with the values it has
+            elif k.startswith(("rm_head.", "v_head.")):      # the head moves into the adapters' buffer with the values it has
                 t.copy_(self.policy.v[k])
         self.lora_seed = int(seed)
         self._lora_calls = 0
@@ -1330,6 +1345,72 @@ class LlavaHipEngine:
                 self.gv["lm_head"].zero_()
             if self.reducer is not None:
                 self.reducer.bucket_ready("lm_head")
+        return dhidden
+
+    # ------------------------------------------------------------------------------------------------ PPO: value head + per-token heads
+    def v_head_views(self):
+        """(weight [H], bias [1], d weight, d bias) of the PPO value head in the trainable buffers of the mode in use"""
+        if not self.cfg.get("v_head"):
+            raise ValueError("this engine was built without cfg['v_head']: it has no value head")
+        if self.lora is not None:
+            return self.lv["v_head.w"], self.lv["v_head.b"], self.lgv["v_head.w"], self.lgv["v_head.b"]
+        return self.policy.v["v_head.w"], self.policy.v["v_head.b"], self.gv["v_head.w"], self.gv["v_head.b"]
+
+    def set_v_head(self, weight, bias):
+        """loads the head (v_head.summary.weight [1, H] or [H], v_head.summary.bias [1]); the optimizer's master copy follows"""
+        w, b, _, _ = self.v_head_views()
+        w.copy_(weight.reshape(-1).to(device=self.dev, dtype=BF16))
+        b.copy_(bias.reshape(-1).to(device=self.dev, dtype=BF16))
+        self._weights_version += 1
+        if self.master is not None:
+            self.init_optimizer()
+
+    def _row_range(self, n):
+        """0..n-1 as int32 on the device (the value head reads every gathered row; every row its own sequence in the lm-head backward)"""
+        t = self._ws.get(("row_range",))
+        if t is None or t.numel() < n:
+            t = self._ws[("row_range",)] = torch.arange(max(n, 4096), dtype=torch.int32, device=self.dev)
+        return t[:n]
+
+    def ppo_forward(self, ctx, labels, label_pad=-100):
+        """per-token log-probs and values on the R response rows (the rows whose logits predict a label != label_pad; trl reads
+        values[:, :-1] under the same mask): the fused lm-head of logps_forward(reduce_seq=False) and vlr_rm_head_fwd with the value
+        head on the same gathered rows.  Returns (tok_logp [R] fp32, values [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the sequences."""
+        _, lp = self.logps_forward(ctx, labels, None, False, label_pad, reduce_seq=False)
+        R = lp["R"]
+        if R == 0:
+            raise ValueError("ppo_forward: no response token in this (mini)batch - every label is the padding label")
+        w, b, _, _ = self.v_head_views()
+        values = torch.empty(R, dtype=torch.float32, device=self.dev)
+        _hip.call("vlr_rm_head_fwd", lp["hg"], self.H, self._row_range(R), w, b, values, R, self.H)
+        return lp["tok"], values, lp
+
+    def ppo_backward(self, lp, dlogp, dvalues):
+        """d tok_logp [R], d values [R] -> d hidden (dense [M,H], zero outside the response rows), the lm_head weight gradient (full
+        fine-tune) and the value head's gradients.  The lm-head backward is logps_backward's with every row its own sequence; the value
+        head adds g_r * w onto the same gathered d hg before the scatter (vlr_v_head_bwd)."""
+        ctx = lp["ctx"]
+        M, H, V, R = ctx["M"], self.H, self.V, lp["R"]
+        if R == 0:
+            raise ValueError("ppo_backward: no response token in this (mini)batch")
+        acc = int(not self.grad_fresh)
+        dhidden = torch.zeros(M, H, dtype=BF16, device=self.dev)
+        fused = bool(_hip.helper("vlr_lmhead_is_fused", R, V, H))
+        lws = self._buf(("lmhead_ws", ctx["tag"], R), (int(_hip.lib().vlr_lmhead_workspace_bytes(R, V)),), torch.uint8)
+        logits = None if fused else self._buf(("logits", ctx["tag"], R), (R, V), torch.float32)
+        dl = self._buf(("dlogits", R), (R, V))
+        _hip.call("vlr_lmhead_logps_bwd", lp["hg"], ctx["ws"].v["lm_head"], lp["tgt"], lp["lse"], self._row_range(R + 1), R,
+                  dlogp.to(torch.float32).contiguous(), 0, dl, lws, logits, R, V, H)
+        dhg = torch.empty(R, H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_gemm_bf16", 1, dl, ctx["ws"].v["lm_head"], dhg, None, None, R, H, V, V, H, H, 0, 0, 0, 0)
+        if self.lora is None:                 # under LoRA the lm_head is frozen (not a target module)
+            _hip.call("vlr_gemm_bf16", 2, dl, lp["hg"], self.gv["lm_head"], None, None, V, H, R, V, H, H, 0, 0, acc, 0)
+        w, _, gw, gb = self.v_head_views()
+        vws = self._buf(("v_head_ws", R), (int(_hip.lib().vlr_v_head_bwd_workspace_bytes(R, H)),), torch.uint8)
+        _hip.call("vlr_v_head_bwd", lp["hg"], w, dvalues.to(torch.float32).contiguous(), dhg, gw, gb, acc, vws, R, H)
+        _hip.call("vlr_scatter_rows", dhg, lp["rows"], dhidden, R, H)
+        if self.reducer is not None and self.lora is None:
+            self.reducer.bucket_ready("lm_head")
         return dhidden
 
     def logits_mean(self, ctx, lo, hi):

@@ -13,13 +13,13 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, gptq
-from ...base.collator import VLDPODataCollatorWithPadding, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
-from ...base.model import VLRewardModel
+from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine import BF16, LlavaHipEngine, WeightSet
 from ...utils.common import flatten_list
-from ..utils import ModelCoreMapper
+from ..utils import ModelCoreMapper, PPOCore
 
 
 @dataclass
@@ -910,6 +910,37 @@ class LlavaRMDataCollatorWithPadding(VLRMDataCollatorWithPadding):
 
 class LlavaRMTrainer(VLRMTrainer):
     ...
+
+
+class LlavaForPPO(LlavaForRL):
+    """LlavaForRL whose engine carries the PPO value head in its trainable buffers (cfg["v_head"]): the base model of LlavaWithValueHead"""
+
+    def __init__(self, cfg: dict, **kw):
+        super().__init__(dict(cfg, v_head=True), **kw)
+
+
+class LlavaWithValueHead(VLModelWithValueHead):
+    """reference Llava/__init__.py LlavaWithValueHead: the policy of PPO, v_head.summary on every position's final hidden state"""
+    base_cls = LlavaForPPO
+    image_count_key = "image_token"
+
+
+@dataclass
+class LlavaPPODataCollator(VLPPODataCollator):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """reference :466-471: the rows' images as `pixel_values` [n, 3, s, s]"""
+        batch = super().__call__(features)
+        ip = self.processor.image_processor if self.processor is not None else None
+        batch["pixel_values"] = load_pixel_values(flatten_list(batch["img_path"]), ip)
+        return batch
+
+
+class LlavaPPOTrainer(VLPPOTrainer):
+    ...
+
+
+# The PPO record of this package.  ModelCoreMapper's value_model / ppo_collator / ppo_trainer slots stay None (models/utils.py says why).
+ppo_core = PPOCore(value_model=LlavaWithValueHead, collator=LlavaPPODataCollator, trainer=LlavaPPOTrainer)
 
 
 core_mapper = ModelCoreMapper(

@@ -15,14 +15,14 @@ from typing import Any, Dict, List, Optional, Union
 import torch
 
 from ... import gptq
-from ...base.collator import VLDPODataCollatorWithPadding, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
-from ...base.model import VLRewardModel
+from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
+from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine_qwen import QwenVLHipEngine
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
-from ..utils import ModelCoreMapper
+from ..utils import ModelCoreMapper, PPOCore
 
 IGNORE_TOKEN_ID = -100           # transformers LabelSmoother.ignore_index
 
@@ -395,6 +395,38 @@ class QwenVLRMDataCollatorWithPadding(VLRMDataCollatorWithPadding):
 
 class QwenVLRMTrainer(VLRMTrainer):
     ...
+
+
+class QwenVLForPPO(QwenVLForRL):
+    """QwenVLForRL whose engine carries the PPO value head in its trainable buffers (cfg["v_head"]): the base model of QwenVLWithValueHead"""
+
+    def __init__(self, cfg: dict, **kw):
+        super().__init__(dict(cfg, v_head=True), **kw)
+
+
+class QwenVLWithValueHead(VLModelWithValueHead):
+    """reference QwenVL/__init__.py QwenVLWithValueHead: the policy of PPO, v_head.summary on every position's final hidden state"""
+    base_cls = QwenVLForPPO
+    image_count_key = "image_start_id"
+
+
+@dataclass
+class QwenVLPPODataCollator(VLPPODataCollator):
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        """the reference's class adds nothing (Qwen-VL reads its images from the paths inside the ids); here the images the rows name are
+        loaded once per batch, as the other Qwen-VL collators do, so that the step's passes do not open the files again"""
+        batch = super().__call__(features)
+        size = getattr(self.processor, "image_size", None) or 448
+        batch["pixel_values"] = load_qwen_pixel_values(flatten_list(batch["img_path"]), size)
+        return batch
+
+
+class QwenVLPPOTrainer(VLPPOTrainer):
+    ...
+
+
+# The PPO record of this package.  ModelCoreMapper's value_model / ppo_collator / ppo_trainer slots stay None (models/utils.py says why).
+ppo_core = PPOCore(value_model=QwenVLWithValueHead, collator=QwenVLPPODataCollator, trainer=QwenVLPPOTrainer)
 
 
 core_mapper = ModelCoreMapper(

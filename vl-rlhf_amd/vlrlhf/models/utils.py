@@ -1,6 +1,10 @@
 """Per-model registry record (mirror of /root/reference/src/vlrlhf/models/utils.py:18-31).  The DPO and SFT slots are filled by every
 model package, the reward slots by LLaVA-1.5 and Qwen-VL; the PPO / value slots stay in the record so a reference user finds the same
-twelve fields, and are None."""
+twelve fields, and are None.
+
+PPO is registered through a record of its own, `ppo_core` (PPOCore: value model, collator, trainer), exported by the packages that cover it
+(LLaVA-1.5, Qwen-VL) and resolved by utils/auto_load.py (PPO_FAMILIES, MyAutoModelWithValueHead, MyAutoPPOCollator, MyAutoPPOTrainer):
+auto_core_mapper hands a ModelCoreMapper out for all four families, and callers read a filled slot as "this family has the stage"."""
 from dataclasses import dataclass
 from typing import Any
 
@@ -19,3 +23,10 @@ class ModelCoreMapper:
     sft_trainer: Any = None
     ppo_collator: Any = None
     ppo_trainer: Any = None
+
+
+@dataclass
+class PPOCore:
+    value_model: Any
+    collator: Any = None
+    trainer: Any = None

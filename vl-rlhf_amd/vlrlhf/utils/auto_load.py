@@ -94,6 +94,49 @@ class MyAutoRMTrainer:
         return _reward_slot(_architecture(model_name_or_path), "reward_trainer")(*args, **kwargs)
 
 
+PPO_FAMILIES = ["Llava", "QwenVL"]      # the families of the reward model: PPO scores its samples with one
+
+
+def _ppo_slot(architecture: str, slot: str):
+    """the PPO record of a model package (`ppo_core`, models/utils.py PPOCore) - not ModelCoreMapper, whose PPO slots stay None"""
+    nick = MODEL_NICKNAME_MAP[architecture]
+    if nick not in PPO_FAMILIES:
+        raise NotImplementedError(f"{nick}: PPO on the MI355X path covers {PPO_FAMILIES} (LLaVA-1.5 and Qwen-VL) only")
+    got = getattr(import_module(f".{nick}", "vlrlhf.models").ppo_core, slot)
+    if got is None:
+        raise NotImplementedError(f"{nick}: the PPO {slot} is not built on the MI355X path yet (the value-head model and the trainer's step are)")
+    return got
+
+
+class MyAutoModelWithValueHead:
+    @classmethod
+    def from_pretrained(cls, model_name_or_path, *args, **kwargs):
+        return _ppo_slot(_architecture(model_name_or_path), "value_model").from_pretrained(model_name_or_path, *args, **kwargs)
+
+
+class MyAutoPPOTrainer:
+    def __new__(cls, model_name_or_path, *args, **kwargs):
+        return _ppo_slot(_architecture(model_name_or_path), "trainer")(*args, **kwargs)
+
+
+class MyAutoPPOCollator:
+    def __new__(cls, model_name_or_path, processor=None):
+        return _ppo_slot(_architecture(model_name_or_path), "collator")(processor)
+
+
+class MyAutoGenerationConfig:
+    @classmethod
+    def from_pretrained(cls, model_name_or_path):
+        """the checkpoint's generation_config.json with the family's defaults filled in by the wrapper's
+        prepare_default_generation_kwargs (Qwen-VL: stop_words_ids ...) - a plain attribute bag, which is all `generate` reads.  (The
+        reference's ppo.py imports a class of this name that its auto_load does not define.)"""
+        from ..eval.utils import read_generation_config
+        model_cls = auto_core_mapper(_architecture(model_name_or_path)).model
+        gc = read_generation_config(model_name_or_path)
+        out = model_cls.prepare_default_generation_kwargs(None, gc)      # (the method reads nothing of the instance)
+        return out.get("generation_config", gc)
+
+
 def auto_load_rlmodel(script_args, training_args, lora_args):
     """-> (model, ref_model=None, lora_config); vision tower frozen (reference :554-555; freeze_vision_tower=False raises).  With use_lora the LoraConfig of
     reference :559-571 is returned as a plain dict (peft itself is not needed: the trainer hands it to
