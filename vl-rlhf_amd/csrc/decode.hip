@@ -10,6 +10,9 @@
 //                        meet in LDS in a fixed order.  K slices (split-K, enough workgroups to cover the chip at N = 4096) write
 //                        fp32 partials; gemv_epilogue_kernel sums them in slice order and applies the epilogue: no atomics, the
 //                        result is bit-reproducible.
+//   gemv_wide_kernel     gemv_kernel for 17 .. 64 rows in ONE pass over W (batches of 32 - 64 sampled sequences): gemv_tile<MT> feeds a lane's
+//                        W fragments to MT = ceil(M / 16) row tiles; grid, chunk order, folds and partial layout are gemv_kernel's, so the
+//                        result is bit for bit that of gemv_kernel on rows [0, 16), [16, 32), ...  (gemv_wide_lora_kernel: with the adapter)
 //   gemv_w4_kernel       the same product with W read PACKED (GPTQ int4, gptq.h): a quarter of the weight bytes.  One int32 of qweight
 //                        is 8 consecutive k of one column - exactly one lane's B fragment of the MFMA - so a lane loads 16 bytes (4
 //                        columns x 8 k), unpacks them to bf16 in registers by the rule of gptq.h and feeds four MFMAs.  Same partials,
@@ -35,15 +38,24 @@ constexpr int GV_TARGET_WGS = 1024;  // split K until about this many workgroups
 
 __device__ __forceinline__ bf16x8 load8(const bf16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(p)); }
 
-// one workgroup's (64 columns, K slice `split`) share of the product; red: the workgroup's LDS
+// one workgroup's (64 columns, K slice `split`) share of the product for MT row tiles of 16 (M <= 16 MT); red: the workgroup's LDS.
+// A lane's four W fragments of a k step are loaded once and feed MT x 4 MFMAs: only the X fragments and the accumulators grow with
+// MT.  Row m = 16 mt + r sees the chunks, the k steps and the four-wave fold of the MT = 1 form in the same order, so its sums do not
+// depend on MT.  The fold runs one row tile at a time through the same 16 KB of LDS.
+template <int MT>
 __device__ __forceinline__ void gemv_tile(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W, float* __restrict__ part,
                                           int M, int N, int K, int cps, int n0, int split, float (*red)[16][GV_COLS]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
     const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
-    const bool mok = r < M;
-    const bf16_t* xrow = X + (size_t)(mok ? r : 0) * ldx;
+    bool mok[MT];
+    const bf16_t* xrow[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        mok[mt] = 16 * mt + r < M;
+        xrow[mt] = X + (size_t)(mok[mt] ? 16 * mt + r : 0) * ldx;
+    }
     const bf16_t* wrow[4];
     bool nok[4];
 #pragma unroll
@@ -52,44 +64,61 @@ __device__ __forceinline__ void gemv_tile(const bf16_t* __restrict__ X, int ldx,
         nok[t] = n < N;
         wrow[t] = W + (size_t)(nok[t] ? n : 0) * K;
     }
-    f32x4 acc[4];
+    f32x4 acc[MT][4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
-    // lane (r, g) holds A[m = r][k = 8 g + j] (X) and B[k = 8 g + j][n = r] (a row of W) of every 32-k step
+    // lane (r, g) holds A[m = 16 mt + r][k = 8 g + j] (X) and B[k = 8 g + j][n = r] (a row of W) of every 32-k step
     for (int c = c0 + wv; c < c1; c += 4) {
-        bf16x8 a[4], b[4][4];
+        bf16x8 a[4][MT], b[4][4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int k = c * GV_CHUNK + u * 32 + g * 8;
             const bool kok = k < K;                        // K % 8 == 0: a lane's 8 k are all in or all out
-            a[u] = (mok && kok) ? load8(xrow + k) : zero;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) a[u][mt] = (mok[mt] && kok) ? load8(xrow[mt] + k) : zero;
 #pragma unroll
             for (int t = 0; t < 4; ++t) b[u][t] = (nok[t] && kok) ? load8(wrow[t] + k) : zero;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[u][t], acc[t], 0, 0, 0);
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u][mt], b[u][t], acc[mt][t], 0, 0, 0);
     }
-    // D map: lane holds D[m = 4 g + i][n = r] of each n tile
+    // D map: lane holds D[m = 16 mt + 4 g + i][n = r] of each n tile
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int mt = 0; mt < MT; ++mt) {
+        if (mt) __syncthreads();                           // the previous row tile has been folded
 #pragma unroll
-        for (int i = 0; i < 4; ++i) red[wv][4 * g + i][t * 16 + r] = acc[t][i];
-    __syncthreads();
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int idx = threadIdx.x + 256 * e, m = idx / GV_COLS, n = idx % GV_COLS;
-        if (m < M && n0 + n < N)
-            part[((size_t)split * M + m) * N + n0 + n] = ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n];
+            for (int i = 0; i < 4; ++i) red[wv][4 * g + i][t * 16 + r] = acc[mt][t][i];
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int idx = threadIdx.x + 256 * e, ml = idx / GV_COLS, m = 16 * mt + ml, n = idx % GV_COLS;
+            if (m < M && n0 + n < N)
+                part[((size_t)split * M + m) * N + n0 + n] = ((red[0][ml][n] + red[1][ml][n]) + red[2][ml][n]) + red[3][ml][n];
+        }
     }
 }
 
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
                                                    float* __restrict__ part, int M, int N, int K, int cps) {
     __shared__ float red[4][16][GV_COLS];
-    gemv_tile(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
+    gemv_tile<1>(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
+}
+
+// the wide form: 17 .. 64 rows (MT = 2 .. 4 row tiles) in ONE pass over W; same grid, chunk assignment and partial layout [slice][M][N]
+template <int MT>
+__global__ __launch_bounds__(256) void gemv_wide_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
+                                                        float* __restrict__ part, int M, int N, int K, int cps) {
+    __shared__ float red[4][16][GV_COLS];
+    gemv_tile<MT>(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
 }
 
 // ---- live LoRA adapters (peft lora.Linear, un-merged): y = x W^T + u B^T with u = bf16(scale * x A^T), for `targets` sub-targets
@@ -116,8 +145,10 @@ __device__ __forceinline__ int lora_target(const GemvLora& lo, int n) { return (
 // COLS output columns from n0 on; ub: COLS * 256 bytes of LDS = 16 rows x COLS * 8 bf16 columns of u.  The column block spans the
 // targets t_lo .. t_hi (one, or two where a target edge falls inside it); the rank is walked in chunks of RC columns per spanned target
 // so that any r fits (one chunk whenever (t_hi - t_lo + 1) * r <= COLS * 8: every shipped configuration); j stays ascending across chunks
+// The 16 rows are rows mbase .. mbase + M - 1 of the call's Mtot (the wide form walks its row tiles; the 16-row calls pass M, 0)
 template <int COLS>
-__device__ __forceinline__ void gemv_lora_slice(const GemvLora& lo, float* __restrict__ slice, int M, int N, int n0, bf16_t* ub) {
+__device__ __forceinline__ void gemv_lora_slice(const GemvLora& lo, float* __restrict__ slice, int M, int N, int n0, bf16_t* ub, int Mtot,
+                                                int mbase) {
     constexpr int RP = 16 * COLS / 256;                      // rows of m per thread
     constexpr int CAP = COLS * 8;                            // bf16 columns of u per row the LDS holds
     const int nlast = min(n0 + COLS, N) - 1;
@@ -136,7 +167,7 @@ __device__ __forceinline__ void gemv_lora_slice(const GemvLora& lo, float* __res
         for (int idx = threadIdx.x; idx < M * nt * rc; idx += 256) {
             const int m = idx / (nt * rc), c = idx % (nt * rc), tt = c / rc, j = c % rc;
             float s = 0.f;
-            for (int k = 0; k < lo.Su; ++k) s += lo.upart[((size_t)k * M + m) * lo.R + (t_lo + tt) * lo.r + jc + j];     // split order: fixed
+            for (int k = 0; k < lo.Su; ++k) s += lo.upart[((size_t)k * Mtot + mbase + m) * lo.R + (t_lo + tt) * lo.r + jc + j];     // split order: fixed
             ub[m * Wd + tt * RC + j] = f32_to_bf16(lo.scale * s);
         }
         __syncthreads();
@@ -157,15 +188,29 @@ __device__ __forceinline__ void gemv_lora_slice(const GemvLora& lo, float* __res
     if (!nok) return;
 #pragma unroll
     for (int i = 0; i < RP; ++i)
-        if (m0 + i < M) slice[(size_t)(m0 + i) * N + n] = acc[i];
+        if (m0 + i < M) slice[(size_t)(mbase + m0 + i) * N + n] = acc[i];
 }
 
 // grid (column blocks, S + 1): slices 0 .. S - 1 are gemv_kernel's, slice S the adapter term
 __global__ __launch_bounds__(256) void gemv_lora_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
                                                         float* __restrict__ part, int M, int N, int K, int cps, int S, GemvLora lo) {
     __shared__ float red[4][16][GV_COLS];
-    if ((int)blockIdx.y == S) gemv_lora_slice<GV_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GV_COLS, (bf16_t*)&red[0][0][0]);
-    else gemv_tile(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
+    if ((int)blockIdx.y == S) gemv_lora_slice<GV_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GV_COLS, (bf16_t*)&red[0][0][0], M, 0);
+    else gemv_tile<1>(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
+}
+
+// the wide form: the adapter slice walks the row tiles through the 16-row code (per row: the same rank chunks, j ascending, u rounded once)
+template <int MT>
+__global__ __launch_bounds__(256) void gemv_wide_lora_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ W,
+                                                             float* __restrict__ part, int M, int N, int K, int cps, int S, GemvLora lo) {
+    __shared__ float red[4][16][GV_COLS];
+    if ((int)blockIdx.y == S) {
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt) __syncthreads();                       // the previous tile's u has been read
+            gemv_lora_slice<GV_COLS>(lo, part + (size_t)S * M * N, min(16, M - 16 * mt), N, blockIdx.x * GV_COLS, (bf16_t*)&red[0][0][0], M,
+                                     16 * mt);
+        }
+    } else gemv_tile<MT>(X, ldx, W, part, M, N, K, cps, blockIdx.x * GV_COLS, blockIdx.y, red);
 }
 
 struct GemvEpi {
@@ -414,10 +459,10 @@ extern "C" long vlr_gemv_workspace_bytes(int M, int N, int K) {
 // the argument rules and the epilogue launch the bf16 and the packed skinny GEMM share
 static int gemv_check(const char* fn, int mode, const void* X, int ldx, const void* Y, int ldy, const void* bias, const void* residual,
                       int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M,
-                      int N, int K, const void* workspace) {
+                      int N, int K, const void* workspace, int max_rows = 16) {
     VLR_REQUIRE(mode >= VLR_GEMV_BF16 && mode <= VLR_GEMV_SWIGLU, "%s: unknown mode %d", fn, mode);
     VLR_REQUIRE(X && Y && workspace, "%s: null argument", fn);
-    VLR_REQUIRE(M >= 1 && M <= 16, "%s: M = %d rows, the skinny GEMM takes 1 <= M <= 16", fn, M);
+    VLR_REQUIRE(M >= 1 && M <= max_rows, "%s: M = %d rows, the skinny GEMM takes 1 <= M <= %d", fn, M, max_rows);
     VLR_REQUIRE(K >= 8 && K % 8 == 0, "%s: K = %d must be a positive multiple of 8", fn, K);
     VLR_REQUIRE(N >= 1 && ldx >= K && ldx % 8 == 0 && ((uintptr_t)X & 15) == 0, "%s: N %d, ldx %d (>= K, multiple of 8) and 16-byte aligned X required",
                 fn, N, ldx);
@@ -444,19 +489,51 @@ static void gemv_epilogue(int mode, const void* workspace, int S, void* Y, int l
     hipLaunchKernelGGL(gemv_epilogue_kernel, dim3((M * units + 255) / 256), dim3(256), 0, st, p, units);
 }
 
+// the product launch for any M <= 64: the 16-row kernel itself up to 16 rows, else one pass over W for all ceil(M / 16) row tiles
+static void gemv_launch(dim3 grid, hipStream_t st, const void* X, int ldx, const void* W, void* part, int M, int N, int K, int cps) {
+    const bf16_t* x = (const bf16_t*)X;
+    const bf16_t* w = (const bf16_t*)W;
+    float* p = (float*)part;
+    switch ((M + 15) / 16) {
+        case 1: hipLaunchKernelGGL(gemv_kernel, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps); break;
+        case 2: hipLaunchKernelGGL(gemv_wide_kernel<2>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps); break;
+        case 3: hipLaunchKernelGGL(gemv_wide_kernel<3>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps); break;
+        default: hipLaunchKernelGGL(gemv_wide_kernel<4>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps); break;
+    }
+}
+
+static int gemv_bf16_rows(const char* fn, int max_rows, int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias,
+                          const void* residual, int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim,
+                          int max_pos, int M, int N, int K, void* workspace, hipStream_t st) {
+    const int rc = gemv_check(fn, mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K,
+                              workspace, max_rows);
+    if (rc != VLR_OK) return rc;
+    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "%s: W must be non-null and 16-byte aligned", fn);
+    const int S = gemv_splits(N, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    gemv_launch(dim3((N + GV_COLS - 1) / GV_COLS, S), st, X, ldx, W, workspace, M, N, K, cps);
+    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch(fn);
+}
+
 extern "C" int vlr_gemv_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
                              int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
                              int M, int N, int K, void* workspace, vlr_stream_t st) {
-    const int rc = gemv_check("vlr_gemv_bf16", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos,
-                              M, N, K, workspace);
-    if (rc != VLR_OK) return rc;
-    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "vlr_gemv_bf16: W must be non-null and 16-byte aligned");
-    const int S = gemv_splits(N, K);
-    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
-    hipLaunchKernelGGL(gemv_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
-                       (float*)workspace, M, N, K, cps);
-    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
-    return vlr_check_launch("vlr_gemv_bf16");
+    return gemv_bf16_rows("vlr_gemv_bf16", 16, mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M,
+                          N, K, workspace, st);
+}
+
+// ---- the wide entry points: the argument lists of their 16-row namesakes, 1 <= M <= 64 rows in one pass over W.  Bit for bit the
+// 16-row entry point on rows [0, 16), [16, 32), ... (gemv_tile).  Workspace: the same split count times min(M, 64) rows.
+extern "C" long vlr_gemv_wide_workspace_bytes(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 8) return 0;
+    return (long)gemv_splits(N, K) * (M > 64 ? 64 : M) * N * 4;
+}
+extern "C" int vlr_gemv_wide_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
+                                  int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos,
+                                  int M, int N, int K, void* workspace, vlr_stream_t st) {
+    return gemv_bf16_rows("vlr_gemv_wide_bf16", 64, mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim,
+                          max_pos, M, N, K, workspace, st);
 }
 
 // ---- the adapter entry points.  Workspace: one more fp32 slice than the adapter-free call; u scratch: the split-K partials of x A^T
@@ -487,10 +564,36 @@ static int gemv_lora_prepare(const char* fn, const void* X, int ldx, const void*
     for (int t = targets; t < 4; ++t) edge[t + 1] = N;
     const int R = targets * r, Su = gemv_splits(R, K);
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + Su - 1) / Su;
-    hipLaunchKernelGGL(gemv_kernel, dim3((R + GV_COLS - 1) / GV_COLS, Su), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)A,
-                       (float*)u, M, R, K, cps);
+    gemv_launch(dim3((R + GV_COLS - 1) / GV_COLS, Su), st, X, ldx, A, u, M, R, K, cps);
     *lo = GemvLora{(const float*)u, (const bf16_t*)B, Su, r, R, targets, edge[1], edge[2], edge[3], scale};      // edge[targets] = N: no row beyond it
     return VLR_OK;
+}
+
+static int gemv_bf16_lora_rows(const char* fn, int max_rows, int mode, const void* X, int ldx, const void* W, void* Y, int ldy,
+                               const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t, const float* sin_t,
+                               int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace, const void* A, const void* B,
+                               int r, int targets, const int* outs, float scale, void* u, hipStream_t st) {
+    const int rc = gemv_check(fn, mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K,
+                              workspace, max_rows);
+    if (rc != VLR_OK) return rc;
+    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "%s: W must be non-null and 16-byte aligned", fn);
+    GemvLora lo;
+    const int rl = gemv_lora_prepare(fn, X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
+    if (rl != VLR_OK) return rl;
+    const int S = gemv_splits(N, K);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    const dim3 grid((N + GV_COLS - 1) / GV_COLS, S + 1);
+    const bf16_t* x = (const bf16_t*)X;
+    const bf16_t* w = (const bf16_t*)W;
+    float* p = (float*)workspace;
+    switch ((M + 15) / 16) {
+        case 1: hipLaunchKernelGGL(gemv_lora_kernel, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps, S, lo); break;
+        case 2: hipLaunchKernelGGL(gemv_wide_lora_kernel<2>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps, S, lo); break;
+        case 3: hipLaunchKernelGGL(gemv_wide_lora_kernel<3>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps, S, lo); break;
+        default: hipLaunchKernelGGL(gemv_wide_lora_kernel<4>, grid, dim3(256), 0, st, x, ldx, w, p, M, N, K, cps, S, lo); break;
+    }
+    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch(fn);
 }
 
 extern "C" int vlr_gemv_bf16_lora(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual,
@@ -499,19 +602,26 @@ extern "C" int vlr_gemv_bf16_lora(int mode, const void* X, int ldx, const void* 
                                   float scale, void* u, vlr_stream_t st) {
     if (!A && !B)      // not adapted: the adapter-free call itself
         return vlr_gemv_bf16(mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K, workspace, st);
-    const int rc = gemv_check("vlr_gemv_bf16_lora", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim,
-                              max_pos, M, N, K, workspace);
-    if (rc != VLR_OK) return rc;
-    VLR_REQUIRE(W && ((uintptr_t)W & 15) == 0, "vlr_gemv_bf16_lora: W must be non-null and 16-byte aligned");
-    GemvLora lo;
-    const int rl = gemv_lora_prepare("vlr_gemv_bf16_lora", X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
-    if (rl != VLR_OK) return rl;
-    const int S = gemv_splits(N, K);
-    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
-    hipLaunchKernelGGL(gemv_lora_kernel, dim3((N + GV_COLS - 1) / GV_COLS, S + 1), dim3(256), 0, st, (const bf16_t*)X, ldx, (const bf16_t*)W,
-                       (float*)workspace, M, N, K, cps, S, lo);
-    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
-    return vlr_check_launch("vlr_gemv_bf16_lora");
+    return gemv_bf16_lora_rows("vlr_gemv_bf16_lora", 16, mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim,
+                               max_pos, M, N, K, workspace, A, B, r, targets, outs, scale, u, st);
+}
+
+// the wide adapter call: x A^T is the wide kernel on A, the adapter slice walks the row tiles (gemv_wide_lora_kernel)
+extern "C" long vlr_gemv_wide_lora_u_bytes(int M, int K, int r_total) { return vlr_gemv_wide_workspace_bytes(M, r_total, K); }
+extern "C" long vlr_gemv_wide_lora_workspace_bytes(int M, int N, int K, int r_total) {
+    if (M < 1 || N < 1 || K < 8 || r_total < 8 || r_total % 8) return 0;
+    const int s = gemv_splits(N, K), s4 = gemv_splits(N, K, 2 * GV_COLS);       // vlr_gemv_lora_workspace_bytes' rule: equal to it at M <= 16
+    return (long)((s > s4 ? s : s4) + 1) * (M > 64 ? 64 : M) * N * 4;
+}
+extern "C" int vlr_gemv_wide_bf16_lora(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias,
+                                       const void* residual, int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols,
+                                       int head_dim, int max_pos, int M, int N, int K, void* workspace, const void* A, const void* B, int r,
+                                       int targets, const int* outs, float scale, void* u, vlr_stream_t st) {
+    if (!A && !B)
+        return vlr_gemv_wide_bf16(mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K,
+                                  workspace, st);
+    return gemv_bf16_lora_rows("vlr_gemv_wide_bf16_lora", 64, mode, X, ldx, W, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
+                               head_dim, max_pos, M, N, K, workspace, A, B, r, targets, outs, scale, u, st);
 }
 
 // ---- the skinny GEMM over packed int4 weights.  A workgroup owns 128 output columns (two halves of 64) and one K slice.  Lane (r, g)
@@ -616,7 +726,7 @@ __global__ __launch_bounds__(256) void gemv_w4_lora_kernel(const bf16_t* __restr
                                                            float* __restrict__ part, int M, int N, int K, int gsz, int cps, int S,
                                                            GemvLora lo) {
     __shared__ float red[4][16][GW_COLS];
-    if ((int)blockIdx.y == S) gemv_lora_slice<GW_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GW_COLS, (bf16_t*)&red[0][0][0]);
+    if ((int)blockIdx.y == S) gemv_lora_slice<GW_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GW_COLS, (bf16_t*)&red[0][0][0], M, 0);
     else gemv_w4_tile<PER_STEP>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
 }
 

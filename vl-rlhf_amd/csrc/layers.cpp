@@ -113,15 +113,17 @@ extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_w
 }
 
 // ---- one decoder layer for one new token per sequence against its KV cache (vlr_decoder_layer_fwd_ex's arithmetic at M = batch rows,
-// the key side read from the cache).  The skinny GEMMs take at most 16 rows: larger batches run them in 16-row groups.
+// the key side read from the cache).  The skinny GEMMs take at most 16 rows: larger batches run them in 16-row groups, or (`wide`:
+// bf16 weights and scratch sized for it) in 64-row groups through the wide entry points - one pass over W per 64 rows, the same bits.
 // W: the bf16 matrix, or (q != NULL) the packed int4 linear of a GPTQ base (vlr_gemv_w4)
 // ad != NULL with ad->A: the live adapter of the projection (vlr_gemv_*_lora)
 struct GemvAdapter { const void* A; const void* B; int r, targets; const int* outs; float scale; void* u; };
 static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_w4_linear* q, void* Y, int ldy, size_t ysz, const void* bias,
                      const void* res, int ldr, size_t rsz, const int* pos, const vlr_llama_cfg* cfg, int rope_cols, int M, int N, int K,
-                     void* ws, hipStream_t st, const GemvAdapter* ad = nullptr) {
-    for (int m0 = 0; m0 < M; m0 += 16) {
-        const int mr = M - m0 < 16 ? M - m0 : 16;
+                     void* ws, hipStream_t st, const GemvAdapter* ad = nullptr, bool wide = false) {
+    const int rows = wide && !q ? 64 : 16;
+    for (int m0 = 0; m0 < M; m0 += rows) {
+        const int mr = M - m0 < rows ? M - m0 : rows;
         const void* x = (const char*)X + (size_t)m0 * ldx * 2;
         void* y = (char*)Y + (size_t)m0 * ldy * ysz;
         const void* r = res ? (const char*)res + (size_t)m0 * ldr * rsz : nullptr;
@@ -130,6 +132,12 @@ static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_
             CHECK(vlr_gemv_w4_lora(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
                                    cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets,
                                    ad->outs, ad->scale, ad->u, st));
+        else if (ad && ad->A && rows == 64)
+            CHECK(vlr_gemv_wide_bf16_lora(mode, x, ldx, W, y, ldy, bias, r, ldr, p, cfg->rope_cos, cfg->rope_sin, rope_cols, cfg->head_dim,
+                                          cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets, ad->outs, ad->scale, ad->u, st));
+        else if (rows == 64)
+            CHECK(vlr_gemv_wide_bf16(mode, x, ldx, W, y, ldy, bias, r, ldr, p, cfg->rope_cos, cfg->rope_sin, rope_cols, cfg->head_dim,
+                                     cfg->max_pos, mr, N, K, ws, st));
         else if (ad && ad->A)
             CHECK(vlr_gemv_bf16_lora(mode, x, ldx, W, y, ldy, bias, r, ldr, p, cfg->rope_cos, cfg->rope_sin, rope_cols, cfg->head_dim,
                                      cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets, ad->outs, ad->scale, ad->u, st));
@@ -177,6 +185,15 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     long need = bytes(mb, N, H);
     const long shapes[3] = {bytes(mb, H, Nq), bytes(mb, 2 * I, H), bytes(mb, H, I)};
     for (long b : shapes) need = b > need ? b : need;
+    // the 64-row groups: more than 16 rows of bf16 weights, and scratch that covers the wide sizes (else the 16-row groups, as ever)
+    const int mw = batch < 64 ? batch : 64;
+    bool wide = batch > 16 && !q4;
+    long need_w = 0;
+    if (wide) {
+        const long wshapes[4] = {vlr_gemv_wide_workspace_bytes(mw, N, H), vlr_gemv_wide_workspace_bytes(mw, H, Nq),
+                                 vlr_gemv_wide_workspace_bytes(mw, 2 * I, H), vlr_gemv_wide_workspace_bytes(mw, H, I)};
+        for (long b : wshapes) need_w = b > need_w ? b : need_w;
+    }
     GemvAdapter a_qkv{}, a_o{}, a_gu{}, a_down{};
     const int o_qkv[3] = {Nq, Nkv, Nkv};
     if (lw) {
@@ -197,7 +214,19 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
                                  lw->a_down ? vlr_gemv_lora_u_bytes(mb, I, r) : 0};
         for (long b : ushapes) need_u = b > need_u ? b : need_u;
         VLR_REQUIRE(lws->u_bytes >= need_u, "%s: the adapter scratch u has %ld bytes, %ld needed", fn, lws->u_bytes, need_u);
+        if (wide) {
+            const long wl[4] = {vlr_gemv_wide_lora_workspace_bytes(mw, N, H, nq * r), vlr_gemv_wide_lora_workspace_bytes(mw, H, Nq, r),
+                                vlr_gemv_wide_lora_workspace_bytes(mw, 2 * I, H, 2 * r),
+                                lw->a_down ? vlr_gemv_wide_lora_workspace_bytes(mw, H, I, r) : 0};
+            for (long b : wl) need_w = b > need_w ? b : need_w;
+            long need_wu = 0;
+            const long wu[4] = {vlr_gemv_wide_lora_u_bytes(mw, H, nq * r), vlr_gemv_wide_lora_u_bytes(mw, Nq, r),
+                                vlr_gemv_wide_lora_u_bytes(mw, H, 2 * r), lw->a_down ? vlr_gemv_wide_lora_u_bytes(mw, I, r) : 0};
+            for (long b : wu) need_wu = b > need_wu ? b : need_wu;
+            wide = lws->u_bytes >= need_wu;
+        }
     }
+    wide = wide && ws->gemv_ws_bytes >= need_w;
     VLR_REQUIRE(ws->gemv_ws_bytes >= need, "%s: gemv_ws has %ld bytes, %ld needed", fn, ws->gemv_ws_bytes, need);
     const long need_a = sh ? vlr_attn_decode_shared_workspace_bytes(sh->prompts, sh->fanout, cfg->heads, sh->prompt_cap, sh->tail_cap)
                            : vlr_attn_decode_workspace_bytes(batch, cfg->heads, cap);
@@ -207,7 +236,7 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     const int mode_res = rf ? VLR_GEMV_F32RES : VLR_GEMV_BF16;
     CHECK(norm_fwd(rf, x_inout, w->ln1, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
     CHECK(gemv_rows(VLR_GEMV_QKV_ROPE, ws->xn, H, w->wqkv, q4 ? &q4->qkv : nullptr, ws->qkv, N, 2, w->bqkv, nullptr, 0, 0, pos, cfg, Nq + Nkv,
-                    batch, N, H, ws->gemv_ws, st, &a_qkv));
+                    batch, N, H, ws->gemv_ws, st, &a_qkv, wide));
     CHECK(vlr_kv_cache_write(off(ws->qkv, Nq), off(ws->qkv, (size_t)Nq + Nkv), N, k_cache, v_cache, batch, 1, kvh, cfg->head_dim, cap, len, st));
     if (sh)
         CHECK(vlr_attn_decode_shared(ws->qkv, N, sh, ws->attn, Nq, ws->attn_ws, cfg->heads, kvh, cfg->head_dim,
@@ -216,12 +245,12 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
         CHECK(vlr_attn_decode_gqa(ws->qkv, N, k_cache, v_cache, key_mask, ws->attn, Nq, ws->attn_ws, batch, cfg->heads, kvh, cfg->head_dim,
                                   cap, len + 1, 1.0f / sqrtf((float)cfg->head_dim), st));
     CHECK(gemv_rows(mode_res, ws->attn, Nq, w->wo, q4 ? &q4->o : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch, H,
-                    Nq, ws->gemv_ws, st, &a_o));
+                    Nq, ws->gemv_ws, st, &a_o, wide));
     CHECK(norm_fwd(rf, x_inout, w->ln2, ws->xn, ws->rstd, batch, H, cfg->rms_eps, st));
     CHECK(gemv_rows(VLR_GEMV_SWIGLU, ws->xn, H, w->wgu, q4 ? &q4->gu : nullptr, ws->act, I, 2, nullptr, nullptr, 0, 0, nullptr, cfg, 0, batch,
-                    2 * I, H, ws->gemv_ws, st, &a_gu));
+                    2 * I, H, ws->gemv_ws, st, &a_gu, wide));
     CHECK(gemv_rows(mode_res, ws->act, I, w->wdown, q4 ? &q4->down : nullptr, x_inout, H, xs, nullptr, x_inout, H, xs, nullptr, cfg, 0, batch,
-                    H, I, ws->gemv_ws, st, &a_down));
+                    H, I, ws->gemv_ws, st, &a_down, wide));
     return VLR_OK;
 }
 extern "C" int vlr_decoder_layer_decode(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_decode_ws* ws, void* x_inout,

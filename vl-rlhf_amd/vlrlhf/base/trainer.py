@@ -1418,7 +1418,7 @@ class VLPPOTrainer:
                 continue
             queries = batch["input_ids"]
             img = {k: batch[k] for k in self.IMAGE_KEYS if k in batch}
-            responses = self.generate(queries, return_prompt=False, **img)
+            responses = self.generate(queries, return_prompt=False, batch_size=32, **img)      # reference :437-442
             batch["response"] = self.tokenizer.batch_decode(responses, skip_special_tokens=True)
             try:
                 scores = self.compute_scores(batch["query"], batch["response"], img)
@@ -1567,18 +1567,36 @@ class VLPPOTrainer:
 
     # ------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def generate(self, queries, return_prompt: bool = False, generation_kwargs=None, **img):
+    def generate(self, queries, return_prompt: bool = False, generation_kwargs=None, batch_size=None, **img):
         """trl PPOTrainer.generate on a batch, as the reference's train() calls it: the queries (1-D id tensors) are LEFT-padded, the
         model's own `generate` samples with the image inputs and `self.generation_kwargs` (updated by `generation_kwargs`), and each row
         comes back without its prompt (unless return_prompt) and without what follows its first stop: an id of `eos_token_id`, or the last
         token of a `stop_words_ids` sequence of the generation config - the rules `generate` itself ends a row by.  The stop stays in the
-        response (every response token counts in step(), the first EOS included).  Under LoRA the adapters run live (merge_lora=False)."""
-        from ..models.Llava import stop_sequences
+        response (every response token counts in step(), the first EOS included).  Under LoRA the adapters run live (merge_lora=False).
+        batch_size (trl's _generate_batched; the reference's train() passes 32): None samples all queries in one call; an integer k
+        samples them k at a time, in order - each chunk left-padded to ITS longest query, each image input that has one entry per
+        query (a tensor's first dimension, a list) sliced to the chunk's rows - and returns the responses in the queries' order."""
         kw = dict(self.generation_kwargs)
         kw.update(generation_kwargs or {})
         if self.is_peft_model:
             kw.setdefault("merge_lora", False)
         queries = [q.reshape(-1).cpu().long() for q in queries]
+        n = len(queries)
+        if batch_size is None or int(batch_size) >= n:
+            return self._generate_rows(queries, return_prompt, kw, img)
+        if int(batch_size) < 1:
+            raise ValueError(f"generate: batch_size must be a positive integer, got {batch_size}")
+        responses = []
+        for lo in range(0, n, int(batch_size)):
+            hi = min(n, lo + int(batch_size))
+            part = {k: (v[lo:hi] if (isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == n) or
+                        (isinstance(v, (list, tuple)) and len(v) == n) else v) for k, v in img.items()}
+            responses += self._generate_rows(queries[lo:hi], return_prompt, kw, part)
+        return responses
+
+    def _generate_rows(self, queries, return_prompt, kw, img):
+        """one call of the model's generate on `queries` (cpu id rows), left-padded to the longest -> the responses, cut at their stop"""
+        from ..models.Llava import stop_sequences
         n, T0, dev = len(queries), max(int(q.numel()) for q in queries), self.accelerator.device
         ids = torch.full((n, T0), self.padding_value, dtype=torch.long)
         mask = torch.zeros(n, T0, dtype=torch.long)

@@ -375,7 +375,9 @@ class KVCache:
     (0 = padded key, the merge's convention), `len` = filled columns (the same for every row), `pos` [B] int32 = each row's NEXT position.
 
     Positions follow the merge (cumsum(mask) - 1 on the attended rows), so a new token's position is the number of attended columns of
-    its row.  The buffers are allocated by `reserve(S)` once the prompt's merged length S is known: capacity = S + `new_tokens`."""
+    its row - unless the engine that made the cache says otherwise: `position_rule` (engine.kv_next_positions, set by
+    engine.new_kv_cache / new_shared_kv_cache; None = the rule above) gives the first new token's position from the mask.
+    The buffers are allocated by `reserve(S)` once the prompt's merged length S is known: capacity = S + `new_tokens`."""
 
     def __init__(self, layers, batch, kv_heads, head_dim, new_tokens, device="cuda"):
         self.L, self.B, self.kv_heads, self.head_dim = int(layers), int(batch), int(kv_heads), int(head_dim)
@@ -384,6 +386,7 @@ class KVCache:
         self.cap = 0
         self.len = 0
         self.k = self.v = self.key_mask = self.pos = None
+        self.position_rule = None
 
     @staticmethod
     def capacity(prompt_len, new_tokens):
@@ -414,7 +417,7 @@ class KVCache:
             raise ValueError(f"KV cache: prompt of {S} merged rows exceeds the capacity {self.cap}")
         self.key_mask[:, :S] = mask.to(device=self.key_mask.device, dtype=torch.int32)
         self.len = S
-        self.pos = self.next_positions(self.key_mask, S)
+        self.pos = (self.position_rule or self.next_positions)(self.key_mask, S).to(torch.int32).contiguous()
 
     def open_column(self):
         """marks column `len` (the token of the coming decode step) as attended in every row; -> that column"""
@@ -464,7 +467,7 @@ class SharedPromptKVCache:
         return 2 * 2 * self.L * self.kv_heads * self.head_dim * (self.P * self.prompt.cap + self.B * self.tail_cap)
 
     def begin(self, alloc=True):
-        """after the prefill: empty tails, and every sample starts at its prompt's next position"""
+        """after the prefill: empty tails, and every sample starts at its prompt's next position (the prompt cache's position_rule)"""
         if self.prompt.len < 1:
             raise ValueError("SharedPromptKVCache.begin: the prompt segment is empty (run the prefill first)")
         self.tail_len = 0
@@ -1105,21 +1108,36 @@ class LlavaHipEngine:
     # ------------------------------------------------------------------------------------------------ decoding
     def new_kv_cache(self, batch, new_tokens) -> KVCache:
         """an empty cache for `batch` sequences and `new_tokens` decode columns; the prefill (forward_hidden(kv_cache=...)) sizes it"""
-        return KVCache(self.L, batch, self.nkv, self.hd, new_tokens, self.dev)
+        cache = KVCache(self.L, batch, self.nkv, self.hd, new_tokens, self.dev)
+        cache.position_rule = self.kv_next_positions
+        return cache
+
+    @staticmethod
+    def kv_next_positions(key_mask, length=None):
+        """[B] int32: the rotary position of the token each row appends after a prefill of `length` columns.  The engine's rule, consulted
+        by KVCache.start (and through the prompt cache by SharedPromptKVCache.begin): here the merge's - the number of attended columns."""
+        return KVCache.next_positions(key_mask, length)
+
+    wide_gemv = True               # batches above 16 rows over bf16 weights take the skinny GEMMs 64 rows per weight pass (False: 16-row groups; same bits)
 
     def _gemv_rows(self, mode, X, W, Y, M, N, K, ws):
-        for m0 in range(0, M, 16):
-            mr = min(16, M - m0)
-            _hip.call("vlr_gemv_bf16", mode, X[m0:m0 + mr], X.shape[1], W, Y[m0:m0 + mr], Y.shape[1], None, None, 0, None, None, None,
+        """the lm-head of a decode step: 16 rows per call, or - above 16 rows, `ws` sized for it by _decode_ws - 64 (vlr_gemv_wide_bf16)"""
+        wide = M > 16 and self.wide_gemv and ws.numel() >= int(_hip.lib().vlr_gemv_wide_workspace_bytes(min(M, 64), N, K))
+        fn, rows = ("vlr_gemv_wide_bf16", 64) if wide else ("vlr_gemv_bf16", 16)
+        for m0 in range(0, M, rows):
+            mr = min(rows, M - m0)
+            _hip.call(fn, mode, X[m0:m0 + mr], X.shape[1], W, Y[m0:m0 + mr], Y.shape[1], None, None, 0, None, None, None,
                       0, self.hd, self.max_pos, mr, N, K, ws)
 
     def new_shared_kv_cache(self, prompts, fanout, new_tokens) -> SharedPromptKVCache:
         """an empty shared-prompt cache: prefill `cache.prompt` (forward_hidden(kv_cache=cache.prompt)), then cache.begin()"""
-        return SharedPromptKVCache(self.L, prompts, fanout, self.nkv, self.hd, new_tokens, self.dev)
+        cache = SharedPromptKVCache(self.L, prompts, fanout, self.nkv, self.hd, new_tokens, self.dev)
+        cache.prompt.position_rule = self.kv_next_positions
+        return cache
 
     def _decode_ws(self, B, cap, shared=None):
         """shared: (prompts, fanout, prompt_cap, tail_cap) of a SharedPromptKVCache - sizes the attention workspace for it"""
-        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0, shared)
+        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0, shared, bool(self.wide_gemv))
         d = self._ws.get(key)
         if d is None:
             self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
@@ -1135,6 +1153,13 @@ class LlavaHipEngine:
                 rt = (nq * r, r, 2 * r, r)
                 gb = max([gb] + [int(_hip.lib().vlr_gemv_lora_workspace_bytes(mb, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
                 ub = max(int(_hip.lib().vlr_gemv_lora_u_bytes(mb, k, t)) for (n, k), t in zip(shapes[:4], rt))
+            if B > 16 and self.packed is None and self.wide_gemv:
+                # bf16 weights: scratch for 64-row groups - what makes vlr_decoder_layer_decode* and the lm-head take the wide calls
+                mw = min(B, 64)
+                gb = max([gb] + [int(_hip.lib().vlr_gemv_wide_workspace_bytes(mw, n, k)) for n, k in shapes])
+                if self.lora is not None:
+                    gb = max([gb] + [int(_hip.lib().vlr_gemv_wide_lora_workspace_bytes(mw, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
+                    ub = max([ub] + [int(_hip.lib().vlr_gemv_wide_lora_u_bytes(mw, k, t)) for (n, k), t in zip(shapes[:4], rt)])
             if shared is not None:
                 ab = int(_hip.lib().vlr_attn_decode_shared_workspace_bytes(shared[0], shared[1], self.nh, shared[2], shared[3]))
             else:

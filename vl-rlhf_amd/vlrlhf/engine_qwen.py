@@ -95,13 +95,22 @@ class QwenVisionWeights:
 
 class QwenVLHipEngine(LlavaHipEngine):
     vision_prefix = "transformer.visual."
-    supports_kv_cache = False      # generation inputs (image ids inside the text) not wired to the cache yet: generate re-runs the forward
+    # generate re-runs the forward per token unless the caller switches the cache on for THIS engine (QwenVLForRL.enable_kv_cache sets
+    # the instance attribute): then one prefill into a KVCache + decode_step, as on LLaVA-1.5.  The class default stays False.
+    supports_kv_cache = False
     row_compact_layers = False     # the row-compact reference pass (forward_hidden(prefix_dedup_rows=True)) is not wired to this engine: dense passes only
 
     def __init__(self, cfg: dict, device="cuda", max_positions: int = 4096):
         c = dict(cfg, family="qwen_vl")
         c.setdefault("rms_eps", 1e-6)
         super().__init__(c, device=device, max_positions=max_positions)
+
+    @staticmethod
+    def kv_next_positions(key_mask, length=None):
+        """Qwen's rotary position is the COLUMN index (_embed_inputs: pos = arange(S) in every row, padded or not): a row that was
+        left-padded appends at position `length`, where the re-forward loop places it - not at its count of attended columns"""
+        n = key_mask.shape[1] if length is None else int(length)
+        return torch.full((key_mask.shape[0],), n, dtype=torch.int32, device=key_mask.device)
 
     # ------------------------------------------------------------------------------------------------ vision tower
     def _init_vision_cfg(self):

@@ -133,10 +133,34 @@ class QwenVLForRL(LlavaForRL):
         generation_config.do_sample = False
         return dict(generation_config=generation_config)
 
+    def enable_kv_cache(self, on: bool = True):
+        """Switches generate(use_cache=True) of THIS model from the re-forward loop to the KV cache: one prefill into a KVCache
+        (SharedPromptKVCache under num_return_sequences), then engine.decode_step per token - the routes of LlavaForRL.generate, with
+        merged, live and disabled adapters and a packed Qwen-VL-Chat-Int4 base.  Sets the attribute on the engine INSTANCE (shared by
+        the models built on it, e.g. create_reference_model's); the class default and every freshly built model stay on the loop.
+        Rules of the cached route:
+          positions  Qwen's rotary position is the column index, so a left-padded row decodes at position `len`
+                     (QwenVLHipEngine.kv_next_positions), where the loop places it;
+          images     looked up only in the prefill; a NEW token whose id is an image marker is embedded as a plain wte row
+                     (modeling_qwen.py:525 looks for images only when past_key_values is None) - the loop raises on such a token;
+          logn attention scaling / dynamic NTK (modeling_qwen.py:287, 605; eval mode, past seq_length) are implemented by neither route.
+        -> self"""
+        self.engine.supports_kv_cache = bool(on)
+        return self
+
+    text_only_prompts = True       # the images ride in the ids: a batch that names none needs no pixel_values
+
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, **kw):
+        """the prefill takes the caller's pixels, else the files the prompt ids name, looked up once (None: a text-only batch)"""
+        if img.get("pixel_values") is None:
+            img = dict(img, pixel_values=self._pixels_from_ids(ids))
+        return LlavaForRL._generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, **kw)
+
     def generate(self, input_ids=None, *args, pixel_values=None, **kw):
         """LlavaForRL.generate; the image files named in the prompt ids are opened once per call, not once per re-forwarded token.
         Only when every row names exactly one image (pixel rows == prompt rows), which is what the num_return_sequences expansion of
-        `pixel_values` assumes; any other batch keeps the forward's own lookup per token."""
+        `pixel_values` assumes; any other batch keeps the forward's own lookup per token (the cached route's: once, in its prefill).
+        The KV cache is opt-in: enable_kv_cache()."""
         if pixel_values is None and input_ids is not None:
             px = self._pixels_from_ids(input_ids)
             if px is not None and px.shape[0] == input_ids.shape[0]:

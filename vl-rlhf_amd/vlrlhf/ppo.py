@@ -148,6 +148,8 @@ def main(argv=None):
         v_head_initializer_range=script_args.v_head_initializer_range, seed=ppo_config.seed)
     model.pretrained_model.freeze_vision_tower()
     model.pretrained_model.config.use_cache = False
+    if hasattr(model.pretrained_model, "enable_kv_cache"):      # Qwen-VL samples from the KV cache only when asked to: PPO asks
+        model.pretrained_model.enable_kv_cache()
     if ppo_config.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     lora_config = lora_config_from_args(model, ppo_config, lora_args)
