@@ -616,8 +616,8 @@ int vlr_attn_decode_gqa(const void* q, int ldq, const void* k_cache, const void*
  *   residual -> RMSNorm -> gate|up SwiGLU -> down_proj + residual.  x_inout [batch][hidden] is the residual stream (fp32 when
  *   cfg->resid_f32, else bf16), updated in place; pos [batch] the new rows' positions; key_mask [batch][cap] must already mark column
  *   len of every row (the new token).  kv_heads and bqkv are honoured; head_dim 128; len < cap.  Batches above 16 rows run the skinny
- *   GEMMs in 16-row groups - or, with bf16 weights and gemv_ws (and the adapter scratch u) sized by the vlr_gemv_wide_* helpers, in
- *   64-row groups through vlr_gemv_wide_bf16 / _lora ("the WIDE skinny GEMM" below): same bits, a quarter of the weight passes.
+ *   GEMMs in 16-row groups - or, with gemv_ws (and the adapter scratch u) sized by the vlr_gemv_wide_* helpers, in 64-row groups
+ *   through vlr_gemv_wide_bf16 / _w4 / _lora ("the WIDE skinny GEMM" below): same bits, a quarter of the weight passes.
  *   Scratch: */
 typedef struct {
     void* xn;          /* bf16 [batch][hidden] */
@@ -626,8 +626,9 @@ typedef struct {
     void* attn;        /* bf16 [batch][Nq] */
     void* act;         /* bf16 [batch][inter] */
     void* gemv_ws;     /* >= gemv_ws_bytes: the largest vlr_gemv_workspace_bytes(min(batch, 16), N, K) of the layer's four projections;
-                        * batch > 16 over bf16 weights: the largest vlr_gemv_wide_workspace_bytes(min(batch, 64), N, K) (with adapters:
-                        * vlr_gemv_wide_lora_workspace_bytes) selects the 64-row groups, anything smaller keeps the 16-row groups */
+                        * batch > 16: the largest vlr_gemv_wide_workspace_bytes(min(batch, 64), N, K) (packed weights:
+                        * vlr_gemv_wide_w4_workspace_bytes; with adapters: vlr_gemv_wide_lora_workspace_bytes) selects the 64-row
+                        * groups, anything smaller keeps the 16-row groups */
     long gemv_ws_bytes;
     void* attn_ws;     /* >= attn_ws_bytes: vlr_attn_decode_workspace_bytes(batch, heads, cap) */
     long attn_ws_bytes;
@@ -755,13 +756,20 @@ int vlr_decoder_layer_decode_shared(const vlr_llama_cfg* cfg, const vlr_layer_we
  *   layout are those of the 16-row kernel, so every output element is summed in the same order: the result equals, BIT FOR BIT, the
  *   16-row entry point called on rows [0, 16), [16, 32), ... of the same X (pos, residual and Y advanced by the same rows).  M <= 16
  *   launches the 16-row kernels themselves.  Workspace and u scratch: the vlr_gemv_wide_* helpers below (>= the 16-row helpers' values,
- *   equal to them at M <= 16).  Packed int4 weights have no wide form: vlr_gemv_w4 keeps 16-row groups.
- * vlr_decoder_layer_decode / _lora / _shared take the wide calls in 64-row groups when batch > 16, the weights are bf16 and
+ *   equal to them at M <= 16).
+ * vlr_gemv_wide_w4 / vlr_gemv_wide_w4_lora - the same for packed int4 weights: the argument lists and rules of vlr_gemv_w4 /
+ *   vlr_gemv_w4_lora with 1 <= M <= 64.  A lane's packed words are unpacked ONCE per k step and column tile and the fragment feeds
+ *   ceil(M / 16) row tiles, so the unpack - what bounds the 16-row packed kernel - is shared by all rows.  Bit for bit vlr_gemv_w4 /
+ *   vlr_gemv_w4_lora on rows [0, 16), [16, 32), ...  Workspace: vlr_gemv_wide_w4_workspace_bytes(M, N, K) (= vlr_gemv_w4_workspace_bytes
+ *   at M <= 16, M times its per-row size above).  The adapter form takes vlr_gemv_wide_lora_workspace_bytes and
+ *   vlr_gemv_wide_lora_u_bytes, which cover the packed split count as their 16-row namesakes do.
+ * vlr_decoder_layer_decode / _w4 / _lora / _w4_lora / _shared take the wide calls in 64-row groups when batch > 16 and
  *   ws->gemv_ws_bytes (with adapters also lws->u_bytes) cover the wide helpers' sizes at min(batch, 64) rows; otherwise they run the
  *   16-row groups as before.  Either way the same bits. */
 long vlr_gemv_wide_workspace_bytes(int M, int N, int K);
 long vlr_gemv_wide_lora_workspace_bytes(int M, int N, int K, int r_total);
 long vlr_gemv_wide_lora_u_bytes(int M, int K, int r_total);
+long vlr_gemv_wide_w4_workspace_bytes(int M, int N, int K);
 int vlr_gemv_wide_bf16(int mode, const void* X, int ldx, const void* W, void* Y, int ldy, const void* bias, const void* residual, int ldr,
                        const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
                        void* workspace, vlr_stream_t stream);
@@ -769,6 +777,14 @@ int vlr_gemv_wide_bf16_lora(int mode, const void* X, int ldx, const void* W, voi
                             int ldr, const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M,
                             int N, int K, void* workspace, const void* A, const void* B, int r, int targets, const int* outs, float scale,
                             void* u, vlr_stream_t stream);
+int vlr_gemv_wide_w4(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
+                     void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t,
+                     const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace,
+                     vlr_stream_t stream);
+int vlr_gemv_wide_w4_lora(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
+                          void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t,
+                          const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace,
+                          const void* A, const void* B, int r, int targets, const int* outs, float scale, void* u, vlr_stream_t stream);
 
 /* ---- data-parallel gradient exchange on RCCL over xGMI (replaces accelerate MULTI_GPU / torch DDP's NCCL all-reduce:
  *      /root/reference accelerate_config/ddp.yaml:1-14; the reference itself never calls a collective).  One process per

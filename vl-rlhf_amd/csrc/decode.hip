@@ -16,7 +16,8 @@
 //   gemv_w4_kernel       the same product with W read PACKED (GPTQ int4, gptq.h): a quarter of the weight bytes.  One int32 of qweight
 //                        is 8 consecutive k of one column - exactly one lane's B fragment of the MFMA - so a lane loads 16 bytes (4
 //                        columns x 8 k), unpacks them to bf16 in registers by the rule of gptq.h and feeds four MFMAs.  Same partials,
-//                        same epilogue kernel, same fixed summation order.
+//                        same epilogue kernel, same fixed summation order.  gemv_w4_kernel<PER_STEP, MT>, MT = 2 .. 4: the wide form -
+//                        a fragment is unpacked once and feeds MT row tiles (17 .. 64 rows); bit for bit the MT = 1 kernel on 16-row groups
 //   gemv_lora_kernel /   the two products with a live LoRA adapter: one more K slice whose workgroups write u B^T, u = bf16(scale * x A^T)
 //   gemv_w4_lora_kernel  (see "live LoRA adapters" below) - the adapter term is summed last, in front of the epilogue
 //   kv_cache_write_kernel  post-RoPE K / V column blocks of the fused qkv rows -> cache columns slot0 .. slot0 + S - 1 (exact copy)
@@ -631,7 +632,11 @@ extern "C" int vlr_gemv_wide_bf16_lora(int mode, const void* X, int ldx, const v
 // scales and zeros are reloaded at every 32-k step (a multiple of 32 divides the step into one group); otherwise once per chunk.
 constexpr int GW_COLS = 128;
 
-template <bool PER_STEP>
+// MT row tiles of 16 (M <= 16 MT): a lane's packed words are unpacked ONCE per (k step, half, n tile) and the fragment feeds MT MFMAs,
+// so the unpack - what bounds the 16-row kernel - is shared by up to 64 rows; only the X fragments and the accumulators grow
+// with MT.  Row m = 16 mt + r sees the chunks, the k steps and the four-wave fold of the MT = 1 form in the same order: its sums do not
+// depend on MT.  The fold runs one row tile at a time through the same 32 KB of LDS.
+template <bool PER_STEP, int MT>
 __device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
                                              const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC, float* __restrict__ part,
                                              int M, int N, int K, int gsz, int cps, int n0, int split, float (*red)[16][GW_COLS]) {
@@ -639,8 +644,13 @@ __device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int l
     const int r = lane & 15, g = lane >> 4;
     const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK;
     const int c0 = split * cps, c1 = min(nchunks, c0 + cps);
-    const bool mok = r < M;
-    const bf16_t* xrow = X + (size_t)(mok ? r : 0) * ldx;
+    bool mok[MT];
+    const bf16_t* xrow[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        mok[mt] = 16 * mt + r < M;
+        xrow[mt] = X + (size_t)(mok[mt] ? 16 * mt + r : 0) * ldx;
+    }
     int nb[2];
     bool nok[2];
 #pragma unroll
@@ -649,16 +659,18 @@ __device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int l
         nok[h] = n < N;                                    // N % 8 == 0: a lane's 4 columns are all in or all out
         nb[h] = nok[h] ? n : 0;
     }
-    f32x4 acc[2][4];
+    f32x4 acc[MT][2][4];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[mt][h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
     const int nz = N / 8, lastk = K - 8;
     constexpr int NS = PER_STEP ? 4 : 1;
     // every load below is unconditional at a clamped address (no branch, all of a chunk's loads in flight together): a k beyond K reads
-    // row K / 8 - 1 again and meets X = 0, a column beyond N reads column 0 and is never stored
+    // row K / 8 - 1 again and meets X = 0, a column beyond N reads column 0 and is never stored, a row beyond M reads row 0 and is zeroed
     for (int c = c0 + wv; c < c1; c += 4) {
         f16x4 sc[NS][2];
         uint32_t zw[NS][2];
@@ -671,14 +683,17 @@ __device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int l
                 zw[s][h] = QZ[(size_t)G * nz + (nb[h] >> 3)];
             }
         }
-        bf16x8 a[4];
+        bf16x8 a[4][MT];
         u32x4 qw[4][2];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int k = c * GV_CHUNK + u * 32 + g * 8;
             const int kc = min(k, lastk);                  // K % 8 == 0: a lane's 8 k are all in or all out
-            const bf16x8 x = load8(xrow + kc);
-            a[u] = (mok && k < K) ? x : zero;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const bf16x8 x = load8(xrow[mt] + kc);
+                a[u][mt] = (mok[mt] && k < K) ? x : zero;
+            }
 #pragma unroll
             for (int h = 0; h < 2; ++h) qw[u][h] = *reinterpret_cast<const u32x4*>(QW + (size_t)(kc >> 3) * N + nb[h]);
         }
@@ -691,43 +706,57 @@ __device__ __forceinline__ void gemv_w4_tile(const bf16_t* __restrict__ X, int l
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const bf16x8 b = __builtin_bit_cast(bf16x8, w4_unpack(qw[u][h][t], (float)sc[s][h][t], w4_zero(zw[s][h], nb[h] + t)));
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b, acc[h][t], 0, 0, 0);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        acc[mt][h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u][mt], b, acc[mt][h][t], 0, 0, 0);
                 }
         }
     }
-    // D map: lane holds D[m = 4 g + i][tile column r] of n tile (h, t) = output column 64 h + 4 r + t
+    // D map: lane holds D[m = 16 mt + 4 g + i][tile column r] of n tile (h, t) = output column 64 h + 4 r + t
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int mt = 0; mt < MT; ++mt) {
+        if (mt) __syncthreads();                           // the previous row tile has been folded
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) red[wv][4 * g + i][64 * h + 4 * r + t] = acc[h][t][i];
-    __syncthreads();
+            for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int idx = threadIdx.x + 256 * e, m = idx / GW_COLS, n = idx % GW_COLS;
-        if (m < M && n0 + n < N)
-            part[((size_t)split * M + m) * N + n0 + n] = ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n];
+                for (int i = 0; i < 4; ++i) red[wv][4 * g + i][64 * h + 4 * r + t] = acc[mt][h][t][i];
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int idx = threadIdx.x + 256 * e, ml = idx / GW_COLS, m = 16 * mt + ml, n = idx % GW_COLS;
+            if (m < M && n0 + n < N)
+                part[((size_t)split * M + m) * N + n0 + n] = ((red[0][ml][n] + red[1][ml][n]) + red[2][ml][n]) + red[3][ml][n];
+        }
     }
 }
 
-template <bool PER_STEP>
+// MT = 1: the 16-row kernel; MT = 2 .. 4: the wide form (17 .. 64 rows in ONE pass over the packed words).  Grid, chunk assignment and
+// partial layout [slice][M][N] do not depend on MT
+template <bool PER_STEP, int MT = 1>
 __global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
                                                       const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
                                                       float* __restrict__ part, int M, int N, int K, int gsz, int cps) {
     __shared__ float red[4][16][GW_COLS];
-    gemv_w4_tile<PER_STEP>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
+    gemv_w4_tile<PER_STEP, MT>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
 }
 
-// the packed product with the adapter term as slice S (gemv_lora_kernel's scheme; the adapter operands are bf16 here too)
-template <bool PER_STEP>
+// the packed product with the adapter term as slice S (gemv_lora_kernel's scheme; the adapter operands are bf16 here too).  MT > 1: the
+// adapter slice walks the row tiles through the 16-row code, as gemv_wide_lora_kernel does
+template <bool PER_STEP, int MT = 1>
 __global__ __launch_bounds__(256) void gemv_w4_lora_kernel(const bf16_t* __restrict__ X, int ldx, const uint32_t* __restrict__ QW,
                                                            const uint32_t* __restrict__ QZ, const uint16_t* __restrict__ SC,
                                                            float* __restrict__ part, int M, int N, int K, int gsz, int cps, int S,
                                                            GemvLora lo) {
     __shared__ float red[4][16][GW_COLS];
-    if ((int)blockIdx.y == S) gemv_lora_slice<GW_COLS>(lo, part + (size_t)S * M * N, M, N, blockIdx.x * GW_COLS, (bf16_t*)&red[0][0][0], M, 0);
-    else gemv_w4_tile<PER_STEP>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
+    if ((int)blockIdx.y == S) {
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt) __syncthreads();                       // the previous tile's u has been read
+            gemv_lora_slice<GW_COLS>(lo, part + (size_t)S * M * N, min(16, M - 16 * mt), N, blockIdx.x * GW_COLS, (bf16_t*)&red[0][0][0], M,
+                                     16 * mt);
+        }
+    } else gemv_w4_tile<PER_STEP, MT>(X, ldx, QW, QZ, SC, part, M, N, K, gsz, cps, blockIdx.x * GW_COLS, blockIdx.y, red);
 }
 
 static int gemv_w4_check(const char* fn, const void* qweight, const void* qzeros, const void* scales, int group_size, int N, int K) {
@@ -745,27 +774,78 @@ extern "C" long vlr_gemv_w4_workspace_bytes(int M, int N, int K) {
     return (long)gemv_splits(N, K, GW_COLS) * (M > 16 ? 16 : M) * N * 4;
 }
 
+// the product launch for any M <= 64: ceil(M / 16) row tiles; one scale / zero group per 128-k chunk when the chunks do not straddle
+// groups, else per 32-k step (a group of K itself never changes)
+static void gemv_w4_launch(dim3 grid, hipStream_t st, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales,
+                           int group_size, void* part, int M, int N, int K, int cps, int S, const GemvLora* lo) {
+    const bf16_t* x = (const bf16_t*)X;
+    const uint32_t* qw = (const uint32_t*)qweight;
+    const uint32_t* qz = (const uint32_t*)qzeros;
+    const uint16_t* sc = (const uint16_t*)scales;
+    float* p = (float*)part;
+    const bool per_step = !(group_size == K || group_size % GV_CHUNK == 0);
+#define W4_LAUNCH(PS, MT)                                                                                                          \
+    do {                                                                                                                           \
+        if (lo) hipLaunchKernelGGL((gemv_w4_lora_kernel<PS, MT>), grid, dim3(256), 0, st, x, ldx, qw, qz, sc, p, M, N, K, group_size, cps, S, *lo); \
+        else hipLaunchKernelGGL((gemv_w4_kernel<PS, MT>), grid, dim3(256), 0, st, x, ldx, qw, qz, sc, p, M, N, K, group_size, cps);  \
+    } while (0)
+#define W4_ROWS(MT)                                                                                                                \
+    do {                                                                                                                           \
+        if (per_step) W4_LAUNCH(true, MT);                                                                                         \
+        else W4_LAUNCH(false, MT);                                                                                                 \
+    } while (0)
+    switch ((M + 15) / 16) {
+        case 1: W4_ROWS(1); break;
+        case 2: W4_ROWS(2); break;
+        case 3: W4_ROWS(3); break;
+        default: W4_ROWS(4); break;
+    }
+#undef W4_ROWS
+#undef W4_LAUNCH
+}
+
+static int gemv_w4_rows(const char* fn, int max_rows, int mode, const void* X, int ldx, const void* qweight, const void* qzeros,
+                        const void* scales, int group_size, void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos,
+                        const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
+                        void* workspace, hipStream_t st) {
+    const int rc = gemv_check(fn, mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K,
+                              workspace, max_rows);
+    if (rc != VLR_OK) return rc;
+    const int rq = gemv_w4_check(fn, qweight, qzeros, scales, group_size, N, K);
+    if (rq != VLR_OK) return rq;
+    const int S = gemv_splits(N, K, GW_COLS);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    gemv_w4_launch(dim3((N + GW_COLS - 1) / GW_COLS, S), st, X, ldx, qweight, qzeros, scales, group_size, workspace, M, N, K, cps, S, nullptr);
+    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch(fn);
+}
+
+static int gemv_w4_lora_rows(const char* fn, int max_rows, int mode, const void* X, int ldx, const void* qweight, const void* qzeros,
+                             const void* scales, int group_size, void* Y, int ldy, const void* bias, const void* residual, int ldr,
+                             const int* pos, const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N,
+                             int K, void* workspace, const void* A, const void* B, int r, int targets, const int* outs, float scale, void* u,
+                             hipStream_t st) {
+    const int rc = gemv_check(fn, mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K,
+                              workspace, max_rows);
+    if (rc != VLR_OK) return rc;
+    const int rq = gemv_w4_check(fn, qweight, qzeros, scales, group_size, N, K);
+    if (rq != VLR_OK) return rq;
+    GemvLora lo;
+    const int rl = gemv_lora_prepare(fn, X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
+    if (rl != VLR_OK) return rl;
+    const int S = gemv_splits(N, K, GW_COLS);
+    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
+    gemv_w4_launch(dim3((N + GW_COLS - 1) / GW_COLS, S + 1), st, X, ldx, qweight, qzeros, scales, group_size, workspace, M, N, K, cps, S, &lo);
+    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
+    return vlr_check_launch(fn);
+}
+
 extern "C" int vlr_gemv_w4(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
                            void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos, const float* cos_t,
                            const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K, void* workspace,
                            vlr_stream_t st) {
-    const int rc = gemv_check("vlr_gemv_w4", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M,
-                              N, K, workspace);
-    if (rc != VLR_OK) return rc;
-    const int rq = gemv_w4_check("vlr_gemv_w4", qweight, qzeros, scales, group_size, N, K);
-    if (rq != VLR_OK) return rq;
-    const int S = gemv_splits(N, K, GW_COLS);
-    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
-    const dim3 grid((N + GW_COLS - 1) / GW_COLS, S);
-    // one group per 128-k chunk when the chunks do not straddle groups; else per 32-k step (a group of K itself never changes)
-    if (group_size == K || group_size % GV_CHUNK == 0)
-        hipLaunchKernelGGL(gemv_w4_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
-                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps);
-    else
-        hipLaunchKernelGGL(gemv_w4_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
-                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps);
-    gemv_epilogue(mode, workspace, S, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
-    return vlr_check_launch("vlr_gemv_w4");
+    return gemv_w4_rows("vlr_gemv_w4", 16, mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t,
+                        rope_cols, head_dim, max_pos, M, N, K, workspace, st);
 }
 
 extern "C" int vlr_gemv_w4_lora(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales, int group_size,
@@ -775,25 +855,34 @@ extern "C" int vlr_gemv_w4_lora(int mode, const void* X, int ldx, const void* qw
     if (!A && !B)
         return vlr_gemv_w4(mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
                            head_dim, max_pos, M, N, K, workspace, st);
-    const int rc = gemv_check("vlr_gemv_w4_lora", mode, X, ldx, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos,
-                              M, N, K, workspace);
-    if (rc != VLR_OK) return rc;
-    const int rq = gemv_w4_check("vlr_gemv_w4_lora", qweight, qzeros, scales, group_size, N, K);
-    if (rq != VLR_OK) return rq;
-    GemvLora lo;
-    const int rl = gemv_lora_prepare("vlr_gemv_w4_lora", X, ldx, A, B, r, targets, outs, scale, u, M, N, K, st, &lo);
-    if (rl != VLR_OK) return rl;
-    const int S = gemv_splits(N, K, GW_COLS);
-    const int nchunks = (K + GV_CHUNK - 1) / GV_CHUNK, cps = (nchunks + S - 1) / S;
-    const dim3 grid((N + GW_COLS - 1) / GW_COLS, S + 1);
-    if (group_size == K || group_size % GV_CHUNK == 0)
-        hipLaunchKernelGGL(gemv_w4_lora_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
-                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps, S, lo);
-    else
-        hipLaunchKernelGGL(gemv_w4_lora_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)X, ldx, (const uint32_t*)qweight,
-                           (const uint32_t*)qzeros, (const uint16_t*)scales, (float*)workspace, M, N, K, group_size, cps, S, lo);
-    gemv_epilogue(mode, workspace, S + 1, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, st);
-    return vlr_check_launch("vlr_gemv_w4_lora");
+    return gemv_w4_lora_rows("vlr_gemv_w4_lora", 16, mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos,
+                             cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K, workspace, A, B, r, targets, outs, scale, u, st);
+}
+
+// ---- the wide packed entry points: the argument lists of vlr_gemv_w4 / vlr_gemv_w4_lora, 1 <= M <= 64 rows in one pass over the packed
+// words.  Bit for bit the 16-row entry point on rows [0, 16), [16, 32), ... (gemv_w4_tile).  Workspace: the same split count times
+// min(M, 64) rows; the adapter form takes vlr_gemv_wide_lora_workspace_bytes / vlr_gemv_wide_lora_u_bytes, which cover both split counts.
+extern "C" long vlr_gemv_wide_w4_workspace_bytes(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 8) return 0;
+    return (long)gemv_splits(N, K, GW_COLS) * (M > 64 ? 64 : M) * N * 4;
+}
+extern "C" int vlr_gemv_wide_w4(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales,
+                                int group_size, void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos,
+                                const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
+                                void* workspace, vlr_stream_t st) {
+    return gemv_w4_rows("vlr_gemv_wide_w4", 64, mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos, cos_t,
+                        sin_t, rope_cols, head_dim, max_pos, M, N, K, workspace, st);
+}
+extern "C" int vlr_gemv_wide_w4_lora(int mode, const void* X, int ldx, const void* qweight, const void* qzeros, const void* scales,
+                                     int group_size, void* Y, int ldy, const void* bias, const void* residual, int ldr, const int* pos,
+                                     const float* cos_t, const float* sin_t, int rope_cols, int head_dim, int max_pos, int M, int N, int K,
+                                     void* workspace, const void* A, const void* B, int r, int targets, const int* outs, float scale,
+                                     void* u, vlr_stream_t st) {
+    if (!A && !B)
+        return vlr_gemv_wide_w4(mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr, pos, cos_t, sin_t, rope_cols,
+                                head_dim, max_pos, M, N, K, workspace, st);
+    return gemv_w4_lora_rows("vlr_gemv_wide_w4_lora", 64, mode, X, ldx, qweight, qzeros, scales, group_size, Y, ldy, bias, residual, ldr,
+                             pos, cos_t, sin_t, rope_cols, head_dim, max_pos, M, N, K, workspace, A, B, r, targets, outs, scale, u, st);
 }
 
 extern "C" int vlr_kv_cache_write(const void* k, const void* v, int ld, void* k_cache, void* v_cache, int batch, int S, int kv_heads,

@@ -114,21 +114,28 @@ extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_w
 
 // ---- one decoder layer for one new token per sequence against its KV cache (vlr_decoder_layer_fwd_ex's arithmetic at M = batch rows,
 // the key side read from the cache).  The skinny GEMMs take at most 16 rows: larger batches run them in 16-row groups, or (`wide`:
-// bf16 weights and scratch sized for it) in 64-row groups through the wide entry points - one pass over W per 64 rows, the same bits.
+// scratch sized for it) in 64-row groups through the wide entry points - one pass over W per 64 rows, the same bits.
 // W: the bf16 matrix, or (q != NULL) the packed int4 linear of a GPTQ base (vlr_gemv_w4)
 // ad != NULL with ad->A: the live adapter of the projection (vlr_gemv_*_lora)
 struct GemvAdapter { const void* A; const void* B; int r, targets; const int* outs; float scale; void* u; };
 static int gemv_rows(int mode, const void* X, int ldx, const void* W, const vlr_w4_linear* q, void* Y, int ldy, size_t ysz, const void* bias,
                      const void* res, int ldr, size_t rsz, const int* pos, const vlr_llama_cfg* cfg, int rope_cols, int M, int N, int K,
                      void* ws, hipStream_t st, const GemvAdapter* ad = nullptr, bool wide = false) {
-    const int rows = wide && !q ? 64 : 16;
+    const int rows = wide ? 64 : 16;
     for (int m0 = 0; m0 < M; m0 += rows) {
         const int mr = M - m0 < rows ? M - m0 : rows;
         const void* x = (const char*)X + (size_t)m0 * ldx * 2;
         void* y = (char*)Y + (size_t)m0 * ldy * ysz;
         const void* r = res ? (const char*)res + (size_t)m0 * ldr * rsz : nullptr;
         const int* p = pos ? pos + m0 : nullptr;
-        if (ad && ad->A && q)
+        if (ad && ad->A && q && rows == 64)
+            CHECK(vlr_gemv_wide_w4_lora(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
+                                        cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r,
+                                        ad->targets, ad->outs, ad->scale, ad->u, st));
+        else if (q && rows == 64)
+            CHECK(vlr_gemv_wide_w4(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
+                                   cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, st));
+        else if (ad && ad->A && q)
             CHECK(vlr_gemv_w4_lora(mode, x, ldx, q->qweight, q->qzeros, q->scales, q->group_size, y, ldy, bias, r, ldr, p, cfg->rope_cos,
                                    cfg->rope_sin, rope_cols, cfg->head_dim, cfg->max_pos, mr, N, K, ws, ad->A, ad->B, ad->r, ad->targets,
                                    ad->outs, ad->scale, ad->u, st));
@@ -185,13 +192,13 @@ static int layer_decode(const char* fn, const vlr_llama_cfg* cfg, const vlr_laye
     long need = bytes(mb, N, H);
     const long shapes[3] = {bytes(mb, H, Nq), bytes(mb, 2 * I, H), bytes(mb, H, I)};
     for (long b : shapes) need = b > need ? b : need;
-    // the 64-row groups: more than 16 rows of bf16 weights, and scratch that covers the wide sizes (else the 16-row groups, as ever)
+    // the 64-row groups: more than 16 rows, and scratch that covers the wide sizes (else the 16-row groups, as ever)
     const int mw = batch < 64 ? batch : 64;
-    bool wide = batch > 16 && !q4;
+    bool wide = batch > 16;
     long need_w = 0;
     if (wide) {
-        const long wshapes[4] = {vlr_gemv_wide_workspace_bytes(mw, N, H), vlr_gemv_wide_workspace_bytes(mw, H, Nq),
-                                 vlr_gemv_wide_workspace_bytes(mw, 2 * I, H), vlr_gemv_wide_workspace_bytes(mw, H, I)};
+        long (*wbytes)(int, int, int) = q4 ? vlr_gemv_wide_w4_workspace_bytes : vlr_gemv_wide_workspace_bytes;
+        const long wshapes[4] = {wbytes(mw, N, H), wbytes(mw, H, Nq), wbytes(mw, 2 * I, H), wbytes(mw, H, I)};
         for (long b : wshapes) need_w = b > need_w ? b : need_w;
     }
     GemvAdapter a_qkv{}, a_o{}, a_gu{}, a_down{};

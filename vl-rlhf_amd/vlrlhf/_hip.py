@@ -200,6 +200,8 @@ _SIGS = {
     # the wide skinny GEMM (include/vlr.h "the WIDE skinny GEMM"): the 16-row signatures, 1 <= M <= 64
     "vlr_gemv_wide_bf16": [I, P, I, P, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P],
     "vlr_gemv_wide_bf16_lora": [I, P, I, P, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, I, P, F, P, P],
+    "vlr_gemv_wide_w4": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P],
+    "vlr_gemv_wide_w4_lora": [I, P, I, P, P, P, I, P, I, P, P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, I, P, F, P, P],
 }
 GEMV_BF16, GEMV_F32, GEMV_F32RES, GEMV_QKV_ROPE, GEMV_SWIGLU = range(5)      # vlr_gemv_bf16 modes
 _INT_HELPERS = {
@@ -229,7 +231,8 @@ _INT_HELPERS = {
 }
 
 
-_LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes", "vlr_gemv_wide_workspace_bytes"]      # (int, int, int) -> long
+_LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes", "vlr_gemv_wide_workspace_bytes",
+                 "vlr_gemv_wide_w4_workspace_bytes"]      # (int, int, int) -> long
 _LONG_HELPERS_N = {"vlr_v_head_bwd_workspace_bytes": 2, "vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5,
                    "vlr_gemv_wide_lora_workspace_bytes": 4, "vlr_gemv_wide_lora_u_bytes": 3}      # name -> number of int arguments, -> long
 

@@ -1118,7 +1118,8 @@ class LlavaHipEngine:
         by KVCache.start (and through the prompt cache by SharedPromptKVCache.begin): here the merge's - the number of attended columns."""
         return KVCache.next_positions(key_mask, length)
 
-    wide_gemv = True               # batches above 16 rows over bf16 weights take the skinny GEMMs 64 rows per weight pass (False: 16-row groups; same bits)
+    wide_gemv = True               # batches above 16 rows take the skinny GEMMs 64 rows per weight pass (False: 16-row groups; same bits)
+    wide_gemv_w4 = True            # ... over packed int4 weights too (vlr_gemv_wide_w4); wide_gemv = False withholds both
 
     def _gemv_rows(self, mode, X, W, Y, M, N, K, ws):
         """the lm-head of a decode step: 16 rows per call, or - above 16 rows, `ws` sized for it by _decode_ws - 64 (vlr_gemv_wide_bf16)"""
@@ -1137,7 +1138,7 @@ class LlavaHipEngine:
 
     def _decode_ws(self, B, cap, shared=None):
         """shared: (prompts, fanout, prompt_cap, tail_cap) of a SharedPromptKVCache - sizes the attention workspace for it"""
-        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0, shared, bool(self.wide_gemv))
+        key = ("decode_ws", B, cap, self.lora["r"] if self.lora is not None else 0, shared, bool(self.wide_gemv), bool(getattr(self, "wide_gemv_w4", False)))
         d = self._ws.get(key)
         if d is None:
             self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k and k[0] == "decode_ws")}
@@ -1153,10 +1154,13 @@ class LlavaHipEngine:
                 rt = (nq * r, r, 2 * r, r)
                 gb = max([gb] + [int(_hip.lib().vlr_gemv_lora_workspace_bytes(mb, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
                 ub = max(int(_hip.lib().vlr_gemv_lora_u_bytes(mb, k, t)) for (n, k), t in zip(shapes[:4], rt))
-            if B > 16 and self.packed is None and self.wide_gemv:
-                # bf16 weights: scratch for 64-row groups - what makes vlr_decoder_layer_decode* and the lm-head take the wide calls
+            if B > 16 and self.wide_gemv and (self.packed is None or getattr(self, "wide_gemv_w4", False)):
+                # scratch for 64-row groups - what makes vlr_decoder_layer_decode* and the lm-head (bf16 in a packed model too) take the
+                # wide calls
                 mw = min(B, 64)
                 gb = max([gb] + [int(_hip.lib().vlr_gemv_wide_workspace_bytes(mw, n, k)) for n, k in shapes])
+                if self.packed is not None:
+                    gb = max([gb] + [int(_hip.lib().vlr_gemv_wide_w4_workspace_bytes(mw, n, k)) for n, k in shapes[:4]])
                 if self.lora is not None:
                     gb = max([gb] + [int(_hip.lib().vlr_gemv_wide_lora_workspace_bytes(mw, n, k, t)) for (n, k), t in zip(shapes[:4], rt)])
                     ub = max([ub] + [int(_hip.lib().vlr_gemv_wide_lora_u_bytes(mw, k, t)) for (n, k), t in zip(shapes[:4], rt)])

@@ -32,7 +32,11 @@ PLORA_SEED_XOR = 0x2A5A5A5A5A
 
 
 class InternLMHipEngine(LlavaHipEngine):
-    supports_kv_cache = False      # the PLoRA layers are composed per pass (image rows): generate re-runs the forward
+    # generate re-runs the forward per token unless the caller switches the cache on for THIS engine (InternLMXC2ForRL.enable_kv_cache
+    # sets the instance attribute): then one prefill through _layer_fwd_call (PLoRA on the image rows) into a KVCache + decode_step.  A
+    # new token is a text row - the PLoRA pairs add nothing to it (build_mlp.py:194-199; modeling_internlm2.py:787 builds a zero im_mask
+    # when none is given) - so decode_step is the base engine's, on this family's weights.  The class default stays False.
+    supports_kv_cache = False
     row_compact_layers = False     # the row-compact reference pass (forward_hidden(prefix_dedup_rows=True)) is not wired to this engine: dense passes only
     vision_prefix = "vit.vision_tower."
 
@@ -52,6 +56,25 @@ class InternLMHipEngine(LlavaHipEngine):
         self.plora_seed = int(c.get("seed", 0))
         self.lora_fused = False                  # set by enable_lora: peft LoRA over PLoRA on vlr_decoder_layer_*_lora2
         self.last_train_plora_seed = None        # PLoRA dropout seed of the last training-mode policy pass
+
+    # ------------------------------------------------------------------------------------------------ decoding
+    @staticmethod
+    def kv_next_positions(key_mask, length=None):
+        """the rotary position is the index in the merged sequence (_embed_inputs: pos = arange(S) in every row, padded or not): a row
+        that was left-padded appends at position `length`, where the re-forward loop places it - not at its count of attended columns"""
+        n = key_mask.shape[1] if length is None else int(length)
+        return torch.full((key_mask.shape[0],), n, dtype=torch.int32, device=key_mask.device)
+
+    @property
+    def kv_cache_layers(self):
+        """False while the decoder layers are the ones composed from bf16 primitives (peft LoRA under VLR_ILM_LORA_FUSED=0): they keep the
+        re-forward loop.  Read when generate starts - enable_lora may run after the cache was switched on."""
+        return self.lora is None or self.lora_fused
+
+    def decode_step(self, ws, tokens, cache, lora=None):
+        if not self.kv_cache_layers:
+            raise ValueError("InternLMHipEngine: the composed bf16 layers (VLR_ILM_LORA_FUSED=0) have no KV-cache decoding")
+        return super().decode_step(ws, tokens, cache, lora)
 
     # ------------------------------------------------------------------------------------------------ embed
     def _embed_inputs(self, ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta):

@@ -2,7 +2,7 @@
 load_model_and_processor :25-48, run_vqa :51-82, run_vqa_ppl :85-120).
 
 Nothing here launches a kernel of its own: run_vqa is `model.generate` (one prefill + engine.decode_step per token on the engines with a
-KV cache - Qwen-VL checkpoints are switched onto it by load_model_and_processor - and the re-forward loop on InternLM-XComposer2) and run_vqa_ppl is `model(**inputs)` + the fused lm-head log-probs of
+KV cache - Qwen-VL and InternLM-XComposer2 checkpoints are switched onto it by load_model_and_processor) and run_vqa_ppl is `model(**inputs)` + the fused lm-head log-probs of
 VLDPOTrainer.get_batch_logps on the label rows, so the [B,S,V] logits are never written out.
 
 Several GPUs are several invocations, not a collective: every entry point takes --num_shards N --shard_id i, evaluates a contiguous
@@ -81,7 +81,7 @@ def load_model_and_processor(model_path, processor_path=None, **kwargs):
     else:
         model = MyAutoModel.from_pretrained(model_path, **kwargs)
     model.eval()
-    if hasattr(model, "enable_kv_cache"):      # Qwen-VL: answers decode from the KV cache (opt-in per model; a fresh model re-forwards)
+    if hasattr(model, "enable_kv_cache"):      # Qwen-VL, InternLM-XComposer2: answers decode from the KV cache (opt-in per model; a fresh model re-forwards)
         model.enable_kv_cache()
     config_dir = base if base is not None else model_path
     processor = MyAutoProcessor.from_pretrained(processor_path if processor_path is not None else config_dir)

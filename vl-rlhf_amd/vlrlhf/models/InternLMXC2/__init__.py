@@ -102,6 +102,35 @@ class InternLMXC2ForRL(LlavaForRL):
         generation_config.stop_words_ids = [[92542]]
         return dict(generation_config=generation_config)
 
+    def enable_kv_cache(self, on: bool = True):
+        """Switches generate(use_cache=True) of THIS model from the re-forward loop to the KV cache: one prefill into a KVCache
+        (SharedPromptKVCache under num_return_sequences), then engine.decode_step per token - the routes of LlavaForRL.generate, with
+        full fine-tune weights and with merged, live and disabled peft adapters.  Sets the attribute on the engine INSTANCE (shared by
+        the models built on it, e.g. create_reference_model's); the class default and every freshly built model stay on the loop.
+        Rules of the cached route:
+          prefill    the engine's own layer calls: the PLoRA pairs act on the image rows, with peft LoRA over them or without (also
+                     inside disable_adapter(), as in the reference pass);
+          decode     a new token is a text row: the PLoRA pairs add nothing to it (build_mlp.py:194-199), so a step is the base
+                     projections plus - live - the peft adapters (one over the fused wqkv, one each on wo, w1 | w3 and w2);
+          positions  the rotary position is the index in the merged sequence, so a left-padded row decodes at position `len`
+                     (InternLMHipEngine.kv_next_positions), where the loop places it;
+          fallback   the layers composed from bf16 primitives (VLR_ILM_LORA_FUSED=0) keep the loop: decided when generate starts.
+        logn attention scaling / dynamic NTK are implemented by neither route.  -> self"""
+        self.engine.supports_kv_cache = bool(on)
+        return self
+
+    def generate(self, *args, **kw):
+        """LlavaForRL.generate; the KV cache is opt-in (enable_kv_cache()).  The composed bf16 layers never take it: the switch is
+        withheld for the length of such a call (decided here, not in enable_kv_cache - enable_lora may run after it)"""
+        eng = self.engine
+        if eng.kv_cache_layers or not eng.supports_kv_cache:
+            return LlavaForRL.generate(self, *args, **kw)
+        eng.supports_kv_cache = False
+        try:
+            return LlavaForRL.generate(self, *args, **kw)
+        finally:
+            eng.supports_kv_cache = True
+
     ce_selects_by_mask = False     # reference :211-219 shifts without the attention mask: the label alone selects a row
 
     def forward(self, input_ids=None, pixel_values=None, im_mask=None, attention_mask=None, position_ids=None, past_key_values=None,

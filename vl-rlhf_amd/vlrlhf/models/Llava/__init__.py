@@ -504,9 +504,9 @@ class LlavaForRL(nn.Module):
             step runs them live (engine.decode_step -> vlr_decoder_layer_decode_lora), which is what sampling from the policy inside a
             training loop needs; the first token's logits are then those of use_cache=False bit for bit;
           a packed GPTQ base (q_lora) always takes the live path, whatever merge_lora says: nothing can be merged into packed weights.
-        With the adapters disabled (disable_adapter()) or absent the plain weights are decoded.  Qwen-VL takes all of these routes once
-        the caller has switched its cache on (QwenVLForRL.enable_kv_cache(); a fresh model re-forwards).  use_cache=False, or an engine
-        without the cache (Qwen-VL by default, InternLM-XComposer2): every new token
+        With the adapters disabled (disable_adapter()) or absent the plain weights are decoded.  Qwen-VL and InternLM-XComposer2 take
+        these routes once the caller has switched their cache on (enable_kv_cache(); a fresh model re-forwards).  use_cache=False, or an
+        engine without the cache (Qwen-VL and InternLM-XComposer2 by default): every new token
         re-runs the forward of the whole sequence (the vision features of the batch are cached by the engine), the running batch
         left-padded to a multiple of 32 tokens so that the engine sees a new shape every 32 steps, not every step.
 
@@ -517,7 +517,7 @@ class LlavaForRL(nn.Module):
             prefilled ONCE into a SharedPromptKVCache, the first logits are repeated n times, and every further token is one decode step
             of P * n rows over the shared prompt K / V plus each sample's own tail (engine.decode_step -> vlr_decoder_layer_decode_shared):
             one prefill, one copy of the prompt's K / V, one read of it per token;
-          n > 1 otherwise (use_cache=False, Qwen-VL without enable_kv_cache(), InternLM-XComposer2, other head dims): ids, mask and every image input are expanded
+          n > 1 otherwise (use_cache=False, Qwen-VL / InternLM-XComposer2 without enable_kv_cache(), other head dims): ids, mask and every image input are expanded
             by repeat_interleave(n) and the loop above runs on P * n rows - nothing is shared.
 
         Stop rules of a `generation_config` (each read with getattr(..., None); a call that passes none of them is unchanged):
