@@ -28,7 +28,7 @@ extern "C" int vlr_abi_version(void) { return 9; }
 
 // ---- in-library kernel timing (bench.py roofline leg): HIP events on the launch stream around selected kernels -------
 #include <vector>
-struct ProfRec { hipEvent_t a, b; int kernel; double work; };
+struct ProfRec { hipEvent_t a, b; int kernel; double work; bool ended; };
 static std::vector<ProfRec> g_prof;
 static int g_prof_on = 0;                 // 0 off; N >= 1: bracket one launch in N (pseudo-randomly, per kernel id)
 #define VLR_PROF_KERNELS 16
@@ -54,23 +54,26 @@ int vlr_prof_begin(int kernel, double work, hipStream_t st) {
     // the launches of one kernel id repeat with the layer structure: pick by a hash of the running count, not every N-th
     if (g_prof_on > 1 && (unsigned)((n * 2654435761ul) >> 16) % (unsigned)g_prof_on != 0) return -1;
     ProfRec r;
-    r.kernel = kernel; r.work = work;
+    r.kernel = kernel; r.work = work; r.ended = false;
     hipEventCreate(&r.a); hipEventCreate(&r.b);
     hipEventRecord(r.a, st);
     g_prof.push_back(r);
     return (int)g_prof.size() - 1;
 }
 void vlr_prof_end(int idx, hipStream_t st) {
-    if (idx >= 0) hipEventRecord(g_prof[idx].b, st);
+    if (idx >= 0) { hipEventRecord(g_prof[idx].b, st); g_prof[idx].ended = true; }
 }
 // out[kernel*3 + {0,1,2}] = {launches, total ms, total work}; kernels 0..nk-1.  Synchronises on the recorded events.
 extern "C" int vlr_prof_collect(double* out, int nk) {
     double ms_sum[VLR_PROF_KERNELS] = {0}, n_sampled[VLR_PROF_KERNELS] = {0};
     for (int i = 0; i < nk * 3; ++i) out[i] = 0.0;
     for (auto& r : g_prof) {
+        // a bracket whose launch was declined (end never recorded) is not queried: hipEventElapsedTime fails on it, and HIP keeps that
+        // failure as the thread's last error - the next launch check (vlr_check_launch, or the caller's own) then reports a failed launch
+        if (!r.ended) continue;
         hipEventSynchronize(r.b);
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) continue;     // a bracket whose launch was declined (end never recorded)
+        if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) { (void)hipGetLastError(); continue; }
         ms_sum[r.kernel] += ms; n_sampled[r.kernel] += 1.0;
     }
     for (int k = 0; k < nk && k < VLR_PROF_KERNELS; ++k) {
