@@ -233,6 +233,14 @@ int vlr_colsum(const void* X, int R, int C, int ld, void* out, int accumulate, v
 int vlr_colsum_f32(const void* X, int R, int C, int ld, float* out, void* workspace, vlr_stream_t stream);
 int vlr_gather_rows(const void* src, const int* rows, void* dst, int R, int H, vlr_stream_t stream);
 int vlr_scatter_rows(const void* src, const int* rows, void* dst, int R, int H, vlr_stream_t stream);
+/* The two row copies of the row-compact policy backward (vlr_decoder_layer_bwd_compact; maps: vlr_row_maps below).  bf16 rows of W
+ * columns, 16-byte accesses.  Preconditions of both: no null pointer; M / Mc > 0; W > 0 and W % 8 == 0; src, dst 16-byte aligned and
+ * not overlapping; every map entry inside its source (dense_own[m] < the rows of src, compact_rows[j] and twin[j] < the rows of src).
+ *   vlr_expand_rows_zero: dst [M][W]: dense row m = src row dense_own[m], or zeros where dense_own[m] < 0.
+ *   vlr_fold_rows       : dst [Mc][W]: row j = src row compact_rows[j], plus src row twin[j] where twin[j] >= 0 - the sum formed in
+ *                         fp32 and rounded to bf16 once (round to nearest even).  One writer per row, fixed order: no atomics. */
+int vlr_expand_rows_zero(const void* src, const int* dense_own, void* dst, int M, int W, vlr_stream_t stream);
+int vlr_fold_rows(const void* src, const int* compact_rows, const int* twin, void* dst, int Mc, int W, vlr_stream_t stream);
 /* strided row-list operations on a column block of a wider matrix (PLoRA of InternLM-XComposer2, reference
  * models/InternLMXC2/build_mlp.py:194-202: `res[im_mask] += Plora_B(Plora_A(x[im_mask]))`):
  *   vlr_rows_gather: dst [R][W] (contiguous) = src[rows[r]][0:W], src row stride lds
@@ -469,6 +477,55 @@ int vlr_decoder_layer_bwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, 
                           int accumulate, const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const void* x_in,
                           const void* dx_out, void* dx_in, const int* pos, const int* key_mask, int batch, int S,
                           vlr_stream_t stream);
+
+/* ---- the row-compact POLICY pass: forward kept for a backward, and that backward (additive: vlr_abi_version() does not move) ----
+ * The maps of one [chosen ; rejected] batch, device int32 arrays (vlrlhf/prefix_dedup.py build_policy_plan), M = batch * S:
+ *   compact_rows [Mc], dense_src [M], pos_compact [Mc]   as for vlr_decoder_layer_fwd_compact;
+ *   dense_own [M]   the kept row of a KEPT dense row, -1 for a dropped row;
+ *   twin [Mc]       the dense index of the dropped twin of a shared kept row, -1 for a row that stands for itself alone. */
+typedef struct {
+    const int* compact_rows; const int* dense_src; const int* dense_own; const int* twin; const int* pos_compact;
+    int Mc, tail_rows;
+} vlr_row_maps;
+typedef struct {  /* dense scratch of the attention section, [batch * S] rows each: qkv, dqkv [.][Nq + 2 Nkv]; attn, dattn [.][Nq] */
+    void* qkv; void* attn; void* dattn; void* dqkv;
+} vlr_dense_scratch;
+/* vlr_decoder_layer_fwd_compact with keep_for_backward: 1 writes a->gu as vlr_decoder_layer_fwd_ex does; 0 is
+ * vlr_decoder_layer_fwd_compact itself (which forwards here).  What the pass keeps - every tensor of `a` but a->lse - holds Mc rows.
+ * Preconditions: no null pointer but key_mask; 0 < Mc <= batch * S; 0 <= tail_rows <= Mc; heads % kv_heads == 0; the maps as
+ * described above; every buffer sized as stated there; nothing is allocated. */
+int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a, const void* x_in,
+                                     const int* pos_compact, const int* dense_src, const int* compact_rows, int Mc, int tail_rows,
+                                     void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S, int keep_for_backward,
+                                     vlr_stream_t stream);
+/* The activations that pass left on Mc rows (`c`), copied to the dense layout (`d`: batch * S = M rows) through dense_src, so that the
+ * unchanged vlr_decoder_layer_bwd runs on `d` and computes what it computes after a dense forward - the same bits wherever
+ * vlr_decoder_layer_compact_exact says 1.  Copied: x_out, and with keep_for_backward = 1 also xn1, rstd1, x_mid, xn2, rstd2, gu, act.
+ * NOT copied: q|k|v, attn, lse - give the compact forward d->qkv and d->attn as its dense scratch and set c->lse = d->lse.
+ * Preconditions: no null pointer among the copied tensors; M > 0; dense_src[m] < Mc for every m; hidden % 8 == 0 and inter % 8 == 0;
+ * `c` and `d` do not overlap; nothing is allocated.  vlr_gather_f32: dst[i] = src[idx[i]], n > 0 fp32 values (the rstd copies). */
+int vlr_layer_acts_expand(const vlr_llama_cfg* cfg, const vlr_layer_acts* c, const vlr_layer_acts* d, const int* dense_src, int M,
+                          int keep_for_backward, vlr_stream_t stream);
+int vlr_gather_f32(const float* src, const int* idx, float* dst, int n, vlr_stream_t stream);
+/* The adjoint of that pass: vlr_decoder_layer_bwd with every row-wise call at Mc rows, in the same order.  x_in, dx_out, dx_in, the
+ * tensors of `a` (a->lse excepted) and of `ws` (ws->delta excepted: [batch][heads][align64(S)]) hold Mc rows.  The attention backward
+ * alone runs densely: d attn is expanded with zeros on the dropped rows (no gradient enters there: their delta and dS are exactly 0),
+ * q|k|v and attn are expanded through dense_src, the unchanged vlr_attn_bwd_gqa runs on [batch * S] rows, and d qkv is folded - a shared
+ * row receives its own gradient plus what the rejected response rows sent to the dropped copy's keys and values; that one bf16 sum is
+ * the only rounding the dense backward does not have.  ws->dqkv holds the folded d qkv [Mc] afterwards (its column sum is the gradient
+ * of a q|k|v bias).
+ * Preconditions: no null pointer but key_mask, in the structs too; 0 < m->Mc <= batch * S; heads % kv_heads == 0;
+ * hidden % 8 == 0, (Nq + 2 Nkv) % 8 == 0 and Nq % 8 == 0 (the row copies); nothing is allocated.  The weight-gradient GEMMs contract
+ * over the kept rows: Mc % 8 == 0 lets dW_gate|up and dW_down share one launch (vlr_gemm_bf16_tn_pair), as in the dense backward. */
+int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                                  const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const vlr_row_maps* m,
+                                  const vlr_dense_scratch* d, const void* x_in, const void* dx_out, void* dx_in, const int* key_mask,
+                                  int batch, int S, vlr_stream_t stream);
+/* 1: every kept row of the row-compact forward over Mc of batch * S rows is computed by the kernel, and in the K order, the dense
+ * forward computes it in - the two passes agree bit for bit on the kept rows (16-byte aligned operands assumed).  Host arithmetic
+ * only: all four projections take the persistent 256-tile kernel at batch * S and at Mc rows, and the rows the dense residual
+ * projections peel (vlr_gemm_peel_rows) lie inside the tail_rows kept last rows.  0 otherwise, and for arguments out of range. */
+int vlr_decoder_layer_compact_exact(const vlr_llama_cfg* cfg, int batch, int S, int Mc, int tail_rows);
 
 /* ---- LoRA (peft) adapters on the seven decoder linears (reference: LoraConfig built in utils/auto_load.py:559-571 from
  * LlavaForRL.default_lora_target, Llava/__init__.py:273-286; r/alpha/dropout defaults dpo.py:60-63, scripts/ddpo_llava.sh:24-31).

@@ -651,6 +651,77 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16_t* __restr
     for (int c = threadIdx.x * 8; c < H; c += 256 * 8)
         *reinterpret_cast<u32x4*>(dst + d + c) = *reinterpret_cast<const u32x4*>(src + (size_t)r * H + c);
 }
+// The two row copies of the row-compact policy backward (layers.cpp: vlr_decoder_layer_bwd_compact), in gather_rows_kernel's access
+// pattern: 16-byte accesses, four loads in flight per thread before the first store.
+// dst [M][W]: dense row m = compact row own[m], or zeros where own[m] < 0 (a dropped row: no gradient enters through it)
+__global__ __launch_bounds__(256) void expand_rows_zero_kernel(const bf16_t* __restrict__ src, const int* __restrict__ own,
+                                                               bf16_t* __restrict__ dst, int M, int W) {
+    const int m = blockIdx.x;
+    const int o = own[m];
+    const size_t s = (size_t)(o < 0 ? 0 : o) * W;
+    for (int c0 = threadIdx.x * 8; c0 < W; c0 += 4 * 256 * 8) {
+        u32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 256 * 8;
+            v[j] = u32x4{0u, 0u, 0u, 0u};
+            if (c < W && o >= 0) v[j] = *reinterpret_cast<const u32x4*>(src + s + c);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j * 256 * 8;
+            if (c < W) *reinterpret_cast<u32x4*>(dst + (size_t)m * W + c) = v[j];
+        }
+    }
+}
+// dst [Mc][W]: compact row j = dense row rows[j], plus dense row twin[j] where twin[j] >= 0 (the dropped copy of a shared row): the sum
+// in fp32, rounded to bf16 once.  One writer per output row, a fixed order of the two addends: no atomics.
+__global__ __launch_bounds__(256) void fold_rows_kernel(const bf16_t* __restrict__ src, const int* __restrict__ rows,
+                                                        const int* __restrict__ twin, bf16_t* __restrict__ dst, int Mc, int W) {
+    const int r = blockIdx.x;
+    const size_t s = (size_t)rows[r] * W;
+    const int t = twin[r];
+    if (t < 0) {
+        for (int c0 = threadIdx.x * 8; c0 < W; c0 += 4 * 256 * 8) {
+            u32x4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = c0 + j * 256 * 8;
+                if (c < W) v[j] = *reinterpret_cast<const u32x4*>(src + s + c);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = c0 + j * 256 * 8;
+                if (c < W) *reinterpret_cast<u32x4*>(dst + (size_t)r * W + c) = v[j];
+            }
+        }
+        return;
+    }
+    const size_t s2 = (size_t)t * W;
+    for (int c0 = threadIdx.x * 8; c0 < W; c0 += 2 * 256 * 8) {      // two columns groups x two rows = four loads in flight
+        u32x4 va[2], vb[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = c0 + j * 256 * 8;
+            if (c < W) {
+                va[j] = *reinterpret_cast<const u32x4*>(src + s + c);
+                vb[j] = *reinterpret_cast<const u32x4*>(src + s2 + c);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = c0 + j * 256 * 8;
+            if (c < W) {
+                float a[8], b[8];
+                unpack8(va[j], a);
+                unpack8(vb[j], b);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) a[e] += b[e];
+                *reinterpret_cast<u32x4*>(dst + (size_t)r * W + c) = pack8(a);
+            }
+        }
+    }
+}
 // strided variants for sub-matrices (PLoRA of InternLM-XComposer2: the image rows of one column block of a fused activation)
 __global__ __launch_bounds__(256) void rows_gather_kernel(const bf16_t* __restrict__ src, int lds, const int* __restrict__ rows,
                                                           bf16_t* __restrict__ dst, int W) {
@@ -919,6 +990,28 @@ extern "C" int vlr_scatter_rows(const void* src, const int* rows, void* dst, int
     VLR_REQUIRE(R > 0 && H % 8 == 0, "vlr_scatter_rows: bad shape");
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(R), dim3(256), 0, st, (const bf16_t*)src, rows, (bf16_t*)dst, R, H);
     return vlr_check_launch("vlr_scatter_rows");
+}
+// dst[i] = src[idx[i]]: one fp32 per row (the rstd of a row-compact pass expanded to the dense rows)
+__global__ __launch_bounds__(256) void gather_f32_kernel(const float* __restrict__ src, const int* __restrict__ idx, float* __restrict__ dst, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
+extern "C" int vlr_gather_f32(const float* src, const int* idx, float* dst, int n, hipStream_t st) {
+    VLR_REQUIRE(src && idx && dst && n > 0, "vlr_gather_f32: bad arguments (n = %d)", n);
+    hipLaunchKernelGGL(gather_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, idx, dst, n);
+    return vlr_check_launch("vlr_gather_f32");
+}
+extern "C" int vlr_expand_rows_zero(const void* src, const int* dense_own, void* dst, int M, int W, hipStream_t st) {
+    VLR_REQUIRE(src && dense_own && dst, "vlr_expand_rows_zero: null argument");
+    VLR_REQUIRE(M > 0 && W > 0 && W % 8 == 0, "vlr_expand_rows_zero: bad shape M=%d W=%d (W must be a positive multiple of 8)", M, W);
+    hipLaunchKernelGGL(expand_rows_zero_kernel, dim3(M), dim3(256), 0, st, (const bf16_t*)src, dense_own, (bf16_t*)dst, M, W);
+    return vlr_check_launch("vlr_expand_rows_zero");
+}
+extern "C" int vlr_fold_rows(const void* src, const int* compact_rows, const int* twin, void* dst, int Mc, int W, hipStream_t st) {
+    VLR_REQUIRE(src && compact_rows && twin && dst, "vlr_fold_rows: null argument");
+    VLR_REQUIRE(Mc > 0 && W > 0 && W % 8 == 0, "vlr_fold_rows: bad shape Mc=%d W=%d (W must be a positive multiple of 8)", Mc, W);
+    hipLaunchKernelGGL(fold_rows_kernel, dim3(Mc), dim3(256), 0, st, (const bf16_t*)src, compact_rows, twin, (bf16_t*)dst, Mc, W);
+    return vlr_check_launch("vlr_fold_rows");
 }
 extern "C" int vlr_rows_gather(const void* src, int lds, const int* rows, void* dst, int R, int W, hipStream_t st) {
     VLR_REQUIRE(R > 0 && W > 0 && W % 8 == 0 && lds % 8 == 0 && lds >= W, "vlr_rows_gather: bad shape R=%d W=%d lds=%d", R, W, lds);

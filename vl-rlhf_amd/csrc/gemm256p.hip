@@ -1775,3 +1775,22 @@ bool vlr_gemm256p_try_launch(int layout, const GemmParams& p_in, hipStream_t str
     vlr_prof_end(pi, stream);
     return true;
 }
+
+// Host arithmetic for vlr_decoder_layer_compact_exact (layers.cpp): which kernel the launches above pick for a shape, 16-byte aligned
+// operands assumed - the predicates of vlr_gemm256p_try_launch and vlr_gemm256p_fused_try_launch restated without a launch.
+// plain NT product with a residual (o_proj / down_proj; res_f32: the fp32 stream): 0 = not this kernel, 1 = per-tile, 2 = continuous pipeline
+int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % 8 != 0) return 0;
+    const int ntiles = ((M + PT - 1) / PT) * ((N + PT - 1) / PT);
+    if (ntiles < 192) return 0;
+    const int tiles = persist_grid(ntiles, gemm256p_n_cu());
+    const bool shape_ok = res_f32 ? N % 4 == 0 : false;      // a bf16 residual stays on the per-tile kernel (res_ok above)
+    return (ntiles > tiles && shape_ok && K >= 4 * PK) ? 2 : 1;
+}
+// fused NT projections: fuse 1 (SwiGLU; N = 2 I) and 2 (RoPE): 1 = the fused kernel takes every row, whatever the row count
+int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols) {
+    if (K < 4 * PK || K % 8 != 0) return 0;
+    if (fuse == 2) return N % PT == 0 && rope_cols % PT == 0;
+    if (fuse == 1) return (N >> 1) % 8 == 0;
+    return 0;
+}

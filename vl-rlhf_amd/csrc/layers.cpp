@@ -68,16 +68,17 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
     CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
     return VLR_OK;
 }
-// Row-compact no-grad layer (keep_for_backward = 0 semantics): the row-wise operators run on the Mc kept rows of a batch whose other rows
+// Row-compact layer: the row-wise operators run on the Mc kept rows of a batch whose other rows
 // duplicate a kept one (the shared prompt of a DPO pair: causal attention makes the rejected sequence's prompt rows equal the chosen
 // sequence's in every layer).  Attention alone sees the dense [batch * S] layout, rebuilt by a row copy through dense_src and compacted
 // again through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st);      // gemm.hip: proj_res with the rows of the 128x128 kernel named by the caller
-extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
-                                             const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
-                                             int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
-                                             int S, vlr_stream_t st) {
+// keep_for_backward = 1 (the policy pass): gate | up is written too, as in vlr_decoder_layer_fwd_ex; what the backward reads holds Mc rows
+extern "C" int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                                const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
+                                                int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
+                                                int S, int keep_for_backward, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && a && x_in && pos_compact && dense_src && compact_rows && qkv_dense && attn_dense,
                 "vlr_decoder_layer_fwd_compact: null argument");
     const int H = cfg->hidden, I = cfg->inter, M = batch * S;
@@ -102,8 +103,108 @@ extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr
     CHECK(vlr_gather_rows(attn_dense, compact_rows, a->attn, Mc, Nq, st));       // compact row j = dense row compact_rows[j]
     CHECK(vlr_internal_gemm_res_peel(rf, a->attn, w->wo, a->x_mid, x_in, Mc, H, Nq, peel_rows, st));
     CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, Mc, H, cfg->rms_eps, st));
-    CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, Mc, I, H, H, 0, st));
+    CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, Mc, I, H, H, keep_for_backward ? 1 : 0, st));
     CHECK(vlr_internal_gemm_res_peel(rf, a->act, w->wdown, a->x_out, a->x_mid, Mc, H, I, peel_rows, st));
+    return VLR_OK;
+}
+extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                             const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
+                                             int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
+                                             int S, vlr_stream_t st) {
+    return vlr_decoder_layer_fwd_compact_ex(cfg, w, a, x_in, pos_compact, dense_src, compact_rows, Mc, tail_rows, qkv_dense, attn_dense,
+                                            key_mask, batch, S, 0, st);
+}
+// What vlr_decoder_layer_fwd_compact_ex left on Mc rows (`c`), copied to the dense layout (`d`, batch * S rows) through dense_src: a
+// dropped row takes its twin's values, which ARE its values - the dense backward then runs unchanged on `d` and computes what it
+// computes after a dense forward.  q|k|v, attn and lse are not copied: the compact forward was given d->qkv / d->attn as its dense
+// scratch and d->lse as its lse.  keep_for_backward = 0 (a checkpointed pass): x_out alone
+extern "C" int vlr_gather_f32(const float* src, const int* idx, float* dst, int n, hipStream_t st);
+extern "C" int vlr_layer_acts_expand(const vlr_llama_cfg* cfg, const vlr_layer_acts* c, const vlr_layer_acts* d, const int* dense_src,
+                                     int M, int keep_for_backward, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && c && d && dense_src && M > 0, "vlr_layer_acts_expand: null argument");
+    const int H = cfg->hidden, I = cfg->inter;
+    const int Hr = cfg->resid_f32 ? 2 * H : H;       // (fp32 residual rows as 16-bit columns)
+    VLR_REQUIRE(H % 8 == 0 && I % 8 == 0, "vlr_layer_acts_expand: hidden %d and inter %d must be multiples of 8", H, I);
+    VLR_REQUIRE(c->x_out && d->x_out, "vlr_layer_acts_expand: null x_out");
+    CHECK(vlr_gather_rows(c->x_out, dense_src, d->x_out, M, Hr, st));
+    if (!keep_for_backward) return VLR_OK;
+    VLR_REQUIRE(c->xn1 && c->rstd1 && c->x_mid && c->xn2 && c->rstd2 && c->gu && c->act && d->xn1 && d->rstd1 && d->x_mid && d->xn2 &&
+                d->rstd2 && d->gu && d->act, "vlr_layer_acts_expand: null activation pointer");
+    CHECK(vlr_gather_rows(c->xn1, dense_src, d->xn1, M, H, st));
+    CHECK(vlr_gather_f32(c->rstd1, dense_src, d->rstd1, M, st));
+    CHECK(vlr_gather_rows(c->x_mid, dense_src, d->x_mid, M, Hr, st));
+    CHECK(vlr_gather_rows(c->xn2, dense_src, d->xn2, M, H, st));
+    CHECK(vlr_gather_f32(c->rstd2, dense_src, d->rstd2, M, st));
+    CHECK(vlr_gather_rows(c->gu, dense_src, d->gu, M, 2 * I, st));
+    CHECK(vlr_gather_rows(c->act, dense_src, d->act, M, I, st));
+    return VLR_OK;
+}
+// gemm256p.hip: the kernel a launch would pick, as host arithmetic
+int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32);
+int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
+extern "C" int vlr_decoder_layer_compact_exact(const vlr_llama_cfg* cfg, int batch, int S, int Mc, int tail_rows) {
+    if (!cfg || batch <= 0 || S <= 0) return 0;
+    const long Ml = (long)batch * S;
+    if (Ml > 0x7fffffffL || Mc <= 0 || Mc > Ml || tail_rows < 0 || tail_rows > Mc) return 0;
+    const int M = (int)Ml, H = cfg->hidden, I = cfg->inter;
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    if (H <= 0 || I <= 0 || kvh <= 0 || cfg->heads % kvh != 0) return 0;
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    // q|k|v + RoPE and gate|up + SwiGLU: the fused kernel takes every row of any row count (its peeled tile rows run the same kernel), or
+    // none - then the plain GEMM's route depends on the row count
+    if (cfg->head_dim != 128 || !vlr_internal_gemm256p_fused_takes(2, N, H, Nq + Nkv) || !vlr_internal_gemm256p_fused_takes(1, 2 * I, H, 0))
+        return 0;
+    // o_proj / down_proj: the dense launch peels its last rows to the 128x128 split-K kernel; the compact launch peels the same rows when
+    // they are kept (vlr_decoder_layer_fwd_compact_ex), and both main parts must run the same variant of the persistent kernel
+    const int peel = vlr_gemm_peel_rows(M, H);
+    if (peel > tail_rows || peel >= Mc) return 0;
+    if (H <= 512) return 0;          // (the skinny split-K route of the plain GEMM is chosen by the row count)
+    const int Ks[2] = {Nq, I};
+    for (int K : Ks) {
+        const int vd = vlr_internal_gemm256p_res_variant(M - peel, H, K, cfg->resid_f32);
+        if (vd == 0 || vd != vlr_internal_gemm256p_res_variant(Mc - peel, H, K, cfg->resid_f32)) return 0;
+    }
+    return 1;
+}
+// Backward of vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1): vlr_decoder_layer_bwd with every row-wise call at Mc rows, the
+// attention backward alone on the dense layout (include/vlr.h)
+double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip
+extern "C" int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                                             const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const vlr_row_maps* m,
+                                             const vlr_dense_scratch* d, const void* x_in, const void* dx_out, void* dx_in,
+                                             const int* key_mask, int batch, int S, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && g && a && ws && m && d && x_in && dx_out && dx_in, "vlr_decoder_layer_bwd_compact: null argument");
+    VLR_REQUIRE(m->compact_rows && m->dense_src && m->dense_own && m->twin && m->pos_compact, "vlr_decoder_layer_bwd_compact: null row map");
+    VLR_REQUIRE(d->qkv && d->attn && d->dattn && d->dqkv, "vlr_decoder_layer_bwd_compact: null dense scratch");
+    const int H = cfg->hidden, I = cfg->inter, M = batch * S, Mc = m->Mc;
+    VLR_REQUIRE(batch > 0 && S > 0 && Mc > 0 && Mc <= M, "vlr_decoder_layer_bwd_compact: %d compact rows of %d x %d dense rows", Mc, batch, S);
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_bwd_compact: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    // ---- MLP
+    CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, Mc, I, H, st));
+    CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, Mc, accumulate, st));
+    CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, Mc, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
+    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, Mc, H, st));
+    // ---- attention
+    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;      // (vlr_decoder_layer_bwd's rule, unchanged)
+    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, Mc, H, Nq, Nq, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, Mc, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
+    // a shared row's d attn is the sum of both branches' gradients already (downstream of it the two copies were one row): it enters at
+    // the chosen copy, the dropped copy gets dO = 0 - there delta = 0 and dS = P (dP - delta) = 0 exactly
+    CHECK(vlr_expand_rows_zero(ws->dattn, m->dense_own, d->dattn, M, Nq, st));
+    CHECK(vlr_gather_rows(a->qkv, m->dense_src, d->qkv, M, N, st));
+    CHECK(vlr_gather_rows(a->attn, m->dense_src, d->attn, M, Nq, st));
+    CHECK(vlr_attn_bwd_gqa(d->qkv, off(d->qkv, Nq), off(d->qkv, (size_t)Nq + Nkv), N, d->attn, d->dattn, Nq, a->lse, ws->delta,
+                           key_mask, d->dqkv, off(d->dqkv, Nq), off(d->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
+                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    // the rejected response rows' dK / dV on the prompt keys landed on the dropped rows: added to the chosen twin (fp32, one rounding)
+    CHECK(vlr_fold_rows(d->dqkv, m->compact_rows, m->twin, ws->dqkv, Mc, N, st));
+    CHECK(vlr_rope_heads(ws->dqkv, m->pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
+    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, Mc, 0, st));
+    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, Mc, N, H, H, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, Mc, H, N, N, H, H, 0, 0, 0, 0, st));
+    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, Mc, H, st));
     return VLR_OK;
 }
 extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,

@@ -34,6 +34,14 @@ class LayerBwdWs(C.Structure):
     _fields_ = [(n, P) for n in ("dact", "dxn", "dattn", "dqkv", "dx_mid", "delta", "norm_ws")]
 
 
+class RowMaps(C.Structure):      # vlr_row_maps: the maps of a row-compact policy pass (prefix_dedup.build_policy_plan)
+    _fields_ = [(n, P) for n in ("compact_rows", "dense_src", "dense_own", "twin", "pos_compact")] + [("Mc", I), ("tail_rows", I)]
+
+
+class DenseScratch(C.Structure):      # vlr_dense_scratch: the dense attention operands of vlr_decoder_layer_bwd_compact
+    _fields_ = [(n, P) for n in ("qkv", "attn", "dattn", "dqkv")]
+
+
 class LoraWeights(C.Structure):
     _fields_ = [("r", I), ("scale", F), ("dropout", F)] + [(n, P) for n in ("a_qkv", "b_qkv", "a_o", "b_o", "a_gu", "b_gu", "a_down", "b_down")] + [("qkv_targets", I), ("mask_bits", P)]
 
@@ -140,6 +148,13 @@ _SIGS = {
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],
     "vlr_decoder_layer_fwd_ex": [P, P, P, P, P, P, I, I, I, P],
     "vlr_decoder_layer_fwd_compact": [P, P, P, P, P, P, P, I, I, P, P, P, I, I, P],
+    # the row-compact policy pass (include/vlr.h "the row-compact POLICY pass")
+    "vlr_decoder_layer_fwd_compact_ex": [P, P, P, P, P, P, P, I, I, P, P, P, I, I, I, P],
+    "vlr_decoder_layer_bwd_compact": [P, P, P, I, P, P, P, P, P, P, P, P, I, I, P],
+    "vlr_layer_acts_expand": [P, P, P, P, I, I, P],
+    "vlr_gather_f32": [P, P, P, I, P],
+    "vlr_expand_rows_zero": [P, P, P, I, I, P],
+    "vlr_fold_rows": [P, P, P, P, I, I, P],
     "vlr_gemm_swiglu": [P, P, P, P, I, I, I, I, I, P],
     "vlr_gemm_swiglu_bwd": [P, P, P, P, I, I, I, P],
     "vlr_gemm_qkv_rope": [P, P, P, P, P, P, I, I, I, I, I, I, I, P],
@@ -211,6 +226,7 @@ _INT_HELPERS = {
     "vlr_grad_sqnorm_workspace_bytes": [],
     "vlr_abi_version": [],
     "vlr_gemm_peel_rows": [I, I],
+    "vlr_decoder_layer_compact_exact": [P, I, I, I, I],
     "vlr_prof_enable": [I],
     "vlr_prof_collect": [P, I],
     "vlr_gemm_set_splitk_workspace": [P, L],

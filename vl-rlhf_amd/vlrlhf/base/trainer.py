@@ -772,6 +772,12 @@ class VLDPOTrainer(VLTrainerLoop):
         (LlavaForRL.reference_pass) are told so for the duration of the call"""
         return owner.reference_pass() if hasattr(owner, "reference_pass") else contextlib.nullcontext()
 
+    @staticmethod
+    def _policy_pass(owner):
+        """the policy forward of a DPO step is back-propagated as a whole and reads the two sequences of every pair: models that can run
+        the pair's shared prompt rows once, forward and backward (LlavaForRL.policy_pass), are told so for the duration of the call"""
+        return owner.policy_pass() if hasattr(owner, "policy_pass") else contextlib.nullcontext()
+
     def null_ref_context(self):
         """trl==0.8.1 DPOTrainer.null_ref_context: the peft policy with its adapters disabled is the reference model."""
         return self.model.disable_adapter() if self.is_peft_model else contextlib.nullcontext()
@@ -849,7 +855,8 @@ class VLDPOTrainer(VLTrainerLoop):
         elif self._ref_side_ok(batch):
             rc, rr = self._launch_reference(batch)
             use_side = True
-        pc, pr, pcl, prl = self.concatenated_forward(model, batch)
+        with self._policy_pass(model):
+            pc, pr, pcl, prl = self.concatenated_forward(model, batch)
         if use_side:
             main.wait_stream(self._ref_stream)
             rc.record_stream(main)

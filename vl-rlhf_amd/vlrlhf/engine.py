@@ -560,6 +560,12 @@ class LlavaHipEngine:
         self.prefix_dedup_min_share = 1.0 / 8    # taken when the shared rows are at least this share of the M dense rows: below it the row copies cost what the GEMMs save
         self.prefix_dedup_passes = 0             # row-compact passes so far
         self.last_prefix_dedup = None            # dict(P, Mc, M) of the last row-compact pass
+        # ... and so does the policy's training pass, forward and backward (forward_hidden(save=True, prefix_dedup_rows=True))
+        self.prefix_dedup_policy = True          # False: the policy pass is dense (prefix_dedup = False withholds both)
+        self.prefix_dedup_policy_exact_only = True   # taken only where its forward is the dense forward bit for bit (vlr_decoder_layer_compact_exact)
+        self.prefix_dedup_policy_backward = False    # True: the backward runs on the kept rows too (vlr_decoder_layer_bwd_compact): a third fewer GEMM rows, gradients within bf16 rounding of the dense backward's but not its bits
+        self.prefix_dedup_policy_passes = 0      # row-compact policy passes so far
+        self.last_prefix_dedup_policy = None     # dict(P, Mc, M, exact) of the last one
         self._norm_ws = torch.empty(_hip.helper("vlr_rmsnorm_bwd_workspace_bytes", self.H), dtype=torch.uint8, device=self.dev)
         self._colsum_ws = torch.empty(_hip.helper("vlr_colsum_workspace_bytes", max(self.H, self.Nqkv, 8)), dtype=torch.uint8, device=self.dev)
         self._sq_ws = torch.empty(_hip.helper("vlr_grad_sqnorm_workspace_bytes"), dtype=torch.uint8, device=self.dev)
@@ -999,6 +1005,89 @@ class LlavaHipEngine:
             return None
         return plan
 
+    def _policy_plan(self, e, ids, Bn, meta):
+        """the row maps of a row-compact POLICY pass over this [chosen ; rejected] batch (prefix_dedup.build_policy_plan: Mc % 8 == 0),
+        on the device, or None when the pass is to run dense: too few shared rows, or - prefix_dedup_policy_exact_only - a shape at
+        which the compact forward would not be the dense forward bit for bit.  Cached on the batch (`meta`) under its own key."""
+        if meta is not None and "prefix_dedup_policy" in meta:
+            plan = meta["prefix_dedup_policy"]
+        else:
+            S = e["S"]
+            src, mask, pos = (e[k].reshape(Bn, S) for k in ("src", "mask", "pos"))
+            if meta is not None and "prefix_dedup" in meta:
+                P = meta["prefix_dedup"]["P"]                  # (the reference pass of this batch has read them already)
+            else:
+                P = prefix_dedup.shared_prefix_lengths(prefix_dedup.source_key(src, ids), mask, pos).tolist()
+            plan = prefix_dedup.build_policy_plan(P, S)
+            for k in ("compact_rows", "dense_src", "dense_own", "twin"):
+                plan[k] = plan[k].to(self.dev)
+            plan["pos"] = pos.reshape(-1)[plan["compact_rows"].long()].contiguous()
+            plan["struct"] = _hip.RowMaps(plan["compact_rows"].data_ptr(), plan["dense_src"].data_ptr(), plan["dense_own"].data_ptr(),
+                                          plan["twin"].data_ptr(), plan["pos"].data_ptr(), plan["Mc"], plan["tail"])
+            if meta is not None:
+                meta["prefix_dedup_policy"] = plan
+        if plan["shared"] == 0 or plan["shared"] < self.prefix_dedup_min_share * plan["M"] or plan["Mc"] % 8:
+            return None
+        # (asked per pass: the rows the dense launches peel depend on the CUs the compute kernels have at the moment)
+        plan["exact"] = bool(_hip.helper("vlr_decoder_layer_compact_exact", _hip.C.byref(self.llama_cfg), Bn, e["S"], plan["Mc"], plan["tail"]))
+        if self.prefix_dedup_policy_exact_only and not plan["exact"]:
+            return None
+        return plan
+
+    def _forward_layers_compact_policy(self, ws, e, plan, x0, Bn, S, tag, ckpt):
+        """the decoder layers and the final norm of a pass that will be back-propagated, on the kept rows of `plan`;
+        -> (hidden [M, H] dense, rstd_f [Mc], x_last [Mc], acts, x0_c [Mc]).  The activation sets are the dense pass's own (their first
+        Mc rows; lse keeps its dense shape); q|k|v and the attention output also exist densely, for vlr_attn_fwd_gqa alone."""
+        M, Mc, H = plan["M"], plan["Mc"], self.H
+        rows, dsrc = plan["compact_rows"], plan["dense_src"]
+        w16 = 2 if x0.dtype == torch.float32 else 1                  # (row copy: fp32 rows = 2H 16-bit columns)
+        x0_c = self._buf((tag, "dedup_x0", Bn, S), (M, H), x0.dtype)
+        _hip.call("vlr_gather_rows", x0, rows, x0_c, Mc, H * w16)
+        qkv_d = self._buf((tag, "dedup_qkv", Bn, S), (M, self.Nqkv))
+        attn_d = self._buf((tag, "dedup_attn", Bn, S), (M, self.Nq))
+        x, acts = x0_c, []
+        for l in range(self.L):
+            a = self._ckpt_acts(tag, l, Bn, S) if ckpt else self._layer_acts(tag, l, Bn, S)
+            self._layer_fwd_compact_call(ws, l, a, x, e, plan, qkv_d, attn_d, Bn, S, not ckpt)
+            acts.append(a)
+            x = a["x_out"]
+        hidden_c = self._buf((tag, "dedup_hidden", Bn, S), (M, H))
+        rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
+        self._norm_fwd(x, ws.v["norm"], hidden_c, rstd_f, Mc)
+        hidden = torch.empty(M, H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_gather_rows", hidden_c, dsrc, hidden, M, H)
+        self.prefix_dedup_policy_passes += 1
+        self.last_prefix_dedup_policy = dict(P=list(plan["P"]), Mc=Mc, M=M, exact=plan["exact"], backward="compact")
+        return hidden, rstd_f, x, acts, x0_c
+
+    def _forward_layers_compact_expand(self, ws, e, plan, x0, Bn, S, tag, ckpt):
+        """the decoder layers of a pass that will be back-propagated DENSELY: every layer's forward runs on the kept rows of `plan`
+        into one of two scratch activation sets and what the backward reads is copied to the layer's dense set (vlr_layer_acts_expand;
+        q|k|v, attn and lse are written there by the compact forward itself).  -> (x_last [M] dense, acts): the context is a dense
+        pass's context, and where the plan is exact the backward computes the dense step's bits.  Under gradient checkpointing only
+        x_out is copied; the recompute is the dense layer forward, as ever."""
+        M, Mc, H = plan["M"], plan["Mc"], self.H
+        w16 = 2 if x0.dtype == torch.float32 else 1                  # (row copy: fp32 rows = 2H 16-bit columns)
+        x = self._buf((tag, "dedup_x0", Bn, S), (M, H), x0.dtype)
+        _hip.call("vlr_gather_rows", x0, plan["compact_rows"], x, Mc, H * w16)
+        acts = []
+        for l in range(self.L):
+            a = self._ckpt_acts(tag, l, Bn, S) if ckpt else self._layer_acts(tag, l, Bn, S)
+            s = self._layer_acts(tag + "/compact", l % 2, Bn, S)
+            sv = dict(s, lse=a["lse"])                               # the attention statistics are dense: written where the backward reads them
+            self._layer_fwd_compact_call(ws, l, dict(struct=self._acts_struct(sv)), x, e, plan, a["qkv"], a["attn"], Bn, S, not ckpt)
+            _hip.call("vlr_layer_acts_expand", self.llama_cfg, s["struct"], a["struct"], plan["dense_src"], M, int(not ckpt))
+            acts.append(a)
+            x = s["x_out"]
+        self.prefix_dedup_policy_passes += 1
+        self.last_prefix_dedup_policy = dict(P=list(plan["P"]), Mc=Mc, M=M, exact=plan["exact"], backward="dense")
+        return acts[-1]["x_out"], acts
+
+    def _layer_fwd_compact_call(self, ws, l, a, x, e, plan, qkv_d, attn_d, Bn, S, keep):
+        """one decoder layer forward of the row-compact policy pass into the activation set `a` (keep: also write what only the backward reads)"""
+        _hip.call("vlr_decoder_layer_fwd_compact_ex", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], x, plan["pos"],
+                  plan["dense_src"], plan["compact_rows"], plan["Mc"], plan["tail"], qkv_d, attn_d, e["mask"], Bn, S, int(keep))
+
     def _forward_layers_compact(self, ws, e, plan, x0, Bn, S, tag):
         """the decoder layers and the final norm of a no-grad pass on the kept rows of `plan`; -> (hidden [M, H] dense, rstd_f, x_last)
         The activation set is the pass's dense scratch set (its first Mc rows; lse keeps its dense shape); q|k|v and the attention
@@ -1030,7 +1119,11 @@ class LlavaHipEngine:
         hidden states [Bn*S, H] and the merged labels / mask / positions.  kv_cache (generate's prefill, no-grad, engines with
         supports_kv_cache): each layer's post-RoPE K / V rows are copied into it right after the layer ran.
         prefix_dedup_rows (the trainer's reference passes): a no-grad pass over a [chosen ; rejected] batch (image_dup == 2) computes the
-        rows of each pair's shared prompt once (_prefix_plan) - the context keeps its dense contract, ctx["x_last"] alone is compact."""
+        rows of each pair's shared prompt once (_prefix_plan) - the context keeps its dense contract, ctx["x_last"] alone is compact.
+        With save=True on the policy weights (the DPO trainer's policy pass) the training forward does the same (_policy_plan: full
+        fine-tune, no NEFTune; by default only where the compact forward is the dense one bit for bit) and copies what the backward
+        reads to the dense layout: the context is a dense pass's.  With prefix_dedup_policy_backward the backward runs on the kept rows
+        too: ctx["plan"] is set, ctx["acts"], ctx["x_last"], ctx["rstd_f"] and ctx["x0_c"] hold the kept rows, ctx["hidden"] is dense."""
         c = self.cfg
         if ws is self.policy:
             self.wait_optimizer()
@@ -1078,9 +1171,23 @@ class LlavaHipEngine:
         if (prefix_dedup_rows and self.prefix_dedup and self.row_compact_layers and not save and kv_cache is None and image_dup == 2
                 and not use_lora and Bn % 2 == 0):
             plan = self._prefix_plan(e, ids, Bn, meta)
+        # the policy's training pass (VLDPOTrainer asks for it): the forward on the kept rows, the backward dense on the expanded
+        # activations (the dense step's bits where the plan is exact) or - prefix_dedup_policy_backward - on the kept rows too (one more
+        # bf16 rounding per shared d qkv row).  NEFTune draws different noise for the two copies of a prompt row: under it the rows are
+        # not equal, and the pass is dense
+        pplan, x0_c, layers_done = None, None, False
+        if (prefix_dedup_rows and self.prefix_dedup and self.prefix_dedup_policy and self.row_compact_layers and save and ws is self.policy
+                and kv_cache is None and image_dup == 2 and not use_lora and self.lora is None and Bn % 2 == 0 and self.neftune is None):
+            pplan = self._policy_plan(e, ids, Bn, meta)
         if plan is not None:
             hidden, rstd_f, x = self._forward_layers_compact(ws, e, plan, x0, Bn, S, tag)
-        for l in range(self.L if plan is None else 0):
+        elif pplan is not None and self.prefix_dedup_policy_backward:
+            hidden, rstd_f, x, acts, x0_c = self._forward_layers_compact_policy(ws, e, pplan, x0, Bn, S, tag, ckpt)
+            plan = pplan
+        elif pplan is not None:         # compact forward, dense backward: the context below is a dense pass's (the final norm runs on M rows)
+            x, acts = self._forward_layers_compact_expand(ws, e, pplan, x0, Bn, S, tag, ckpt)
+            pplan, layers_done = None, True
+        for l in range(self.L if plan is None and not layers_done else 0):
             if ckpt:
                 a = self._ckpt_acts(tag, l, Bn, S)
             else:
@@ -1103,6 +1210,7 @@ class LlavaHipEngine:
                     img_map=img_map.bool(), hidden=hidden, rstd_f=rstd_f, x_last=x, x0=x0, acts=acts if save else None,
                     vit_feat=vit_feat, feats=feats, proj_z=z, proj_h=h, image_dup=image_dup, n_rows=n_rows, n_feat=n_feat,
                     pack=pack, tag=tag, lora_seed=lora_seed, neftune=nf, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
+                    plan=pplan, x0_c=x0_c,     # a row-compact policy pass: acts, x_last, rstd_f and x0_c hold the plan's Mc kept rows; hidden is dense
                     embed=dict(pos=e["pos"], mask=e["mask"], extra=e.get("extra"), tag=tag, img_map=e["img_map"], plora_seed=e.get("plora_seed"), grad_pass=bool(save)))
 
     # ------------------------------------------------------------------------------------------------ decoding
@@ -1510,8 +1618,22 @@ class LlavaHipEngine:
         acc = int(not self.grad_fresh)
         dxa = self._buf(("dxa", M), (M, self.H))
         dxb = self._buf(("dxb", M), (M, self.H))
-        self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"] if full else None, acc if full else 0, M)
-        cur = self._layers_backward(ctx, self._layer_bwd(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
+        plan = ctx.get("plan")
+        if plan is not None:
+            # a row-compact policy pass (full fine-tune only): the dense d hidden is folded onto the kept rows - a shared row may carry
+            # a label of both sequences (an identical pair) - the final norm and the layers run at Mc rows, and d x0 is expanded with
+            # zeros on the dropped rows for the unchanged embedding backward
+            Mc = plan["Mc"]
+            dh_c = self._buf(("dedup_dhidden", M), (M, self.H))
+            _hip.call("vlr_fold_rows", dhidden, plan["compact_rows"], plan["twin"], dh_c, Mc, self.H)
+            self._norm_bwd(dh_c, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"], acc, Mc)
+            cur = self._layers_backward(ctx, self._layer_bwd_compact(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
+            nxt = dxb if cur is dxa else dxa
+            _hip.call("vlr_expand_rows_zero", cur, plan["dense_own"], nxt, M, self.H)
+            cur = nxt
+        else:
+            self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"] if full else None, acc if full else 0, M)
+            cur = self._layers_backward(ctx, self._layer_bwd(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
         if full:
             self._embed_backward(ctx, cur, acc)
         self.grad_fresh = False
@@ -1531,16 +1653,37 @@ class LlavaHipEngine:
         parameter gradients.  Under gradient checkpointing each layer's forward is re-run first, as the pass itself ran it (same adapters,
         same dropout seeds).  -> the gradient of the decoder's input"""
         ws, Bn, S = ctx["ws"], ctx["Bn"], ctx["S"]
+        plan = ctx.get("plan")           # a row-compact policy pass: the layer inputs are its kept rows, the recompute is the compact forward
+        if plan is not None and ctx["ckpt"]:
+            qkv_d, attn_d = (self._buf((ctx["tag"], k, Bn, S), (ctx["M"], n)) for k, n in (("dedup_qkv", self.Nqkv), ("dedup_attn", self.Nq)))
         for l in range(self.L - 1, -1, -1):
             a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else ctx["x0"]
-            if ctx["ckpt"]:
+            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else (ctx["x0"] if plan is None else ctx["x0_c"])
+            if ctx["ckpt"] and plan is not None:
+                self._layer_fwd_compact_call(ws, l, a, x_in, ctx["embed"], plan, qkv_d, attn_d, Bn, S, True)
+            elif ctx["ckpt"]:
                 self._layer_fwd_call(ws, l, a, x_in, ctx["embed"], Bn, S, True, ctx["use_lora"], ctx["lora_seed"])
             layer_bwd(l, a, x_in, cur, nxt)
             cur, nxt = nxt, cur
             if self.lora is None and self.reducer is not None:       # (LoRA: one bucket when the backward is done)
                 self.reducer.bucket_ready(f"layer{l}")
         return cur
+
+    def _layer_bwd_compact(self, ctx, acc, wsb, lws):
+        """the per-layer backward of a row-compact policy pass (ctx["plan"]), for _layers_backward: vlr_decoder_layer_bwd_compact over the
+        backward's own scratch (its first Mc rows) and four dense operands of the attention backward"""
+        ws, Bn, S, M, plan = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"], ctx["plan"]
+        tag = ctx["tag"]
+        dense = dict(qkv=self._buf((tag, "dedup_qkv", Bn, S), (M, self.Nqkv)), attn=self._buf((tag, "dedup_attn", Bn, S), (M, self.Nq)),
+                     dattn=self._buf((tag, "dedup_dattn", Bn, S), (M, self.Nq)), dqkv=self._buf((tag, "dedup_dqkv", Bn, S), (M, self.Nqkv)))
+        ds = _hip.DenseScratch(*(dense[n].data_ptr() for n, _ in _hip.DenseScratch._fields_))
+
+        def compact(l, a, x_in, cur, nxt):
+            _hip.call("vlr_decoder_layer_bwd_compact", self.llama_cfg, self.layer_weights(ws, l, tag), self.layer_grads(l), acc, a["struct"],
+                      lws, plan["struct"], ds, x_in, cur, nxt, ctx["mask"], Bn, S)
+            if f"l{l}.bqkv" in self.gv:          # (the folded d qkv of the kept rows: a shared row's entry is already the sum of its two copies)
+                _hip.call("vlr_colsum", wsb["dqkv"], plan["Mc"], self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
+        return compact
 
     def _layer_bwd(self, ctx, acc, wsb, lws):
         """the per-layer backward of this engine's current mode, for _layers_backward"""

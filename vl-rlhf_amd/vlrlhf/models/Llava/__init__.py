@@ -57,7 +57,8 @@ class _HiddenFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, input_ids, attention_mask, labels, pixel_values, dup, image_sizes=None):
         c = model.engine.forward_hidden(model.weights, input_ids, attention_mask, labels, pixel_values, image_dup=dup,
-                                        save=True, tag="policy", image_sizes=image_sizes)
+                                        save=True, tag="policy", image_sizes=image_sizes,
+                                        prefix_dedup_rows=bool(getattr(model, "_policy_pass", False)))
         ctx.c, ctx.engine = c, model.engine
         model._last_ctx = c
         return c["hidden"]
@@ -420,6 +421,18 @@ class LlavaForRL(nn.Module):
             yield
         finally:
             self._reference_pass = prev
+
+    @contextlib.contextmanager
+    def policy_pass(self):
+        """the DPO trainer's policy forward runs inside: a training pass over a [chosen ; rejected] batch may then compute each pair's
+        shared prompt rows once, forward and backward (engine.forward_hidden(save=True, prefix_dedup_rows=True)).  A no-grad policy
+        forward inside it stays dense: only reference_pass() speaks for those."""
+        prev = getattr(self, "_policy_pass", False)
+        self._policy_pass = True
+        try:
+            yield
+        finally:
+            self._policy_pass = prev
 
     def lora_state_dict(self):
         self.engine.wait_optimizer()

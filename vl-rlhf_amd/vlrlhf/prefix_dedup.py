@@ -8,7 +8,12 @@ row by row, so in every layer the rejected sequence's first P_i rows repeat the 
     compact_rows [M']   the kept dense rows (b * S + s), ascending: every chosen row, then the rows s >= P_i of every rejected sequence
     dense_src    [M]    for every dense row the compact row that holds its value (a dropped row names its chosen twin)
 
-Pure tensor code: runs on CPU tensors (tests/test_prefix_dedup_host.py) and on the device tensors of the engine alike."""
+The policy's training pass (forward_hidden(save=True, prefix_dedup_rows=True)) keeps one copy too and needs two more maps for its
+backward (build_policy_plan): dense_own, through which a gradient on kept rows is expanded with zeros on the dropped ones, and twin,
+through which a dense gradient is folded - a shared row receives the sum of its two copies.
+
+Pure tensor code: runs on CPU tensors (tests/test_prefix_dedup_host.py, tests/test_prefix_dedup_policy_host.py) and on the device
+tensors of the engine alike."""
 from typing import Sequence, Tuple
 
 import torch
@@ -51,3 +56,34 @@ def build_row_maps(P: Sequence[int], S: int) -> Tuple[torch.Tensor, torch.Tensor
     twin[B:] = torch.where(keep[B:], twin[B:], twin[:B])       # a dropped rejected row reads its chosen twin
     dense_src = index[twin.reshape(-1)]
     return compact_rows.int(), dense_src.int()
+
+
+def build_policy_plan(P: Sequence[int], S: int) -> dict:
+    """Row maps of the row-compact POLICY pass (forward and backward) of B = len(P) pairs of S merged positions; CPU tensors.
+    The last pair's prefix is lowered by up to 7 rows (never below 0; what it lacks is taken from the pair before it) so that
+    Mc % 8 == 0: the kept rows are then merely computed twice, which is always valid, and the joint weight-gradient launch, which
+    contracts over the Mc rows, keeps its 16-byte K alignment.  (With fewer shared rows than the trim in the whole batch Mc = M stays
+    as it is; the caller - who checks plan["Mc"] % 8 and plan["shared"] - runs dense then.)
+        P, shared, M, Mc, tail     the trimmed prefixes, their sum, the dense and compact row counts, S - P[-1]
+        compact_rows [Mc], dense_src [M]    build_row_maps of the trimmed prefixes
+        dense_own [M]   the compact row of a kept dense row, -1 for a dropped row (vlr_expand_rows_zero)
+        twin [Mc]       the dense index of the dropped twin of a shared compact row, -1 otherwise (vlr_fold_rows)"""
+    P = [int(p) for p in P]
+    B = len(P)
+    if B < 1 or S < 1 or any(p < 0 or p > S for p in P):
+        raise ValueError(f"build_policy_plan: prefix lengths {P} outside 0 .. S = {S}")
+    M = 2 * B * S
+    trim = (-(M - sum(P))) % 8                                 # rows to keep again: (Mc + trim) % 8 == 0
+    for i in range(B - 1, -1, -1):                             # the last pair's; a last prefix shorter than the trim leaves the rest to the pair before it
+        take = min(trim, P[i])
+        P[i] -= take
+        trim -= take
+    compact_rows, dense_src = build_row_maps(P, S)
+    Mc = int(compact_rows.numel())
+    own = torch.full((M,), -1, dtype=torch.int64)
+    own[compact_rows.long()] = torch.arange(Mc)
+    dropped = torch.nonzero(own < 0).reshape(-1)               # dense rows (B + i) * S + s, s < P_i
+    twin = torch.full((Mc,), -1, dtype=torch.int64)
+    twin[dense_src.long()[dropped]] = dropped
+    return dict(P=P, shared=sum(P), M=M, Mc=Mc, tail=S - P[-1], compact_rows=compact_rows, dense_src=dense_src,
+                dense_own=own.int(), twin=twin.int())
