@@ -98,6 +98,29 @@ int vlr_gemm_qkv_rope_bias(const void* x, const void* wqkv, const void* bias, vo
  *                     [M][I] is scratch for the rows / shapes that take the plain GEMM + vlr_swiglu_bwd. */
 int vlr_gemm_swiglu_bwd(const void* dy, const void* wdown, void* gu_inout, void* dact_ws, int M, int I, int H,
                         vlr_stream_t stream);
+/*  vlr_gemm_swiglu_bwd_src: the same OUT OF PLACE through a source-row map (additive: vlr_abi_version() does not move) - gate | up of
+ *                     row m are row src_rows[m] of gu_src [Mc][2I] (the kept rows of a row-compact forward; read only, rows may
+ *                     repeat), [d gate | d up] go to row m of dgu_out [M][2I].  src_rows: M device int32 in [0, Mc), not checked by
+ *                     the kernels.  dgu_out must not overlap gu_src (refused where the library can see it).  Peel, route and
+ *                     arithmetic are vlr_gemm_swiglu_bwd's at M rows - its bits on gate | up expanded through src_rows; rows that
+ *                     fall back take the plain GEMM + vlr_swiglu_bwd_src.  There is no addend form. */
+int vlr_gemm_swiglu_bwd_src(const void* dy, const void* wdown, const void* gu_src, const int* src_rows, void* dgu_out, void* dact_ws,
+                            int M, int I, int H, vlr_stream_t stream);
+/* The forward NT products of a decoder layer with an M-SIDE ROW MAP on the A operand (additive: vlr_abi_version() does not move): logical
+ * row m of x / a is row a_rows[m] of the buffer (M device int32, every entry a valid buffer row, not checked; rows may repeat and need not
+ * ascend).  The map is read once per output tile and on the general staging path (K % 64 != 0, the next tile's first K tiles), never in
+ * the steady-state K loop.  Same launches, kernels and K order as vlr_gemm_qkv_rope_bias / vlr_gemm_swiglu / vlr_gemm_bf16[_f32res] on a
+ * gathered A: the same bits.  Only the persistent 256-tile kernels take a map: a shape they refuse is an ERROR here, not a fallback.
+ * vlr_gemm_res_rows: y [M][N] (fp32 if f32, else bf16) = a W^T + res, NT, lda = ldb = K, ldc = ldr = N.  peel_rows > 0: the LAST
+ * peel_rows logical rows run on the 128x128 split-K kernel, which takes a plain pointer: they must be the contiguous buffer rows
+ * tail_row0 .. tail_row0 + peel_rows - 1 (not checked).  0: none. */
+int vlr_gemm_qkv_rope_bias_rows(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv, const int* pos,
+                                const float* cos_t, const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim,
+                                int max_pos, vlr_stream_t stream);
+int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void* wgu, void* gu, void* act, int M, int I, int K, int ldx, int store_gu,
+                         vlr_stream_t stream);
+int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
+                      int peel_rows, int tail_row0, vlr_stream_t stream);
 /* The same projections with the LoRA adapters of the group riding the K loop of the base GEMM (peft lora.Linear.forward,
  * result = base(x) + lora_B(lora_A(dropout(x))) * scaling; reference targets src/vlrlhf/models/Llava/__init__.py:273-286):
  * after the K tiles of x . W^T the kernel runs on into u . Bl^T, u [M][ldu] = scaling * dropout_t(x) A_t^T of the group's
@@ -209,6 +232,22 @@ int vlr_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* r
 /* the same with the forward input x in fp32; dy / dres / dx (the gradient stream) are bf16 */
 int vlr_rmsnorm_bwd_f32(const void* dy, const float* x, const void* w, const float* rstd, const void* dres, void* dx,
                         void* dw, int dw_accumulate, void* workspace, int M, int H, vlr_stream_t stream);
+/* The two above with x and rstd read through a SOURCE-ROW MAP (additive: vlr_abi_version() does not move): x [Mc][H] and rstd [Mc] hold
+ * the kept rows of a row-compact forward, and dense row m of the backward is row src_rows[m] of them.  src_rows: M device int32, every
+ * entry in [0, Mc) - the kernels do not check it; rows may repeat.  dy, dres, dx are dense [M][H]; dx must not overlap x.  The row walk,
+ * the dw partials and their reduction are the unmapped call's: the result is that call's on x / rstd expanded through src_rows, bit
+ * for bit. */
+int vlr_rmsnorm_bwd_src(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
+                        int dw_accumulate, void* workspace, const int* src_rows, int M, int H, vlr_stream_t stream);
+int vlr_rmsnorm_bwd_f32_src(const void* dy, const float* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
+                            int dw_accumulate, void* workspace, const int* src_rows, int M, int H, vlr_stream_t stream);
+/* RMSNorm forward of the kept rows of a row-compact pass, written DENSELY (additive): x [Mc][H] and rstd [Mc] hold the kept rows; row j of
+ * the result goes to row compact_rows[j] of y and, where twin[j] >= 0 (a shared row), to row twin[j] as well - the maps vlr_fold_rows
+ * reads (vlr_row_maps).  Rows of y that no kept row maps to are not written.  The values are vlr_rmsnorm_fwd's, bit for bit. */
+int vlr_rmsnorm_fwd_scatter(const void* x, const void* w, void* y, float* rstd, const int* compact_rows, const int* twin, int Mc, int H,
+                            float eps, vlr_stream_t stream);
+int vlr_rmsnorm_fwd_f32_scatter(const float* x, const void* w, void* y, float* rstd, const int* compact_rows, const int* twin, int Mc, int H,
+                                float eps, vlr_stream_t stream);
 int vlr_layernorm_fwd(const void* x, const void* w, const void* b, void* y, int M, int D, float eps, vlr_stream_t stream);
 /* backward of y = LayerNorm(x) * w + b (Qwen-VL resampler: ln_q / ln_kv / ln_post, QwenVL/visual.py:122-123,391): mean and rstd are
  * recomputed from x; dx may be NULL, dw / db (bf16 [D], `accumulate`: +=) may be NULL; workspace = vlr_layernorm_bwd_workspace_bytes(D) */
@@ -226,6 +265,9 @@ int vlr_rope_heads(void* qkv, const int* pos, const float* cos_t, const float* s
                    int max_pos, int backward, vlr_stream_t stream);
 int vlr_swiglu_fwd(const void* gate_up, void* act, int M, int I, vlr_stream_t stream);
 int vlr_swiglu_bwd(void* gate_up_inout, const void* dact, int M, int I, vlr_stream_t stream);
+/* out of place through a source-row map: gate | up of row m at row src_rows[m] of gu_src (read only), [d gate | d up] to row m of
+ * dgu_out [M][2I], which must not overlap gu_src */
+int vlr_swiglu_bwd_src(const void* gu_src, const int* src_rows, void* dgu_out, const void* dact, int M, int I, vlr_stream_t stream);
 int vlr_gelu_fwd(const void* z, void* h, long n, vlr_stream_t stream);
 int vlr_gelu_bwd(const void* z, const void* dh, void* dz, long n, vlr_stream_t stream);
 int vlr_colsum_workspace_bytes(int C);
@@ -461,7 +503,8 @@ int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
  * x_in and every tensor of `a` hold Mc rows, except a->lse, which stays [batch][heads][align64(S)].  qkv_dense [batch * S][Nq + 2 Nkv]
  * and attn_dense [batch * S][Nq] are scratch: the q|k|v rows are expanded through dense_src, vlr_attn_fwd_gqa runs on the dense
  * layout with the dense key_mask exactly as in vlr_decoder_layer_fwd_ex, and its rows are compacted again through compact_rows.
- * keep_for_backward = 0 semantics (a->gu is not written).
+ * (Where the persistent kernel takes o_proj with a row map it reads those dense rows through compact_rows instead, and a->attn is not
+ * written.)  keep_for_backward = 0 semantics (a->gu is not written).
  * tail_rows: how many of the LAST dense rows are kept (the compact rows Mc - tail_rows .. Mc - 1 are the dense rows
  * batch * S - tail_rows .. batch * S - 1).  The residual projections of the dense pass run their last vlr_gemm_peel_rows(batch * S, hidden)
  * rows on the 128x128 split-K kernel, whose fp32 sums are formed in another order than the persistent kernel's; when these rows lie
@@ -521,6 +564,31 @@ int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weig
                                   const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const vlr_row_maps* m,
                                   const vlr_dense_scratch* d, const void* x_in, const void* dx_out, void* dx_in, const int* key_mask,
                                   int batch, int S, vlr_stream_t stream);
+/* ---- the dense backward on the kept rows IN PLACE (additive: vlr_abi_version() does not move).  vlr_layer_acts_expand buys the dense
+ * layout back with eight row copies per layer; five of them feed consumers that walk rows one at a time and can read row m at
+ * src[dense_src[m]] instead.
+ * vlr_decoder_layer_fwd_compact_keep: vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1) writing
+ *   - rstd1, x_mid, rstd2, gu, x_out on Mc rows into the layer's own set `a` (never copied),
+ *   - xn1, xn2 straight to the M dense rows of `a` (vlr_rmsnorm_fwd_scatter; the fused projections read them through compact_rows) where
+ *     the fused kernels take every row of the layer's shapes - elsewhere on Mc rows into `s` and copied through m->dense_src,
+ *   - act on Mc rows into `s`, then copied to the M dense rows of `a` (with xn1, xn2 the K-side operands of the weight-gradient GEMMs),
+ *   - q|k|v and attn densely into a->qkv / a->attn (s->qkv and s->attn take the Mc-row forms), lse into a->lse.
+ * o_proj reads the dense attention rows through compact_rows where the persistent kernel takes it.  Of `s` only xn1, qkv, attn, xn2, act
+ * are used; none of them may be the same buffer as its namesake in `a`.  m->dense_own is not read.
+ * vlr_decoder_layer_bwd_src: vlr_decoder_layer_bwd call for call, in the same order, at M = batch * S rows, on such a set.  x_in holds
+ * the KEPT rows of the layer's input (the previous layer's a->x_out, or the embedding rows gathered through compact_rows); both norm
+ * backwards are the _src forms over src_rows = dense_src; the SwiGLU backward is vlr_gemm_swiglu_bwd_src into dgu [M][2I], a scratch
+ * all layers may share, which must not overlap a->gu.  a->gu stays the forward's gate | up.  dx_out, dx_in, `ws` and pos are dense, as
+ * for vlr_decoder_layer_bwd, and ws->dqkv holds d qkv [M] afterwards.  Every weight gradient and dx_in equal, bit for bit, those of
+ * vlr_decoder_layer_fwd_compact_ex + vlr_layer_acts_expand + vlr_decoder_layer_bwd.
+ * Preconditions: no null pointer but key_mask, in the structs too; every src_rows / dense_src entry in [0, Mc); nothing is allocated. */
+int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                       const vlr_layer_acts* s, const void* x_in, const vlr_row_maps* m, const int* key_mask, int batch,
+                                       int S, vlr_stream_t stream);
+int vlr_decoder_layer_bwd_src(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                              const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, void* dgu, const int* src_rows, const void* x_in,
+                              const void* dx_out, void* dx_in, const int* pos, const int* key_mask, int batch, int S,
+                              vlr_stream_t stream);
 /* 1: every kept row of the row-compact forward over Mc of batch * S rows is computed by the kernel, and in the K order, the dense
  * forward computes it in - the two passes agree bit for bit on the kept rows (16-byte aligned operands assumed).  Host arithmetic
  * only: all four projections take the persistent 256-tile kernel at batch * S and at Mc rows, and the rows the dense residual

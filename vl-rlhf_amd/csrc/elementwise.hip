@@ -15,13 +15,17 @@ __device__ __forceinline__ void load8(const float* p, float* v) {
 }
 // REG (H <= 8192): the row stays in registers between the sum of squares and the scaling - x is read ONCE (the two-pass form reads it a
 // second time out of the L2: the same values, the same order of additions, a longer dependent chain per workgroup)
-template <typename XT, bool REG>
-__global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__ x, const bf16_t* __restrict__ w,
-                                                          bf16_t* __restrict__ y, float* __restrict__ rstd_out, int H,
-                                                          float eps) {
+// SCAT (vlr_rmsnorm_fwd_scatter): x and rstd hold the kept rows of a row-compact pass; row j of y is written to dense row
+// compact_rows[j] and, where twin[j] >= 0 (a shared row), also to its dropped copy twin[j] - the same values from the same arithmetic
+template <typename XT, bool REG, bool SCAT>
+__device__ __forceinline__ void rmsnorm_fwd_body(const XT* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y,
+                                                 float* __restrict__ rstd_out, int H, float eps, const int* __restrict__ compact_rows,
+                                                 const int* __restrict__ twin) {
     __shared__ float red[16];
     const size_t row = blockIdx.x;
     const XT* xr = x + row * H;
+    const size_t yrow = SCAT ? (size_t)compact_rows[row] : row;
+    const long trow = SCAT ? (long)twin[row] : -1;
     float ss = 0.f;
     if constexpr (REG) {
         constexpr int MAXC = 4;
@@ -46,7 +50,9 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__
                 unpack8(*reinterpret_cast<const u32x4*>(w + c), g);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = g[e] * (v[i][e] * rstd);
-                *reinterpret_cast<u32x4*>(y + row * H + c) = pack8(o);
+                const u32x4 q = pack8(o);
+                *reinterpret_cast<u32x4*>(y + yrow * H + c) = q;
+                if (SCAT && trow >= 0) *reinterpret_cast<u32x4*>(y + (size_t)trow * H + c) = q;
             }
         }
         return;
@@ -66,8 +72,22 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__
         unpack8(*reinterpret_cast<const u32x4*>(w + c), g);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = g[e] * (v[e] * rstd);
-        *reinterpret_cast<u32x4*>(y + row * H + c) = pack8(v);
+        const u32x4 q = pack8(v);
+        *reinterpret_cast<u32x4*>(y + yrow * H + c) = q;
+        if (SCAT && trow >= 0) *reinterpret_cast<u32x4*>(y + (size_t)trow * H + c) = q;
     }
+}
+template <typename XT, bool REG>
+__global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__ x, const bf16_t* __restrict__ w,
+                                                          bf16_t* __restrict__ y, float* __restrict__ rstd_out, int H,
+                                                          float eps) {
+    rmsnorm_fwd_body<XT, REG, false>(x, w, y, rstd_out, H, eps, nullptr, nullptr);
+}
+template <typename XT, bool REG>
+__global__ __launch_bounds__(256) void rmsnorm_fwd_scatter_kernel(const XT* __restrict__ x, const bf16_t* __restrict__ w,
+                                                                  bf16_t* __restrict__ y, float* __restrict__ rstd_out, int H, float eps,
+                                                                  const int* __restrict__ compact_rows, const int* __restrict__ twin) {
+    rmsnorm_fwd_body<XT, REG, true>(x, w, y, rstd_out, H, eps, compact_rows, twin);
 }
 
 // RMSNorm backward.  dx = rstd * (dy*w - xhat * mean(dy*w*xhat)) (+ dres), dw partial[j] += dy*xhat.
@@ -76,11 +96,14 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const XT* __restrict__
 // latency per row less).
 // MAXC: 8-column chunks per thread the register arrays are sized for (H <= 2048 MAXC): with 4 for every H the 7B width (2 used) cost 150
 // registers = 3 waves per SIMD; MAXC = 2 leaves room for more rows in flight per CU (the same instructions on the same values)
-template <typename XT, int MAXC>
-__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const XT* __restrict__ x,
-                                                          const bf16_t* __restrict__ w, const float* __restrict__ rstd,
-                                                          const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
-                                                          float* __restrict__ dw_part, int M, int H, int row0, int part0) {
+// SRC (vlr_rmsnorm_bwd_src): x and rstd hold the kept rows of a row-compact forward and dense row `row` reads them at src_rows[row] -
+// the same values in the same order as on the expanded copies; dy, dres and dx stay dense
+template <typename XT, int MAXC, bool SRC>
+__device__ __forceinline__ void rmsnorm_bwd_body(const bf16_t* __restrict__ dy, const XT* __restrict__ x,
+                                                 const bf16_t* __restrict__ w, const float* __restrict__ rstd,
+                                                 const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                 float* __restrict__ dw_part, int M, int H, int row0, int part0,
+                                                 const int* __restrict__ src_rows) {
     // rows [row0, M); the workgroup's dw partial goes to row part0 + blockIdx.x of dw_part (the one launch there is passes row0 = part0 = 0)
     __shared__ float red[16];
     float dwacc[MAXC][8];      // H <= 256*8*MAXC
@@ -90,7 +113,9 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
         for (int e = 0; e < 8; ++e) dwacc[i][e] = 0.f;
     for (int row = row0 + blockIdx.x; row < M; row += gridDim.x) {
         const size_t off = (size_t)row * H;
-        const float rs = rstd[row];
+        const size_t xrow = SRC ? (size_t)src_rows[row] : (size_t)row;
+        const size_t xoff = xrow * H;
+        const float rs = rstd[xrow];
         float dot = 0.f;
         float gx[MAXC][8], xh[MAXC][8];
         u32x4 rraw[MAXC];
@@ -101,7 +126,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
                 float a[8], b[8], g[8];
                 if (dres) rraw[i] = *reinterpret_cast<const u32x4*>(dres + off + c);
                 unpack8(*reinterpret_cast<const u32x4*>(dy + off + c), a);
-                load8(x + off + c, b);
+                load8(x + xoff + c, b);
                 unpack8(*reinterpret_cast<const u32x4*>(w + c), g);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -139,6 +164,21 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
             *reinterpret_cast<f32x4*>(d + 4) = f32x4{dwacc[i][4], dwacc[i][5], dwacc[i][6], dwacc[i][7]};
         }
     }
+}
+template <typename XT, int MAXC>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const XT* __restrict__ x,
+                                                          const bf16_t* __restrict__ w, const float* __restrict__ rstd,
+                                                          const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                          float* __restrict__ dw_part, int M, int H, int row0, int part0) {
+    rmsnorm_bwd_body<XT, MAXC, false>(dy, x, w, rstd, dres, dx, dw_part, M, H, row0, part0, nullptr);
+}
+template <typename XT, int MAXC>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_src_kernel(const bf16_t* __restrict__ dy, const XT* __restrict__ x,
+                                                              const bf16_t* __restrict__ w, const float* __restrict__ rstd,
+                                                              const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                              float* __restrict__ dw_part, int M, int H,
+                                                              const int* __restrict__ src_rows) {
+    rmsnorm_bwd_body<XT, MAXC, true>(dy, x, w, rstd, dres, dx, dw_part, M, H, 0, 0, src_rows);
 }
 
 // out[c] (bf16, optional +=) = sum_p part[p][c]
@@ -461,6 +501,28 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(bf16_t* __restrict__ gu
         }
         *reinterpret_cast<u32x4*>(gu + row * 2 * I + c) = pack8(dg);
         *reinterpret_cast<u32x4*>(gu + row * 2 * I + I + c) = pack8(du);
+    }
+}
+// the same out of place, gate | up read at the source row of the dense row (vlr_swiglu_bwd_src)
+__global__ __launch_bounds__(256) void swiglu_bwd_src_kernel(const bf16_t* __restrict__ gu, const int* __restrict__ src_rows,
+                                                             bf16_t* __restrict__ dgu, const bf16_t* __restrict__ dact, long M, int I) {
+    const long chunks = (long)M * (I / 8);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long)gridDim.x * 256) {
+        const long row = i / (I / 8);
+        const int c = (int)(i % (I / 8)) * 8;
+        const long srow = src_rows[row];
+        float g[8], u[8], d[8], dg[8], du[8];
+        unpack8(*reinterpret_cast<const u32x4*>(gu + srow * 2 * I + c), g);
+        unpack8(*reinterpret_cast<const u32x4*>(gu + srow * 2 * I + I + c), u);
+        unpack8(*reinterpret_cast<const u32x4*>(dact + row * I + c), d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float sg = fast_sigmoid(g[e]);
+            du[e] = d[e] * g[e] * sg;
+            dg[e] = d[e] * u[e] * sg * (1.f + g[e] * (1.f - sg));
+        }
+        *reinterpret_cast<u32x4*>(dgu + row * 2 * I + c) = pack8(dg);
+        *reinterpret_cast<u32x4*>(dgu + row * 2 * I + I + c) = pack8(du);
     }
 }
 
@@ -792,6 +854,28 @@ extern "C" int vlr_rmsnorm_fwd_f32(const float* x, const void* w, void* y, float
     return vlr_check_launch("vlr_rmsnorm_fwd_f32");
 }
 
+// x [Mc][H] and rstd [Mc] on the kept rows of a row-compact pass, y DENSE: row j is written to row compact_rows[j] of y and, where
+// twin[j] >= 0, to row twin[j] too (the maps vlr_fold_rows reads).  Rows of y no kept row maps to are not written
+template <typename XT>
+static int rmsnorm_fwd_scatter_impl(const char* fn, const XT* x, const void* w, void* y, float* rstd, const int* compact_rows, const int* twin,
+                                    int Mc, int H, float eps, hipStream_t st) {
+    VLR_REQUIRE(x && w && y && compact_rows && twin, "%s: null argument", fn);
+    VLR_REQUIRE(Mc > 0 && H > 0 && H % 8 == 0, "%s: bad shape M=%d H=%d", fn, Mc, H);
+    if (H <= 8192)
+        hipLaunchKernelGGL((rmsnorm_fwd_scatter_kernel<XT, true>), dim3(Mc), dim3(256), 0, st, x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps, compact_rows, twin);
+    else
+        hipLaunchKernelGGL((rmsnorm_fwd_scatter_kernel<XT, false>), dim3(Mc), dim3(256), 0, st, x, (const bf16_t*)w, (bf16_t*)y, rstd, H, eps, compact_rows, twin);
+    return vlr_check_launch(fn);
+}
+extern "C" int vlr_rmsnorm_fwd_scatter(const void* x, const void* w, void* y, float* rstd, const int* compact_rows, const int* twin, int Mc,
+                                       int H, float eps, hipStream_t st) {
+    return rmsnorm_fwd_scatter_impl("vlr_rmsnorm_fwd_scatter", (const bf16_t*)x, w, y, rstd, compact_rows, twin, Mc, H, eps, st);
+}
+extern "C" int vlr_rmsnorm_fwd_f32_scatter(const float* x, const void* w, void* y, float* rstd, const int* compact_rows, const int* twin,
+                                           int Mc, int H, float eps, hipStream_t st) {
+    return rmsnorm_fwd_scatter_impl("vlr_rmsnorm_fwd_f32_scatter", x, w, y, rstd, compact_rows, twin, Mc, H, eps, st);
+}
+
 // 1024 workgroups (4 per CU) keep enough loads in flight for an HBM-bound pass; their dw partials are reduced in two
 // deterministic stages (1024 -> 16 -> 1)
 #define VLR_NORM_BWD_BLOCKS 1024
@@ -799,7 +883,8 @@ extern "C" int vlr_rmsnorm_fwd_f32(const float* x, const void* w, void* y, float
 extern "C" int vlr_rmsnorm_bwd_workspace_bytes(int H) { return (VLR_NORM_BWD_BLOCKS + VLR_NORM_BWD_STAGE2) * H * 4; }
 
 static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void* w, const float* rstd, const void* dres,
-                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st);
+                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st,
+                            const int* src_rows = nullptr);
 extern "C" int vlr_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres,
                                void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
     return rmsnorm_bwd_impl(dy, x, 0, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st);
@@ -809,8 +894,21 @@ extern "C" int vlr_rmsnorm_bwd_f32(const void* dy, const float* x, const void* w
                                    void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
     return rmsnorm_bwd_impl(dy, x, 1, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st);
 }
+// the two above with x and rstd read through a source-row map: x [Mc][H] and rstd [Mc] hold the kept rows of a row-compact forward, dense
+// row m of the backward is row src_rows[m] of them (src_rows [M], every entry a valid row of x); dy, dres and dx are dense [M][H] and
+// must not overlap x.  Same row walk, same dw partials and reduction: the bits of the unmapped call on the expanded x / rstd
+extern "C" int vlr_rmsnorm_bwd_src(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
+                                   int dw_accumulate, void* workspace, const int* src_rows, int M, int H, hipStream_t st) {
+    VLR_REQUIRE(src_rows, "vlr_rmsnorm_bwd_src: null row map");
+    return rmsnorm_bwd_impl(dy, x, 0, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st, src_rows);
+}
+extern "C" int vlr_rmsnorm_bwd_f32_src(const void* dy, const float* x, const void* w, const float* rstd, const void* dres, void* dx,
+                                       void* dw, int dw_accumulate, void* workspace, const int* src_rows, int M, int H, hipStream_t st) {
+    VLR_REQUIRE(src_rows, "vlr_rmsnorm_bwd_f32_src: null row map");
+    return rmsnorm_bwd_impl(dy, x, 1, w, rstd, dres, dx, dw, dw_accumulate, workspace, M, H, st, src_rows);
+}
 static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void* w, const float* rstd, const void* dres,
-                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st) {
+                            void* dx, void* dw, int dw_accumulate, void* workspace, int M, int H, hipStream_t st, const int* src_rows) {
     VLR_REQUIRE(dy && x && w && rstd && dx, "vlr_rmsnorm_bwd: null argument");
     VLR_REQUIRE(M > 0 && H % 8 == 0 && H <= 8192, "vlr_rmsnorm_bwd: bad shape M=%d H=%d (H<=8192)", M, H);
     VLR_REQUIRE(workspace, "vlr_rmsnorm_bwd: workspace of vlr_rmsnorm_bwd_workspace_bytes(H) required");
@@ -822,9 +920,19 @@ static int rmsnorm_bwd_impl(const void* dy, const void* x, int x_f32, const void
         else hipLaunchKernelGGL((rmsnorm_bwd_kernel<XT_, 4>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,              \
                                 (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, M, H, 0, 0);              \
     } while (0)
-    if (x_f32) NORM_BWD_LAUNCH(float);
+#define NORM_BWD_SRC_LAUNCH(XT_)                                                                                                       \
+    do {                                                                                                                               \
+        if (H <= 4096) hipLaunchKernelGGL((rmsnorm_bwd_src_kernel<XT_, 2>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x, \
+                                          (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, M, H, src_rows); \
+        else hipLaunchKernelGGL((rmsnorm_bwd_src_kernel<XT_, 4>), dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const XT_*)x,          \
+                                (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)workspace, M, H, src_rows);          \
+    } while (0)
+    if (src_rows && x_f32) NORM_BWD_SRC_LAUNCH(float);
+    else if (src_rows) NORM_BWD_SRC_LAUNCH(bf16_t);
+    else if (x_f32) NORM_BWD_LAUNCH(float);
     else NORM_BWD_LAUNCH(bf16_t);
 #undef NORM_BWD_LAUNCH
+#undef NORM_BWD_SRC_LAUNCH
     if (dw) {
         float* part2 = (float*)workspace + (size_t)VLR_NORM_BWD_BLOCKS * H;
         const int S2 = G < VLR_NORM_BWD_STAGE2 ? 1 : VLR_NORM_BWD_STAGE2;
@@ -921,6 +1029,15 @@ extern "C" int vlr_swiglu_fwd(const void* gu, void* act, int M, int I, hipStream
     hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid_for((long)M * I / 8, 256)), dim3(256), 0, st, (const bf16_t*)gu,
                        (bf16_t*)act, (long)M, I);
     return vlr_check_launch("vlr_swiglu_fwd");
+}
+// out of place through a source-row map (the rows vlr_gemm_swiglu_bwd_src leaves to the unfused route): gate | up of dense row m at row
+// src_rows[m] of gu_src, [d gate | d up] to row m of dgu_out
+extern "C" int vlr_swiglu_bwd_src(const void* gu_src, const int* src_rows, void* dgu_out, const void* dact, int M, int I, hipStream_t st) {
+    VLR_REQUIRE(gu_src && src_rows && dgu_out && dact, "vlr_swiglu_bwd_src: null argument");
+    VLR_REQUIRE(M > 0 && I > 0 && I % 8 == 0, "vlr_swiglu_bwd_src: bad shape");
+    hipLaunchKernelGGL(swiglu_bwd_src_kernel, dim3(grid_for((long)M * I / 8, 256)), dim3(256), 0, st, (const bf16_t*)gu_src, src_rows,
+                       (bf16_t*)dgu_out, (const bf16_t*)dact, (long)M, I);
+    return vlr_check_launch("vlr_swiglu_bwd_src");
 }
 extern "C" int vlr_swiglu_bwd(void* gu_inout, const void* dact, int M, int I, hipStream_t st) {
     VLR_REQUIRE(M > 0 && I % 8 == 0, "vlr_swiglu_bwd: bad shape");

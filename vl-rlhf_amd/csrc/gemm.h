@@ -28,6 +28,8 @@ struct GemmParams {
     //             tile's two heads, so a lane owns both members of every rotate-half pair; columns < rope_cols are rotated by
     //             pos[row] in fp32 before the single rounding to bf16, the rest (v) pass through.
     //  3 SwiGLU backward (NN): acc = d act; C2 = gate | up [M][2I] is replaced in place by d gate | d up; C is not written.
+    //  7 SwiGLU backward (NN) out of place through a source-row map: gate | up of output row m are row pos[m] of C2 [.][ldc2] (read
+    //             only), d gate | d up go to row m of C [M][ldc], ldc == ldc2 == 2I; no addend (vlr_gemm_swiglu_bwd_src).
     int fuse;
     int store_c;
     void* C2;
@@ -102,6 +104,10 @@ struct GemmParams {
     // contract over, ascending - the tiles that hold an image row (vlr_rows_tile_list); every other row of both operands' product is zero
     // by construction (PLoRA's u / v on the text rows).  The count is read on the device: split-K slices cut the LIST into equal runs.
     const int* ktlist;
+    // ---- M-side row map of a K-contiguous A operand (NT / NN launches of gemm256p.hip without an adapter segment): logical row m of A is
+    // row a_rows[m] of the buffer at A (M device ints, not checked; rows may repeat).  Read once per piece at tile setup and on the general
+    // staging path (K tail, the next piece's first K tiles) - never in the steady-state K loop.  NULL: A is read in place.
+    const int* a_rows;
 #ifdef VLR_GEMM_TRACE
     uint32_t* trace;         // diagnostics build only: set by the launchers of gemm256p.hip (vlr_gemm_set_trace), never by callers
     int epi_abl, trace_clk;
@@ -136,7 +142,8 @@ bool vlr_gemm256p_seg_try_launch(const GemmParams& p, hipStream_t stream);
 bool vlr_gemm256p_fused_try_launch(const GemmParams& p, hipStream_t stream);
 // two TN problems of equal K (the weight gradients of two linears of one layer) as ONE persistent launch; false: shapes it does not take
 bool vlr_gemm256p_tn_pair_try_launch(const GemmParams& p0, const GemmParams& p1, hipStream_t stream);
-// fuse = 3 (NN): d act = dy . Wdown with the SwiGLU backward applied in the epilogue to gate | up in p.C2 (in place)
+// fuse = 3 (NN): d act = dy . Wdown with the SwiGLU backward applied in the epilogue to gate | up in p.C2 (in place); fuse = 7: the
+// same reading gate | up at row p.pos[m] of p.C2 and writing d gate | d up to p.C (false also where that launch lacks an operand)
 bool vlr_gemm256p_swiglu_bwd_try_launch(const GemmParams& p, hipStream_t stream);
 // fuse = 4 | 5: the lm-head GEMM with the log-softmax statistics / the logits gradient in its epilogue
 bool vlr_gemm256p_lmhead_try_launch(const GemmParams& p, hipStream_t stream);

@@ -693,6 +693,16 @@ extern "C" int vlr_gemm_peel_rows(int M, int N) {
 // choose_peel picks for their own M - the row-compact layer pass (layers.cpp) keeps every row in the kernel the dense pass computes
 // it in, so that both passes round alike
 static thread_local int t_peel_rows = -1;
+// != NULL: the K-contiguous A operand of the next NT launches of this thread is read through this M-side row map (GemmParams::a_rows:
+// logical row m = buffer row t_a_rows[m]) - the plain residual projection below and the fused q|k|v + RoPE / gate|up + SwiGLU launches.
+// Only the persistent 256x256 kernel takes a map: a launch it refuses is an error, not a fallback.  t_a_tail0: the buffer row at which the
+// caller-named peeled rows (t_peel_rows) stand as ONE contiguous run - the 128x128 kernel gets a plain pointer
+static thread_local const int* t_a_rows = nullptr;
+static thread_local int t_a_tail0 = -1;
+struct ARowsScope {
+    ARowsScope(const int* r, int tail0, int peel) { t_a_rows = r; t_a_tail0 = tail0; t_peel_rows = peel; }
+    ~ARowsScope() { t_a_rows = nullptr; t_a_tail0 = -1; t_peel_rows = -1; }
+};
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st) {
     t_peel_rows = peel_rows;
@@ -820,8 +830,27 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     p.sched = 0;
     p.A1 = p.B1 = nullptr; p.C1 = nullptr; p.M1 = p.N1 = p.lda1 = p.ldb1 = p.ldc1 = 0;
     p.groups = 1; p.gA = p.gB = p.gC = 0; p.mask_on = 0; p.mask_seed = 0; p.mask_thr = 0; p.mask_ld = 0;
-    p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0;
+    p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0; p.a_rows = nullptr;
     const int pi = vlr_prof_begin(layout, 2.0 * M * N * K, stream);
+    if (t_a_rows) {       // A through a row map (vlr_gemm_res_rows): the persistent kernel for all rows but the caller-named peeled ones
+        const int pr = t_peel_rows > 0 ? t_peel_rows : 0;
+        GemmParams p1 = p;
+        p1.M = M - pr; p1.a_rows = t_a_rows;
+        const bool ok = layout == 0 && pr < M && (pr == 0 || t_a_tail0 >= 0) && vlr_gemm256p_try_launch(layout, p1, stream);
+        if (ok && pr) {
+            GemmParams p2 = p;
+            const size_t esz = out_f32 ? 4 : 2;
+            p2.M = pr;
+            p2.A = p.A + (size_t)t_a_tail0 * lda;
+            p2.C = (char*)p.C + (size_t)p1.M * ldc * esz;
+            if (p.residual) p2.residual = (const bf16_t*)((const char*)p.residual + (size_t)p1.M * ldr * (p.res_f32 ? 4 : 2));
+            const int t2 = ((p2.M + BM - 1) / BM) * ((N + BN - 1) / BN);
+            if (!launch_splitk128(layout, p2, stream, 4096)) launch128(layout, p2, dim3(t2), stream);
+        }
+        vlr_prof_end(ok ? pi : -1, stream);
+        VLR_REQUIRE(ok, "vlr_gemm_res_rows: the persistent kernel does not take M=%d N=%d K=%d with a row map (%d peeled rows)", M, N, K, pr);
+        return vlr_check_launch("vlr_gemm_res_rows");
+    }
     // ---- split-K for problems whose output is a handful of tiles but whose reduction is long: the LoRA adapter gradients
     // (TN: dB = dy^T u [out x r], dA = v^T x [r x in], reduction over all tokens) - 32..96 workgroups would leave most CUs idle
     if (layout == 2 && launch_splitk128(layout, p, stream, 2048)) {
@@ -900,7 +929,7 @@ static GemmParams fused_params(const void* A, const void* B, void* C, int M, int
     p.sched = 0;
     p.A1 = p.B1 = nullptr; p.C1 = nullptr; p.M1 = p.N1 = p.lda1 = p.ldb1 = p.ldc1 = 0;
     p.groups = 1; p.gA = p.gB = p.gC = 0; p.mask_on = 0; p.mask_seed = 0; p.mask_thr = 0; p.mask_ld = 0;
-    p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0;
+    p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0; p.a_rows = nullptr;
     return p;
 }
 
@@ -962,6 +991,8 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
     const int M1 = peel ? (tm256 - peel) * 256 : M;
     GemmParams p = fused_params(x, wgu, gu, M1, 2 * I, K, ldx, K, 2 * I);
     p.fuse = 1; p.store_c = store_gu; p.C2 = act; p.ldc2 = I;
+    VLR_REQUIRE(!t_a_rows || !seg, "vlr_gemm_swiglu: no row map on a launch with an adapter segment");
+    p.a_rows = t_a_rows;
     seg_set(p, sg, &skp, 0);
     int done = 0;
     const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * M1 * 2 * I * K, stream);    // per-layout totals of the bench line (the fallback rows below are counted by gemm_impl)
@@ -977,6 +1008,7 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
         // arithmetic - act from the fp32 accumulators - whatever the batch size
         GemmParams p2 = fused_params((const bf16_t*)x + (size_t)done * ldx, wgu, (bf16_t*)gu + (size_t)done * 2 * I, M - done, 2 * I, K, ldx, K, 2 * I);
         p2.fuse = 1; p2.store_c = store_gu; p2.C2 = (bf16_t*)act + (size_t)done * I; p2.ldc2 = I;
+        if (t_a_rows) { p2.A = (const bf16_t*)x; p2.a_rows = t_a_rows + done; }
         if (seg) { SegArgs s2 = *sg; s2.u = (const bf16_t*)sg->u + (size_t)done * sg->ldu; seg_set(p2, &s2, &skp, done); }
         const int pj_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * (M - done) * 2 * I * K, stream);
         const bool took2_ = seg ? vlr_gemm256p_seg_try_launch(p2, stream) : vlr_gemm256p_fused_try_launch(p2, stream);
@@ -987,6 +1019,7 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
             done = M;
         }
     }
+    VLR_REQUIRE(done == M || !t_a_rows, "vlr_gemm_swiglu_rows: the fused kernel does not take M=%d I=%d K=%d with a row map", M, I, K);
     if (done < M) {       // remaining rows: plain GEMM (+ the adapter GEMMs) + SwiGLU kernel
         const bf16_t* xa = (const bf16_t*)x + (size_t)done * ldx;
         bf16_t* gur = (bf16_t*)gu + (size_t)done * 2 * I;
@@ -1030,6 +1063,8 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
         GemmParams p = fused_params(x, wqkv, qkv, M1, N, K, ldx, K, N);
         p.fuse = 2; p.pos = pos; p.rope_cos = cos_t; p.rope_sin = sin_t; p.max_pos = max_pos; p.rope_cols = rope_cols;
         p.bias = (const bf16_t*)bias;
+        VLR_REQUIRE(!t_a_rows || !seg, "vlr_gemm_qkv_rope: no row map on a launch with an adapter segment");
+        p.a_rows = t_a_rows;
         seg_set(p, sg, &skp, 0);
         const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * M1 * N * K, stream);
         const bool took_ = seg ? vlr_gemm256p_seg_try_launch(p, stream) : vlr_gemm256p_fused_try_launch(p, stream);
@@ -1044,6 +1079,7 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
         GemmParams p2 = fused_params((const bf16_t*)x + (size_t)done * ldx, wqkv, (bf16_t*)qkv + (size_t)done * N, M - done, N, K, ldx, K, N);
         p2.fuse = 2; p2.pos = pos + done; p2.rope_cos = cos_t; p2.rope_sin = sin_t; p2.max_pos = max_pos; p2.rope_cols = rope_cols;
         p2.bias = (const bf16_t*)bias;
+        if (t_a_rows) { p2.A = (const bf16_t*)x; p2.a_rows = t_a_rows + done; }
         if (seg) { SegArgs s2 = *sg; s2.u = (const bf16_t*)sg->u + (size_t)done * sg->ldu; seg_set(p2, &s2, &skp, done); }
         const int pj_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * (M - done) * N * K, stream);
         const bool took2_ = seg ? vlr_gemm256p_seg_try_launch(p2, stream) : vlr_gemm256p_fused_try_launch(p2, stream);
@@ -1054,6 +1090,7 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
             done = M;
         }
     }
+    VLR_REQUIRE(done == M || !t_a_rows, "vlr_gemm_qkv_rope_rows: the fused kernel does not take M=%d N=%d K=%d with a row map", M, N, K);
     if (done < M) {
         bf16_t* qr = (bf16_t*)qkv + (size_t)done * N;
         int rc = gemm_impl(0, (const bf16_t*)x + (size_t)done * ldx, wqkv, qr, bias, nullptr, M - done, N, K, ldx, K, N, 0, 0, 0, 0, 1.0f, stream);
@@ -1073,6 +1110,32 @@ extern "C" int vlr_gemm_qkv_rope(const void* x, const void* wqkv, void* qkv, con
 extern "C" int vlr_gemm_qkv_rope_bias(const void* x, const void* wqkv, const void* bias, void* qkv, const int* pos, const float* cos_t,
                                       const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim, int max_pos, hipStream_t stream) {
     return gemm_qkv_rope_impl(x, wqkv, qkv, pos, cos_t, sin_t, M, N, rope_cols, K, ldx, head_dim, max_pos, nullptr, bias, stream);
+}
+// The three forward NT products of a decoder layer with the A operand read through an M-side row map (include/vlr.h): logical row m of
+// x / a is row a_rows[m] of the buffer.  Same launches, same kernels, same K order as the unmapped entry points on a gathered A
+extern "C" int vlr_gemm_qkv_rope_bias_rows(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv, const int* pos,
+                                           const float* cos_t, const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim,
+                                           int max_pos, hipStream_t stream) {
+    VLR_REQUIRE(a_rows, "vlr_gemm_qkv_rope_bias_rows: null row map");
+    const ARowsScope scope(a_rows, -1, -1);
+    return gemm_qkv_rope_impl(x, wqkv, qkv, pos, cos_t, sin_t, M, N, rope_cols, K, ldx, head_dim, max_pos, nullptr, bias, stream);
+}
+extern "C" int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void* wgu, void* gu, void* act, int M, int I, int K, int ldx,
+                                    int store_gu, hipStream_t stream) {
+    VLR_REQUIRE(a_rows, "vlr_gemm_swiglu_rows: null row map");
+    const ARowsScope scope(a_rows, -1, -1);
+    return gemm_swiglu_impl(x, wgu, gu, act, M, I, K, ldx, store_gu, nullptr, stream);
+}
+// y [M][N] (fp32 when f32, else bf16) = a W^T + res: the residual projection (vlr_gemm_bf16 / vlr_gemm_bf16_f32res, NT, lda = ldb = K,
+// ldc = ldr = N).  peel_rows > 0: the LAST peel_rows logical rows go to the 128x128 split-K kernel and must stand as one contiguous run of
+// buffer rows starting at tail_row0 (a_rows[M - peel_rows + i] == tail_row0 + i - not checked); 0: none
+extern "C" int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
+                                 int peel_rows, int tail_row0, hipStream_t stream) {
+    VLR_REQUIRE(a && a_rows && W && y, "vlr_gemm_res_rows: null argument");
+    VLR_REQUIRE(peel_rows >= 0 && peel_rows < M && (peel_rows == 0 || tail_row0 >= 0), "vlr_gemm_res_rows: %d peeled rows of %d at buffer row %d", peel_rows, M, tail_row0);
+    const ARowsScope scope(a_rows, tail_row0, peel_rows);
+    return f32 ? gemm_impl_ex(0, a, W, y, nullptr, res, M, N, K, K, K, N, N, 0, 0, 1, 1.0f, res ? 1 : 0, stream)
+               : gemm_impl(0, a, W, y, nullptr, res, M, N, K, K, K, N, N, 0, 0, 0, 1.0f, stream);
 }
 // the same with the LoRA adapters of q_proj / k_proj / v_proj: u [M][ldu] = the three s drop_t(x) A_t^T side by side, Bl = lora_B
 // rows of q | k | v [N][r]; q_cols / kv_cols = widths of the q and of the k (= v) output blocks
@@ -1186,6 +1249,43 @@ extern "C" int vlr_gemm_swiglu_bwd_add(const void* dy, const void* wdown, void* 
                                        int H, hipStream_t stream) {
     VLR_REQUIRE(dact_add, "vlr_gemm_swiglu_bwd_add: null addend");
     return gemm_swiglu_bwd_impl(dy, wdown, gu, dact_ws, dact_add, M, I, H, stream);
+}
+// Out of place through a source-row map: gate | up of dense row m are row src_rows[m] of gu_src [Mc][2I] (the kept rows of a
+// row-compact forward; read only), [d gate | d up] go to row m of dgu_out [M][2I], which must not overlap gu_src.  Peel, route and
+// arithmetic are vlr_gemm_swiglu_bwd's at M rows: the bits of that call on the expanded gate | up.  (No addend variant.)
+extern "C" int vlr_swiglu_bwd_src(const void* gu_src, const int* src_rows, void* dgu_out, const void* dact, int M, int I, hipStream_t st);
+extern "C" int vlr_gemm_swiglu_bwd_src(const void* dy, const void* wdown, const void* gu_src, const int* src_rows, void* dgu_out,
+                                       void* dact_ws, int M, int I, int H, hipStream_t stream) {
+    VLR_REQUIRE(dy && wdown && gu_src && src_rows && dgu_out && dact_ws, "vlr_gemm_swiglu_bwd_src: null operand");
+    VLR_REQUIRE(M > 0 && I > 0 && H > 0 && I % 8 == 0 && H % 8 == 0, "vlr_gemm_swiglu_bwd_src: bad shape M=%d I=%d H=%d", M, I, H);
+    VLR_REQUIRE((const char*)gu_src < (const char*)dgu_out || (const char*)gu_src >= (const char*)dgu_out + (size_t)M * I * 4,
+                "vlr_gemm_swiglu_bwd_src: dgu_out must not alias gu_src");
+    const int tn = (I + 255) / 256;
+    const int peel = choose_peel(M, I, tn, H, stream, true);
+    const int tm256 = (M + 255) / 256;
+    const int M1 = peel ? (tm256 - peel) * 256 : M;
+    int done = 0;
+    for (int part = 0; part < 2; ++part) {       // the main launch, then the peeled rows (same fused epilogue, one tile per workgroup)
+        const int r0 = part ? done : 0, rows = part ? M - done : M1;
+        if (part && (done == 0 || done == M)) break;
+        GemmParams p = fused_params((const bf16_t*)dy + (size_t)r0 * H, wdown, (bf16_t*)dgu_out + (size_t)r0 * 2 * I, rows, I, H, H, I, 2 * I);
+        p.fuse = 7; p.C2 = const_cast<void*>(gu_src); p.ldc2 = 2 * I; p.pos = src_rows + r0;
+        const int pi_ = vlr_prof_begin(VLR_K_GEMM_NN, 2.0 * rows * I * H, stream);
+        const bool took_ = vlr_gemm256p_swiglu_bwd_try_launch(p, stream);
+        vlr_prof_end(took_ ? pi_ : -1, stream);
+        if (!took_) break;
+        int rc = vlr_check_launch(part ? "vlr_gemm_swiglu_bwd_src(fused tail)" : "vlr_gemm_swiglu_bwd_src(fused)");
+        if (rc != VLR_OK) return rc;
+        done = part ? M : M1;
+    }
+    if (done < M) {
+        const bf16_t* dyr = (const bf16_t*)dy + (size_t)done * H;
+        bf16_t* da = (bf16_t*)dact_ws + (size_t)done * I;
+        int rc = gemm_impl(1, dyr, wdown, da, nullptr, nullptr, M - done, I, H, H, I, I, I, 0, 0, 0, 1.0f, stream);
+        if (rc != VLR_OK) return rc;
+        return vlr_swiglu_bwd_src(gu_src, src_rows + done, (bf16_t*)dgu_out + (size_t)done * 2 * I, da, M - done, I, stream);
+    }
+    return VLR_OK;
 }
 static int gemm_swiglu_bwd_impl(const void* dy, const void* wdown, void* gu, void* dact_ws, const void* dact_add, int M, int I, int H,
                                 hipStream_t stream) {

@@ -99,13 +99,15 @@ __device__ __forceinline__ void lds_dma16_s(const char* sbase, uint32_t voff, ui
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "m0");
 }
 // per-lane byte offsets of the two pieces this wave stages for one half tile, relative to the K tile's base address
-__device__ __forceinline__ void piece_off_kc(int ld, int row0, int nrows, int wave, int lane, uint32_t (&off)[2]) {
+// rows != NULL (GemmParams::a_rows): logical row g of the operand is row rows[g] of the buffer - one integer load per piece, at tile setup
+__device__ __forceinline__ void piece_off_kc(int ld, int row0, int nrows, int wave, int lane, uint32_t (&off)[2], const int* __restrict__ rows = nullptr) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = (wave + 8 * i) * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((r >> 1) & 7);
         int grow = row0 + r;
         grow = grow < nrows ? grow : nrows - 1;
+        if (rows) grow = rows[grow];
         off[i] = (uint32_t)(((size_t)grow * ld + c * 8) * 2);
     }
 }
@@ -175,7 +177,7 @@ __device__ __forceinline__ void piece_off_ks(int ld, int col0, int ncols, int wa
 // ---- LDS-DMA of one half tile, 2 wave instructions (1 KiB each) per wave (general form: K tail -> zeros)
 // k-contiguous operand P[rows][ld]: instruction = 8 rows x 128 B
 __device__ __forceinline__ void stage_kc(const bf16_t* __restrict__ P, int ld, int row0, int nrows, int k0, int K,
-                                         const bf16_t* __restrict__ zero16, char* half, int wave, int lane) {
+                                         const bf16_t* __restrict__ zero16, char* half, int wave, int lane, const int* __restrict__ rows = nullptr) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int R = (wave + 8 * i) * 8;
@@ -183,6 +185,7 @@ __device__ __forceinline__ void stage_kc(const bf16_t* __restrict__ P, int ld, i
         const int c = (lane & 7) ^ ((r >> 1) & 7);
         int grow = row0 + r;
         grow = grow < nrows ? grow : nrows - 1;
+        if (rows) grow = rows[grow];
         const int k = k0 + c * 8;
         const bf16_t* g = (k + 8 <= K) ? P + (size_t)grow * ld + k : zero16;
         lds_dma16(g, half + R * 128);
@@ -344,11 +347,13 @@ struct TileProb { const bf16_t* A; const bf16_t* B; void* C; int M, N, lda, ldb,
 // GRP = true (TN continuous pipeline only): the launch covers TWO problems of equal K - (A, B, C, M, N, ld*) and (A1, ... ) of GemmParams -
 // as one list of output tiles, the first problem's tiles first: the weight gradients of gate|up and down_proj are 5.375 + 2.69 rounds
 // of 256 tiles as two launches (6 + 3) and 8.06 as one (the host peels one tile row to the 128x128 kernel: 8).
-template <bool A_KS, bool B_KS, int ABL = 0, bool CONT = false, int FUSE = 0, bool SEG = false, bool GRP = false>
+// AROWS: the K-contiguous A operand is read through GemmParams::a_rows (instantiations of their own: the unmapped kernels carry no test)
+template <bool A_KS, bool B_KS, int ABL = 0, bool CONT = false, int FUSE = 0, bool SEG = false, bool GRP = false, bool AROWS = false>
 __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_t* __restrict__ zero16) {
+    static_assert(!AROWS || (!A_KS && !SEG && !GRP), "row map: K-contiguous A, no adapter segment, one problem");
     static_assert(!GRP || (A_KS && B_KS && CONT && FUSE == 0 && !SEG), "grouped launches: TN, plain epilogue");
-    static_assert(FUSE == 0 || (FUSE == 6 && !CONT && !A_KS && B_KS) || (FUSE != 6 && CONT && !A_KS && (FUSE == 3 ? B_KS : !B_KS)),
-                  "fused epilogues: continuous pipeline; 1, 2, 4, 5 NT, 3 NN; 6 (dropout-accumulate) NN on the LDS-image epilogue");
+    static_assert(FUSE == 0 || (FUSE == 6 && !CONT && !A_KS && B_KS) || (FUSE != 6 && CONT && !A_KS && (FUSE == 3 || FUSE == 7 ? B_KS : !B_KS)),
+                  "fused epilogues: continuous pipeline; 1, 2, 4, 5 NT, 3, 7 NN; 6 (dropout-accumulate) NN on the LDS-image epilogue");
     static_assert(!SEG || (!A_KS && !B_KS && FUSE <= 2), "adapter segment: NT, plain / SwiGLU / RoPE epilogues");
     constexpr int NW = FUSE == 1 ? 128 : PT;      // output columns (of the gate half, for SwiGLU) per workgroup tile
     extern __shared__ __attribute__((aligned(16))) char smem[];   // P_LDS_BYTES
@@ -475,7 +480,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if constexpr (A_KS) piece_off_ks(tp.lda, m0 + h * 128, tp.M, wave, lane, offA[h]);
-        else piece_off_kc(tp.lda, m0 + h * 128, tp.M, wave, lane, offA[h]);
+        else piece_off_kc(tp.lda, m0 + h * 128, tp.M, wave, lane, offA[h], AROWS ? p.a_rows : nullptr);
         if constexpr (B_KS) piece_off_ks(tp.ldb, n0 + h * 128, tp.N, wave, lane, offB[h]);
         else piece_off_kc_b<FUSE>(tp.ldb, n0, h, tp.N, wave, lane, offB[h]);
     }
@@ -498,7 +503,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
                     const int k0 = (kbn + tile - ntp) * PK;
                     if constexpr (h < 2) {
                         if constexpr (A_KS) stage_ks(tnx.A, tnx.lda, m0n + h * 128, tnx.M, k0, p.K, zero16, dst, wave, lane);
-                        else stage_kc(tnx.A, tnx.lda, m0n + h * 128, tnx.M, k0, p.K, zero16, dst, wave, lane);
+                        else stage_kc(tnx.A, tnx.lda, m0n + h * 128, tnx.M, k0, p.K, zero16, dst, wave, lane, AROWS ? p.a_rows : nullptr);
                     } else {
                         if constexpr (B_KS) stage_ks(tnx.B, tnx.ldb, n0n + (h - 2) * 128, tnx.N, k0, p.K, zero16, dst, wave, lane);
                         else stage_kc_b<FUSE>(tnx.B, tnx.ldb, n0n, h - 2, tnx.N, k0, p.K, zero16, dst, wave, lane);
@@ -560,7 +565,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
             const int k0 = (kb + tile) * PK;
             if constexpr (h < 2) {
                 if constexpr (A_KS) stage_ks(tp.A, tp.lda, m0 + h * 128, tp.M, k0, p.K, zero16, dst, wave, lane);
-                else stage_kc(tp.A, tp.lda, m0 + h * 128, tp.M, k0, p.K, zero16, dst, wave, lane);
+                else stage_kc(tp.A, tp.lda, m0 + h * 128, tp.M, k0, p.K, zero16, dst, wave, lane, AROWS ? p.a_rows : nullptr);
             } else {
                 if constexpr (B_KS) stage_ks(tp.B, tp.ldb, n0 + (h - 2) * 128, tp.N, k0, p.K, zero16, dst, wave, lane);
                 else stage_kc_b<FUSE>(tp.B, tp.ldb, n0, h - 2, tp.N, k0, p.K, zero16, dst, wave, lane);
@@ -1159,6 +1164,117 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
                 __builtin_amdgcn_sched_barrier(0);
             });
         });
+    } else if constexpr (CONT && FUSE == 7) {
+        // SwiGLU backward epilogue, OUT OF PLACE through a source-row map (vlr_gemm_swiglu_bwd_src): gate | up of output row gm sit in
+        // row p.pos[gm] of C2 (the kept rows of a row-compact forward, never written), [d gate | d up] go to row gm of C [M][ldc].  The
+        // arithmetic is FUSE 3's, chunk by chunk.  A wave keeps the ring when every valid row r of its 128 rows of the tile reads source
+        // row pos[m0] + r - the run that starts at the TILE's first row reaches through all of them: its load descriptor is based at the
+        // source row of the tile's first row, a second descriptor serves the stores.  Any other wave - a run boundary among its rows, or
+        // in front of them in the other wave group's rows (3 runs per DPO pair) - takes the per-row body: the VLR_EPI_FAST == 0 body with
+        // the load row mapped.
+        const bf16_t* GS = reinterpret_cast<const bf16_t*>(p.C2);
+        bf16_t* GO = reinterpret_cast<bf16_t*>(tp.C);
+        const int I = tp.N;
+        const int ec8 = (lane & 3) * 8, er8 = lane >> 2;
+        const int s0 = p.pos[m0];
+        bool run_ok = true;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {      // (unpredicated, clamped, consumed at once: no load stays pending into the next K loop - EPI_USE)
+            const int r = a * 128 + wr * 64 + lane;
+            const int sr = p.pos[min(m0 + r, tp.M - 1)];
+            EPI_USE(sr);
+            run_ok = run_ok && (m0 + r >= tp.M || sr == s0 + r);
+        }
+        if (__builtin_amdgcn_ballot_w64(!run_ok) == 0) {
+            constexpr int D = 7;
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int rows_v = min(tp.M - m0, PT);                               // >= 1: valid rows of this tile
+            const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(GS) + (size_t)s0 * p.ldc2, 0, rows_v * p.ldc2 * 2, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(GO + (size_t)m0 * tp.ldc, 0, rows_v * tp.ldc * 2, 0x00020000);
+            const int row_l = wr * 64 + (ln >> 2), col_l = n0 + wc * 32 + (ln & 3) * 8;
+            uint32_t vg[2], vu[2];      // per-lane byte offsets (ldc == ldc2 == 2 I: one set serves both descriptors); 0x80000000 = past every descriptor
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const bool okc = col_l + b * 128 + 8 <= I;
+                vg[b] = okc ? (uint32_t)((row_l * p.ldc2 + col_l + b * 128) * 2) : 0x80000000u;
+                vu[b] = okc ? vg[b] + (uint32_t)(I * 2) : 0x80000000u;
+            }
+            const uint32_t nrg = (uint32_t)(rows_v * p.ldc2 * 2);
+            u32x4 gq[D], uq[D];
+            auto request = [&](auto nc) {
+                constexpr int n = decltype(nc)::value;
+                constexpr int a = n >> 3, c = n & 7, i = c >> 1, b = c & 1, sl = n % D;
+                const uint32_t sg_ = min((uint32_t)((a * 128 + i * 16) * p.ldc2 * 2), nrg);
+                gq[sl] = __builtin_amdgcn_raw_buffer_load_b128(rl, vg[b], sg_, 0);
+                uq[sl] = __builtin_amdgcn_raw_buffer_load_b128(rl, vu[b], sg_, 0);
+            };
+            static_for<0, D>(request);
+            static_for<0, 16>([&](auto nc) {
+                constexpr int n = decltype(nc)::value;
+                constexpr int a = n >> 3, c = n & 7, i = c >> 1, b = c & 1, sl = n % D;
+                f32x4 o[2];
+                EPI_XPOSE_F32_8(acc[a][i][b][0], acc[a][i][b][1], o);
+                float d[8] = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
+                float g[8], u[8], dg[8], du[8];
+                unpack8(gq[sl], g);
+                unpack8(uq[sl], u);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float sg = fast_sigmoid(g[e]);
+                    du[e] = d[e] * g[e] * sg;
+                    dg[e] = d[e] * u[e] * sg * (1.f + g[e] * (1.f - sg));
+                }
+                const u32x4 wg = pack8(dg), wu = pack8(du);
+                if constexpr (n + D < 16) request(std::integral_constant<int, n + D>{});
+                const uint32_t sg_ = min((uint32_t)((a * 128 + i * 16) * p.ldc2 * 2), nrg);
+                __builtin_amdgcn_raw_buffer_store_b128(wg, rs, vg[b], sg_, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(wu, rs, vu[b], sg_, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        } else
+        static_for<0, 2>([&](auto ac) {
+            constexpr int a = decltype(ac)::value;
+            u32x4 gq[8], uq[8];
+            static_for<0, 8>([&](auto cc) {      // unpredicated, clamped at the edges
+                constexpr int c = decltype(cc)::value;
+                constexpr int i = c >> 1, b = c & 1;
+                int gm = m0 + a * 128 + wr * 64 + i * 16 + er8;
+                int gn = n0 + b * 128 + wc * 32 + ec8;
+                gm = gm < tp.M ? gm : tp.M - 1;
+                gn = gn + 8 <= I ? gn : I - 8;
+                const size_t sm = (size_t)p.pos[gm];
+                gq[c] = *reinterpret_cast<const u32x4*>(GS + sm * p.ldc2 + gn);
+                uq[c] = *reinterpret_cast<const u32x4*>(GS + sm * p.ldc2 + I + gn);
+            });
+            static_for<0, 8>([&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                constexpr int i = c >> 1, b = c & 1;
+                f32x4 o[2];
+                EPI_XPOSE_F32_8(acc[a][i][b][0], acc[a][i][b][1], o);
+                EPI_USE(gq[c]); EPI_USE(uq[c]);
+                int lc = lane;                        // opaque per chunk: the chunks' addresses are recomputed, not carried
+                asm volatile("" : "+v"(lc));
+                const int gm = m0 + a * 128 + wr * 64 + i * 16 + (lc >> 2);
+                const int gn = n0 + b * 128 + wc * 32 + (lc & 3) * 8;
+                const bool ok = gm < tp.M && gn + 8 <= I;
+                float d[8] = {o[0][0], o[0][1], o[0][2], o[0][3], o[1][0], o[1][1], o[1][2], o[1][3]};
+                float g[8], u[8], dg[8], du[8];
+                unpack8(gq[c], g);
+                unpack8(uq[c], u);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float sg = fast_sigmoid(g[e]);
+                    du[e] = d[e] * g[e] * sg;
+                    dg[e] = d[e] * u[e] * sg * (1.f + g[e] * (1.f - sg));
+                }
+                if (ok) {
+                    EPI_GST(u32x4, GO + (size_t)gm * tp.ldc + gn, pack8(dg));
+                    EPI_GST(u32x4, GO + (size_t)gm * tp.ldc + I + gn, pack8(du));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        });
     } else if constexpr (CONT && FUSE == 2) {
         // RoPE epilogue: acc[a][i][0][j] / acc[a][i][1][j] = features d / d + 64 of one head (rotate-half partners).  Both fp32 chunks go
         // through the patch (row-contiguous: lane -> rows er, er + 8; features fc .. fc + 3 of the head's first / second 64), so that the
@@ -1554,7 +1670,16 @@ bool vlr_gemm256p_fused_try_launch(const GemmParams& p_in, hipStream_t stream) {
     sched_prepare(p);
     TRACE_SET(p);
     const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
-    if (p.fuse == 1) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 1>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    if (p.a_rows) {
+        static bool attr_r = false;
+        if (!attr_r) {
+            attr_r = true;
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 2, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        }
+        if (p.fuse == 1) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 1, false, false, true>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+        else hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 2, false, false, true>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    } else if (p.fuse == 1) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 1>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     else hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 2>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     vlr_prof_end(pi, stream);
     return true;
@@ -1629,6 +1754,7 @@ bool vlr_gemm256p_swiglu_bwd_try_launch(const GemmParams& p_in, hipStream_t stre
     if (!attr) {
         attr = true;
         hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, true, 0, true, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
     }
     bf16_t* zero16 = gemm256p_zero16();
     if (!zero16) return false;
@@ -1637,10 +1763,13 @@ bool vlr_gemm256p_swiglu_bwd_try_launch(const GemmParams& p_in, hipStream_t stre
     if (p.K < 4 * PK) return false;
     const int grid = persist_grid(ntiles, n_cu);
     if ((((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C2) & 15) || p.lda % 8 != 0 || p.ldb % 8 != 0 || p.N % 8 != 0 || p.ldc2 % 8 != 0) return false;
+    // fuse 7: gate | up read at row p.pos[m] of C2, [d gate | d up] written to row m of C [M][ldc] - no addend, one row pitch for both
+    if (p.fuse == 7 && (!p.pos || !p.C || ((uintptr_t)p.C & 15) || p.ldc != p.ldc2 || p.residual)) return false;
     sched_prepare(p);
     TRACE_SET(p);
     const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
-    hipLaunchKernelGGL((gemm256p_kernel<false, true, 0, true, 3>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    if (p.fuse == 7) hipLaunchKernelGGL((gemm256p_kernel<false, true, 0, true, 7>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    else hipLaunchKernelGGL((gemm256p_kernel<false, true, 0, true, 3>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     vlr_prof_end(pi, stream);
     return true;
 }
@@ -1732,6 +1861,15 @@ bool vlr_gemm256p_try_launch(int layout, const GemmParams& p_in, hipStream_t str
     if (!ready) return false;
     const int ntiles = ((p.M + PT - 1) / PT) * ((p.N + PT - 1) / PT);
     if (ntiles < 192) return false;
+    if (p.a_rows) {      // only the NT kernels exist with a row map
+        if (layout != 0) return false;
+        static bool attr_r = false;
+        if (!attr_r) {
+            attr_r = true;
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, false, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES);
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        }
+    }
     const int tiles = persist_grid(ntiles, gemm256p_n_cu());   // grid size: persistent workgroups when there are more tiles than CUs
     // 16-byte DMA source alignment: k-contiguous operands need ld % 8 and K % 8 (checked by the caller), k-strided
     // operands ld % 8 and at least 8 columns; pointers 16-byte aligned
@@ -1763,13 +1901,15 @@ bool vlr_gemm256p_try_launch(int layout, const GemmParams& p_in, hipStream_t str
     if (ntiles > tiles && !p.bias && (p.out_f32 ? f32_ok : (res_ok && !p.res_f32)) && !p.accumulate && p.act == ACT_NONE && p.K >= 4 * PK &&
         (p.out_f32 || (p.ldc % 8 == 0 && p.N % 8 == 0)) && !((uintptr_t)p.C & 15)) {
         sched_prepare(p);
-        if (layout == 0) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+        if (p.a_rows) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 0, false, false, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+        else if (layout == 0) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
         else if (layout == 1) hipLaunchKernelGGL((gemm256p_kernel<false, true, 0, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
         else hipLaunchKernelGGL((gemm256p_kernel<true, true, 0, true>), dim3(tiles), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
         vlr_prof_end(pi, stream);
         return true;
     }
-    if (layout == 0) hipLaunchKernelGGL((gemm256p_kernel<false, false>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    if (p.a_rows) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, false, 0, false, false, true>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    else if (layout == 0) hipLaunchKernelGGL((gemm256p_kernel<false, false>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     else if (layout == 1) hipLaunchKernelGGL((gemm256p_kernel<false, true>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     else hipLaunchKernelGGL((gemm256p_kernel<true, true>), dim3(tiles), dim3(512), TILE_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     vlr_prof_end(pi, stream);

@@ -74,11 +74,29 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
 // again through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st);      // gemm.hip: proj_res with the rows of the 128x128 kernel named by the caller
-// keep_for_backward = 1 (the policy pass): gate | up is written too, as in vlr_decoder_layer_fwd_ex; what the backward reads holds Mc rows
-extern "C" int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
-                                                const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
-                                                int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
-                                                int S, int keep_for_backward, vlr_stream_t st) {
+// gemm.hip: the three forward NT products with the A operand read through an M-side row map; gemm256p.hip: what a launch would pick
+extern "C" int vlr_gemm_qkv_rope_bias_rows(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv, const int* pos,
+                                           const float* cos_t, const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim,
+                                           int max_pos, hipStream_t stream);
+extern "C" int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void* wgu, void* gu, void* act, int M, int I, int K, int ldx,
+                                    int store_gu, hipStream_t stream);
+extern "C" int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
+                                 int peel_rows, int tail_row0, hipStream_t stream);
+int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32);
+int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
+// 1: the fused q|k|v + RoPE and gate|up + SwiGLU kernels take every row of this layer's shapes - what a row map on their A operand needs
+static int fused_take_all(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, int N, int Nq, int Nkv) {
+    return cfg->head_dim == 128 && (!w->bqkv || !((uintptr_t)w->bqkv & 7)) && vlr_internal_gemm256p_fused_takes(2, N, cfg->hidden, Nq + Nkv) &&
+           vlr_internal_gemm256p_fused_takes(1, 2 * cfg->inter, cfg->hidden, 0);
+}
+// attn_in_place: o_proj reads the kept rows of attn_dense through compact_rows where the persistent kernel takes the launch and the
+// peeled rows are the last dense rows (else, and always with attn_in_place = 0, they are compacted into a->attn first).
+// twin != NULL: xn1 / xn2 are written to the DENSE rows of a->xn1 / a->xn2 (and a shared row's dropped copy) by the scatter norms and the
+// fused projections read them through compact_rows - the caller has asked fused_take_all
+static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a, const void* x_in,
+                             const int* pos_compact, const int* dense_src, const int* compact_rows, const int* twin, int attn_in_place,
+                             int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S,
+                             int keep_for_backward, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && a && x_in && pos_compact && dense_src && compact_rows && qkv_dense && attn_dense,
                 "vlr_decoder_layer_fwd_compact: null argument");
     const int H = cfg->hidden, I = cfg->inter, M = batch * S;
@@ -94,25 +112,54 @@ extern "C" int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const 
     // into dropped rows cannot be reproduced: the launch then splits as its own row count suggests
     const int dense_peel = vlr_gemm_peel_rows(M, H);
     const int peel_rows = dense_peel <= tail_rows ? dense_peel : -1;
-    CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, Mc, H, cfg->rms_eps, st));
-    CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H,
-                                 cfg->head_dim, cfg->max_pos, st));
+    if (twin) {
+        CHECK(rf ? vlr_rmsnorm_fwd_f32_scatter((const float*)x_in, w->ln1, a->xn1, a->rstd1, compact_rows, twin, Mc, H, cfg->rms_eps, st)
+                 : vlr_rmsnorm_fwd_scatter(x_in, w->ln1, a->xn1, a->rstd1, compact_rows, twin, Mc, H, cfg->rms_eps, st));
+        CHECK(vlr_gemm_qkv_rope_bias_rows(a->xn1, compact_rows, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N,
+                                          Nq + Nkv, H, H, cfg->head_dim, cfg->max_pos, st));
+    } else {
+        CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, Mc, H, cfg->rms_eps, st));
+        CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H,
+                                     cfg->head_dim, cfg->max_pos, st));
+    }
     CHECK(vlr_gather_rows(a->qkv, dense_src, qkv_dense, M, N, st));              // dense row m = compact row dense_src[m]
     CHECK(vlr_attn_fwd_gqa(qkv_dense, off(qkv_dense, Nq), off(qkv_dense, (size_t)Nq + Nkv), N, attn_dense, Nq, a->lse, key_mask, batch, S,
                            cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(vlr_gather_rows(attn_dense, compact_rows, a->attn, Mc, Nq, st));       // compact row j = dense row compact_rows[j]
-    CHECK(vlr_internal_gemm_res_peel(rf, a->attn, w->wo, a->x_mid, x_in, Mc, H, Nq, peel_rows, st));
-    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, Mc, H, cfg->rms_eps, st));
-    CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, Mc, I, H, H, keep_for_backward ? 1 : 0, st));
+    // o_proj straight from the dense attention rows: the rows the 128x128 kernel gets are the last rows of both layouts (peel_rows >= 0:
+    // they lie in the kept tail) and reach it by a plain pointer
+    if (attn_in_place && H > 512 && peel_rows >= 0 && peel_rows < Mc && vlr_internal_gemm256p_res_variant(Mc - peel_rows, H, Nq, rf) != 0) {
+        CHECK(vlr_gemm_res_rows(rf, attn_dense, compact_rows, w->wo, a->x_mid, x_in, Mc, H, Nq, peel_rows, M - peel_rows, st));
+    } else {
+        CHECK(vlr_gather_rows(attn_dense, compact_rows, a->attn, Mc, Nq, st));       // compact row j = dense row compact_rows[j]
+        CHECK(vlr_internal_gemm_res_peel(rf, a->attn, w->wo, a->x_mid, x_in, Mc, H, Nq, peel_rows, st));
+    }
+    if (twin) {
+        CHECK(rf ? vlr_rmsnorm_fwd_f32_scatter((const float*)a->x_mid, w->ln2, a->xn2, a->rstd2, compact_rows, twin, Mc, H, cfg->rms_eps, st)
+                 : vlr_rmsnorm_fwd_scatter(a->x_mid, w->ln2, a->xn2, a->rstd2, compact_rows, twin, Mc, H, cfg->rms_eps, st));
+        CHECK(vlr_gemm_swiglu_rows(a->xn2, compact_rows, w->wgu, a->gu, a->act, Mc, I, H, H, keep_for_backward ? 1 : 0, st));
+    } else {
+        CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, Mc, H, cfg->rms_eps, st));
+        CHECK(vlr_gemm_swiglu(a->xn2, w->wgu, a->gu, a->act, Mc, I, H, H, keep_for_backward ? 1 : 0, st));
+    }
     CHECK(vlr_internal_gemm_res_peel(rf, a->act, w->wdown, a->x_out, a->x_mid, Mc, H, I, peel_rows, st));
     return VLR_OK;
 }
+// keep_for_backward = 1 (the policy pass): gate | up is written too, as in vlr_decoder_layer_fwd_ex; what the backward reads holds Mc rows
+// - a->attn among them (vlr_decoder_layer_bwd_compact reads it): the attention rows are compacted
+extern "C" int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                                const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
+                                                int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
+                                                int S, int keep_for_backward, vlr_stream_t st) {
+    return layer_fwd_compact(cfg, w, a, x_in, pos_compact, dense_src, compact_rows, nullptr, keep_for_backward ? 0 : 1, Mc, tail_rows,
+                             qkv_dense, attn_dense, key_mask, batch, S, keep_for_backward, st);
+}
+// the no-grad pass keeps nothing: o_proj reads the dense attention rows through compact_rows (a->attn is then not written)
 extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                                              const void* x_in, const int* pos_compact, const int* dense_src, const int* compact_rows,
                                              int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch,
                                              int S, vlr_stream_t st) {
-    return vlr_decoder_layer_fwd_compact_ex(cfg, w, a, x_in, pos_compact, dense_src, compact_rows, Mc, tail_rows, qkv_dense, attn_dense,
-                                            key_mask, batch, S, 0, st);
+    return layer_fwd_compact(cfg, w, a, x_in, pos_compact, dense_src, compact_rows, nullptr, 1, Mc, tail_rows, qkv_dense, attn_dense,
+                             key_mask, batch, S, 0, st);
 }
 // What vlr_decoder_layer_fwd_compact_ex left on Mc rows (`c`), copied to the dense layout (`d`, batch * S rows) through dense_src: a
 // dropped row takes its twin's values, which ARE its values - the dense backward then runs unchanged on `d` and computes what it
@@ -137,6 +184,38 @@ extern "C" int vlr_layer_acts_expand(const vlr_llama_cfg* cfg, const vlr_layer_a
     CHECK(vlr_gather_f32(c->rstd2, dense_src, d->rstd2, M, st));
     CHECK(vlr_gather_rows(c->gu, dense_src, d->gu, M, 2 * I, st));
     CHECK(vlr_gather_rows(c->act, dense_src, d->act, M, I, st));
+    return VLR_OK;
+}
+// vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1) for a backward that reads the kept rows in place (vlr_decoder_layer_bwd_src):
+// what only row-wise consumers read - rstd1, x_mid, rstd2, gate | up, x_out - is written on Mc rows into the layer's own set `a` and
+// never copied; the operands of the weight-gradient GEMMs, whose mapped dimension would be K - xn1, xn2, act - are written on Mc rows
+// into the scratch set `s` and copied to the dense rows of `a`.  q|k|v, attn and lse land densely in `a`, as in the expand route
+extern "C" int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                                  const vlr_layer_acts* s, const void* x_in, const vlr_row_maps* m, const int* key_mask,
+                                                  int batch, int S, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && a && s && x_in && m, "vlr_decoder_layer_fwd_compact_keep: null argument");
+    VLR_REQUIRE(m->compact_rows && m->dense_src && m->pos_compact, "vlr_decoder_layer_fwd_compact_keep: null row map");
+    VLR_REQUIRE(a->xn1 && a->rstd1 && a->qkv && a->attn && a->lse && a->x_mid && a->xn2 && a->rstd2 && a->gu && a->act && a->x_out &&
+                s->xn1 && s->qkv && s->attn && s->xn2 && s->act, "vlr_decoder_layer_fwd_compact_keep: null activation pointer");
+    VLR_REQUIRE(a->xn1 != s->xn1 && a->xn2 != s->xn2 && a->act != s->act && a->qkv != s->qkv && a->attn != s->attn,
+                "vlr_decoder_layer_fwd_compact_keep: the scratch set must not alias the layer's set");
+    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
+    VLR_REQUIRE(H % 8 == 0 && I % 8 == 0, "vlr_decoder_layer_fwd_compact_keep: hidden %d and inter %d must be multiples of 8", H, I);
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    VLR_REQUIRE(kvh > 0 && cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact_keep: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim;
+    // where the fused projections take every row (the 7B shapes; fused_take_all) the norms write xn1 / xn2 to their dense rows and the
+    // projections read them through compact_rows; elsewhere they are written on Mc rows into `s` and copied
+    const int dense_xn = m->twin && fused_take_all(cfg, w, Nq + 2 * Nkv, Nq, Nkv);
+    const vlr_layer_acts t = {dense_xn ? a->xn1 : s->xn1, a->rstd1, s->qkv, s->attn, a->lse, a->x_mid, dense_xn ? a->xn2 : s->xn2, a->rstd2,
+                              a->gu, s->act, a->x_out};
+    CHECK(layer_fwd_compact(cfg, w, &t, x_in, m->pos_compact, m->dense_src, m->compact_rows, dense_xn ? m->twin : nullptr, 1, m->Mc,
+                            m->tail_rows, a->qkv, a->attn, key_mask, batch, S, 1, st));
+    if (!dense_xn) {
+        CHECK(vlr_gather_rows(s->xn1, m->dense_src, a->xn1, M, H, st));
+        CHECK(vlr_gather_rows(s->xn2, m->dense_src, a->xn2, M, H, st));
+    }
+    CHECK(vlr_gather_rows(s->act, m->dense_src, a->act, M, I, st));
     return VLR_OK;
 }
 // gemm256p.hip: the kernel a launch would pick, as host arithmetic
@@ -428,6 +507,41 @@ extern "C" int vlr_decoder_layer_bwd(const vlr_llama_cfg* cfg, const vlr_layer_w
     else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
     CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
     CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, M, H, st));
+    return VLR_OK;
+}
+// vlr_decoder_layer_bwd after vlr_decoder_layer_fwd_compact_keep, call for call, in the same order and at M = batch * S rows: the two
+// norm backwards read x_in / rstd1 and x_mid / rstd2 at src_rows[row], the SwiGLU backward reads gate | up there and writes
+// [d gate | d up] to the dense scratch dgu [M][2I], which the weight-gradient pair and the dgrad read in place of a->gu
+static int norm_bwd_src(int f32, const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
+                        int acc, void* ws, const int* src_rows, int M, int H, hipStream_t st) {
+    return f32 ? vlr_rmsnorm_bwd_f32_src(dy, (const float*)x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st)
+               : vlr_rmsnorm_bwd_src(dy, x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st);
+}
+extern "C" int vlr_decoder_layer_bwd_src(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                                         const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, void* dgu, const int* src_rows,
+                                         const void* x_in, const void* dx_out, void* dx_in, const int* pos, const int* key_mask,
+                                         int batch, int S, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && g && a && ws && dgu && src_rows && x_in && dx_out && dx_in && pos, "vlr_decoder_layer_bwd_src: null argument");
+    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    // ---- MLP
+    CHECK(vlr_gemm_swiglu_bwd_src(dx_out, w->wdown, a->gu, src_rows, dgu, ws->dact, M, I, H, st));
+    CHECK(vlr_gemm_bf16_tn_pair(dgu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
+    CHECK(vlr_gemm_bf16(1, dgu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
+    CHECK(norm_bwd_src(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, src_rows, M, H, st));
+    // ---- attention (vlr_decoder_layer_bwd's calls on the dense q|k|v, attn, lse, xn1)
+    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;
+    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
+    CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
+                           key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
+                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
+    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, M, 0, st));
+    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
+    CHECK(norm_bwd_src(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, src_rows, M, H, st));
     return VLR_OK;
 }
 

@@ -153,6 +153,18 @@ _SIGS = {
     "vlr_decoder_layer_bwd_compact": [P, P, P, I, P, P, P, P, P, P, P, P, I, I, P],
     "vlr_layer_acts_expand": [P, P, P, P, I, I, P],
     "vlr_gather_f32": [P, P, P, I, P],
+    # the dense backward on the kept rows in place: source-row maps in place of the expand copies
+    "vlr_rmsnorm_bwd_src": [P, P, P, P, P, P, P, I, P, P, I, I, P],
+    "vlr_rmsnorm_bwd_f32_src": [P, P, P, P, P, P, P, I, P, P, I, I, P],
+    "vlr_swiglu_bwd_src": [P, P, P, P, I, I, P],
+    "vlr_rmsnorm_fwd_scatter": [P, P, P, P, P, P, I, I, F, P],
+    "vlr_rmsnorm_fwd_f32_scatter": [P, P, P, P, P, P, I, I, F, P],
+    "vlr_gemm_qkv_rope_bias_rows": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "vlr_gemm_swiglu_rows": [P, P, P, P, P, I, I, I, I, I, P],
+    "vlr_gemm_res_rows": [I, P, P, P, P, P, I, I, I, I, I, P],
+    "vlr_gemm_swiglu_bwd_src": [P, P, P, P, P, P, I, I, I, P],
+    "vlr_decoder_layer_fwd_compact_keep": [P, P, P, P, P, P, P, I, I, P],
+    "vlr_decoder_layer_bwd_src": [P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, P],
     "vlr_expand_rows_zero": [P, P, P, I, I, P],
     "vlr_fold_rows": [P, P, P, P, I, I, P],
     "vlr_gemm_swiglu": [P, P, P, P, I, I, I, I, I, P],

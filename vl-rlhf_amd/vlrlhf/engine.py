@@ -563,6 +563,7 @@ class LlavaHipEngine:
         # ... and so does the policy's training pass, forward and backward (forward_hidden(save=True, prefix_dedup_rows=True))
         self.prefix_dedup_policy = True          # False: the policy pass is dense (prefix_dedup = False withholds both)
         self.prefix_dedup_policy_exact_only = True   # taken only where its forward is the dense forward bit for bit (vlr_decoder_layer_compact_exact)
+        self.prefix_dedup_policy_expand = False      # True: the dense backward reads expanded copies of the kept rows (vlr_layer_acts_expand) instead of the kept rows in place - the A/B of the source-row maps, same bits
         self.prefix_dedup_policy_backward = False    # True: the backward runs on the kept rows too (vlr_decoder_layer_bwd_compact): a third fewer GEMM rows, gradients within bf16 rounding of the dense backward's but not its bits
         self.prefix_dedup_policy_passes = 0      # row-compact policy passes so far
         self.last_prefix_dedup_policy = None     # dict(P, Mc, M, exact) of the last one
@@ -1083,6 +1084,34 @@ class LlavaHipEngine:
         self.last_prefix_dedup_policy = dict(P=list(plan["P"]), Mc=Mc, M=M, exact=plan["exact"], backward="dense")
         return acts[-1]["x_out"], acts
 
+    def _forward_layers_compact_keep(self, ws, e, plan, x0, Bn, S, tag):
+        """_forward_layers_compact_expand without the copies a row-wise consumer does not need (vlr_decoder_layer_fwd_compact_keep):
+        rstd1, x_mid, rstd2, gate | up and x_out stay on the kept rows, in the first Mc rows of the layer's own activation set, and the
+        backward reads them through plan["dense_src"] (vlr_decoder_layer_bwd_src); xn1, xn2 and act - the K-side operands of the
+        weight-gradient GEMMs - exist densely: the norms write xn1 / xn2 to their dense rows and the fused projections read them through
+        plan["compact_rows"] (where the fused kernels take the shape; else they are copied), act is copied.  The final norm runs on the kept rows and `hidden` is expanded.
+        -> (hidden [M] dense, rstd_f [Mc], x_last [Mc], acts, x0_c [Mc]).  The same bits as the expand route, step for step."""
+        M, Mc, H = plan["M"], plan["Mc"], self.H
+        w16 = 2 if x0.dtype == torch.float32 else 1                  # (row copy: fp32 rows = 2H 16-bit columns)
+        x0_c = self._buf((tag, "dedup_x0", Bn, S), (M, H), x0.dtype)
+        _hip.call("vlr_gather_rows", x0, plan["compact_rows"], x0_c, Mc, H * w16)
+        x, acts = x0_c, []
+        for l in range(self.L):
+            a = self._layer_acts(tag, l, Bn, S)
+            s = self._layer_acts(tag + "/compact", l % 2, Bn, S)
+            _hip.call("vlr_decoder_layer_fwd_compact_keep", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], s["struct"], x,
+                      plan["struct"], e["mask"], Bn, S)
+            acts.append(a)
+            x = a["x_out"]
+        hidden_c = self._buf((tag, "dedup_hidden", Bn, S), (M, H))
+        rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
+        self._norm_fwd(x, ws.v["norm"], hidden_c, rstd_f, Mc)
+        hidden = torch.empty(M, H, dtype=BF16, device=self.dev)
+        _hip.call("vlr_gather_rows", hidden_c, plan["dense_src"], hidden, M, H)
+        self.prefix_dedup_policy_passes += 1
+        self.last_prefix_dedup_policy = dict(P=list(plan["P"]), Mc=Mc, M=M, exact=plan["exact"], backward="dense")
+        return hidden, rstd_f, x, acts, x0_c
+
     def _layer_fwd_compact_call(self, ws, l, a, x, e, plan, qkv_d, attn_d, Bn, S, keep):
         """one decoder layer forward of the row-compact policy pass into the activation set `a` (keep: also write what only the backward reads)"""
         _hip.call("vlr_decoder_layer_fwd_compact_ex", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], x, plan["pos"],
@@ -1122,7 +1151,10 @@ class LlavaHipEngine:
         rows of each pair's shared prompt once (_prefix_plan) - the context keeps its dense contract, ctx["x_last"] alone is compact.
         With save=True on the policy weights (the DPO trainer's policy pass) the training forward does the same (_policy_plan: full
         fine-tune, no NEFTune; by default only where the compact forward is the dense one bit for bit) and copies what the backward
-        reads to the dense layout: the context is a dense pass's.  With prefix_dedup_policy_backward the backward runs on the kept rows
+        reads to the dense layout: the context is a dense pass's.  Without gradient checkpointing (and unless prefix_dedup_policy_expand)
+        only act is copied (xn1 / xn2 are written densely) and the dense backward reads the rest at dense_src[row]: ctx["src_plan"] is set, ctx["plan"]
+        stays None, the layers' rstd1 / x_mid / rstd2 / gu / x_out, ctx["x_last"], ctx["rstd_f"] and ctx["x0_c"] hold the kept rows,
+        ctx["hidden"] is dense.  With prefix_dedup_policy_backward the backward runs on the kept rows
         too: ctx["plan"] is set, ctx["acts"], ctx["x_last"], ctx["rstd_f"] and ctx["x0_c"] hold the kept rows, ctx["hidden"] is dense."""
         c = self.cfg
         if ws is self.policy:
@@ -1175,7 +1207,7 @@ class LlavaHipEngine:
         # activations (the dense step's bits where the plan is exact) or - prefix_dedup_policy_backward - on the kept rows too (one more
         # bf16 rounding per shared d qkv row).  NEFTune draws different noise for the two copies of a prompt row: under it the rows are
         # not equal, and the pass is dense
-        pplan, x0_c, layers_done = None, None, False
+        pplan, x0_c, layers_done, src_plan = None, None, False, None
         if (prefix_dedup_rows and self.prefix_dedup and self.prefix_dedup_policy and self.row_compact_layers and save and ws is self.policy
                 and kv_cache is None and image_dup == 2 and not use_lora and self.lora is None and Bn % 2 == 0 and self.neftune is None):
             pplan = self._policy_plan(e, ids, Bn, meta)
@@ -1184,6 +1216,11 @@ class LlavaHipEngine:
         elif pplan is not None and self.prefix_dedup_policy_backward:
             hidden, rstd_f, x, acts, x0_c = self._forward_layers_compact_policy(ws, e, pplan, x0, Bn, S, tag, ckpt)
             plan = pplan
+        elif pplan is not None and not ckpt and not self.prefix_dedup_policy_expand:
+            # compact forward, dense backward reading the kept rows in place: ctx["src_plan"] (NOT ctx["plan"]: the backward is dense);
+            # acts hold rstd / x_mid / gate|up / x_out on the kept rows, x_last, rstd_f and x0_c too; hidden is dense
+            hidden, rstd_f, x, acts, x0_c = self._forward_layers_compact_keep(ws, e, pplan, x0, Bn, S, tag)
+            src_plan, pplan, layers_done = pplan, None, True
         elif pplan is not None:         # compact forward, dense backward: the context below is a dense pass's (the final norm runs on M rows)
             x, acts = self._forward_layers_compact_expand(ws, e, pplan, x0, Bn, S, tag, ckpt)
             pplan, layers_done = None, True
@@ -1200,7 +1237,7 @@ class LlavaHipEngine:
                           Bn, S, self.nkv, self.hd, kv_cache.cap, 0)
             acts.append(a)
             x = a["x_out"]
-        if plan is None:
+        if plan is None and src_plan is None:
             hidden = torch.empty(M, self.H, dtype=BF16, device=self.dev)
             rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)
             self._norm_fwd(x, ws.v["norm"], hidden, rstd_f, M)
@@ -1211,6 +1248,7 @@ class LlavaHipEngine:
                     vit_feat=vit_feat, feats=feats, proj_z=z, proj_h=h, image_dup=image_dup, n_rows=n_rows, n_feat=n_feat,
                     pack=pack, tag=tag, lora_seed=lora_seed, neftune=nf, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
                     plan=pplan, x0_c=x0_c,     # a row-compact policy pass: acts, x_last, rstd_f and x0_c hold the plan's Mc kept rows; hidden is dense
+                    src_plan=src_plan,         # a dense backward that reads the kept rows in place (_forward_layers_compact_keep)
                     embed=dict(pos=e["pos"], mask=e["mask"], extra=e.get("extra"), tag=tag, img_map=e["img_map"], plora_seed=e.get("plora_seed"), grad_pass=bool(save)))
 
     # ------------------------------------------------------------------------------------------------ decoding
@@ -1631,6 +1669,14 @@ class LlavaHipEngine:
             nxt = dxb if cur is dxa else dxa
             _hip.call("vlr_expand_rows_zero", cur, plan["dense_own"], nxt, M, self.H)
             cur = nxt
+        elif ctx.get("src_plan") is not None:
+            # the dense backward on the kept rows in place (full fine-tune only): every call of the dense backward at M rows, the
+            # row-wise ones reading x / rstd / gate|up at dense_src[row]
+            dsrc = ctx["src_plan"]["dense_src"]
+            x_last = ctx["x_last"]
+            _hip.call("vlr_rmsnorm_bwd_f32_src" if x_last.dtype == torch.float32 else "vlr_rmsnorm_bwd_src", dhidden, x_last, ws.v["norm"],
+                      ctx["rstd_f"], None, dxa, self.gv["norm"], acc, self._norm_ws, dsrc, M, self.H)
+            cur = self._layers_backward(ctx, self._layer_bwd_src(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
         else:
             self._norm_bwd(dhidden, ctx["x_last"], ws.v["norm"], ctx["rstd_f"], None, dxa, self.gv["norm"] if full else None, acc if full else 0, M)
             cur = self._layers_backward(ctx, self._layer_bwd(ctx, acc, *self._bwd_workspace(ctx)), dxa, dxb)
@@ -1658,7 +1704,8 @@ class LlavaHipEngine:
             qkv_d, attn_d = (self._buf((ctx["tag"], k, Bn, S), (ctx["M"], n)) for k, n in (("dedup_qkv", self.Nqkv), ("dedup_attn", self.Nq)))
         for l in range(self.L - 1, -1, -1):
             a = ctx["acts"][l]
-            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else (ctx["x0"] if plan is None else ctx["x0_c"])
+            kept = plan is not None or ctx.get("src_plan") is not None      # the layer inputs are the pass's kept rows
+            x_in = ctx["acts"][l - 1]["x_out"] if l > 0 else (ctx["x0_c"] if kept else ctx["x0"])
             if ctx["ckpt"] and plan is not None:
                 self._layer_fwd_compact_call(ws, l, a, x_in, ctx["embed"], plan, qkv_d, attn_d, Bn, S, True)
             elif ctx["ckpt"]:
@@ -1684,6 +1731,19 @@ class LlavaHipEngine:
             if f"l{l}.bqkv" in self.gv:          # (the folded d qkv of the kept rows: a shared row's entry is already the sum of its two copies)
                 _hip.call("vlr_colsum", wsb["dqkv"], plan["Mc"], self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
         return compact
+
+    def _layer_bwd_src(self, ctx, acc, wsb, lws):
+        """the per-layer backward after _forward_layers_compact_keep (ctx["src_plan"]), for _layers_backward: vlr_decoder_layer_bwd_src
+        over the dense backward's scratch and one [M][2I] buffer for d gate | d up, shared by all layers"""
+        ws, Bn, S, M, plan = ctx["ws"], ctx["Bn"], ctx["S"], ctx["M"], ctx["src_plan"]
+        dgu = self._buf(("dgu", M), (M, 2 * self.I))
+
+        def src(l, a, x_in, cur, nxt):
+            _hip.call("vlr_decoder_layer_bwd_src", self.llama_cfg, self.layer_weights(ws, l, ctx["tag"]), self.layer_grads(l), acc, a["struct"],
+                      lws, dgu, plan["dense_src"], x_in, cur, nxt, ctx["pos"], ctx["mask"], Bn, S)
+            if f"l{l}.bqkv" in self.gv:          # bias of the fused q|k|v projection: column sum of this layer's d qkv (post rope-transpose)
+                _hip.call("vlr_colsum", wsb["dqkv"], M, self.Nqkv, self.Nqkv, self.gv[f"l{l}.bqkv"], acc, self._colsum_ws)
+        return src
 
     def _layer_bwd(self, ctx, acc, wsb, lws):
         """the per-layer backward of this engine's current mode, for _layers_backward"""
