@@ -437,6 +437,33 @@ long vlr_v_head_bwd_workspace_bytes(int R, int H);
 int vlr_v_head_bwd(const void* hg, const void* w, const float* g, void* dhg_inout, void* dw, void* db, int accumulate, void* workspace,
                    int R, int H, vlr_stream_t stream);
 
+/* ---- GRPO (Group Relative Policy Optimization: G samples per prompt, the advantage is the reward standardised inside its group; no
+ *      value head, no GAE, no whitening across the batch; additive entry points, vlr_abi_version() does not move).  As for PPO: the
+ *      per-token tensors are compact [R] fp32 over the response rows of vlr_build_rows, seq_off [n + 1] delimits the n sequences, no
+ *      atomics, every reduction runs in an order fixed by the sizes alone (two calls give the same bits), exp is expf, nothing allocates.
+ * vlr_grpo_advantages: scores [P * G], row p G + j is sample j of prompt p.  Per group: mean_p = sum_j s / G, std_p = sqrt(sum_j
+ *      (s - mean_p)^2 / (G - 1)) (unbiased, torch.std), A = (s - mean_p) / (std_p + 1e-4) when scale_rewards, else s - mean_p.  The
+ *      moments are taken of the scores shifted by the group's first one, so a group of equal scores gives std_p = 0 and A = 0 exactly,
+ *      never NaN.  stats[4] = {mean of all scores, mean over the groups of std_p, fraction of groups with std_p == 0, 0}.
+ *      P >= 1, G >= 2 (refused before any launch).  One workgroup of 1024 threads: wave per group, lane-strided sums folded by xor
+ *      butterflies, the statistics summed per wave in group order and over the 16 waves in order.
+ * vlr_grpo_loss: for token t of sequence s, with A = adv_seq[s]: r = exp(logp - old_logp),
+ *      l = -min(r A, clamp(r, 1 - eps_low, 1 + eps_high) A), and when beta != 0, with d = ref_logp - logp: l += beta (exp(d) - d - 1).
+ *      loss_type 0 "grpo": (1 / n) sum_s (1 / len_s) sum_t l; 1 "bnpo": sum l / R; 2 "dr_grpo": sum l / (n max_completion_length).
+ *      old_logp NULL stands for logp itself with the gradient stopped: the ratio is exactly 1 and the gradient still flows.  ref_logp
+ *      may be NULL only when beta == 0 (it is not read then).  The bounds 1 - eps_low and 1 + eps_high are formed in double and rounded
+ *      to fp32 once (torch.clamp with Python floats).  dlogp = upstream * d loss / d logp exactly as torch autograd differentiates that
+ *      expression (clamp passes the gradient on its closed interval, min halves a tie): -A r inside the clip range and where the
+ *      unclipped branch is the smaller one, 0 on the clipped side; final on return.  stats[8] = {loss, token-mean of the KL term (0 when
+ *      beta == 0), clip fraction low (r < 1 - eps_low and A < 0), clip fraction high (r > 1 + eps_high and A > 0), their sum, mean
+ *      ratio, mean len_s = R / n, 0}; the fractions and means are over the R tokens.  R >= 1, 1 <= n <= R, eps >= 0, loss_type in
+ *      0..2, max_completion_length >= 1 for loss_type 2 (read by no other).  One workgroup of 1024 threads, one pass: wave per
+ *      sequence (a token finds its sequence without a search), lanes stride its tokens. */
+int vlr_grpo_advantages(const float* scores, int P, int G, int scale_rewards, float* advantages, float* stats, vlr_stream_t stream);
+int vlr_grpo_loss(const float* logp, const float* old_logp, const float* ref_logp, const float* adv_seq, const int* seq_off, int R, int n,
+                  double eps_low, double eps_high, float beta, int loss_type, int max_completion_length, float upstream, float* dlogp,
+                  float* stats, vlr_stream_t stream);
+
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d
  * policy_{chosen,rejected}_logps with g = grad_losses or 1/len(losses) when NULL (trl: loss = losses.mean()). */

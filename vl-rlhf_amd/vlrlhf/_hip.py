@@ -143,6 +143,9 @@ _SIGS = {
     "vlr_ppo_advantages": [P, P, P, P, P, F, I, F, F, I, P, P, P, P, I, I, P],
     "vlr_ppo_loss": [P, P, P, P, P, P, I, D, D, F, F, F, P, P, P, P],
     "vlr_v_head_bwd": [P, P, P, P, P, P, I, P, I, I, P],
+    # GRPO (include/vlr.h "GRPO"): the group-standardised advantages, the clipped per-token loss with its gradient
+    "vlr_grpo_advantages": [P, I, I, I, P, P, P],
+    "vlr_grpo_loss": [P, P, P, P, P, I, I, D, D, F, I, I, F, P, P, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],

@@ -241,6 +241,46 @@ class _PpoHeadsFn(torch.autograd.Function):
         return dh, None, None, None, None
 
 
+class _TokenLogpsFn(torch.autograd.Function):
+    """hidden [M, H] -> token log-probs [R] on the response rows (engine.token_logps_forward / token_logps_backward) as one autograd node"""
+
+    @staticmethod
+    def forward(ctx, hidden, model, c, labels, label_pad):
+        tok, lp = model.engine.token_logps_forward(c, labels, label_pad)
+        ctx.lp, ctx.engine = lp, model.engine
+        model._last_lp = lp
+        return tok
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        dh = ctx.engine.token_logps_backward(ctx.lp, dlogp.contiguous())
+        ctx.lp = None
+        return dh, None, None, None, None
+
+
+def token_logps(model, input_ids, attention_mask, labels, **img):
+    """-> token log-probs [R] fp32 of a PLAIN family wrapper (LlavaForRL, QwenVLForRL: no value head) on the R response rows - the
+    positions whose logits predict a token with label != -100, sequence after sequence; token_seq_off(model) [Bn + 1] delimits them.
+    What GRPO trains on: the same forward as VLModelWithValueHead's, without the value head."""
+    if labels is None:
+        raise ValueError("token_logps needs labels (-100 outside the response): log-probs exist on the response rows only")
+    out = model(input_ids=input_ids, attention_mask=attention_mask, labels=labels, **img)
+    lg = out.logits
+    c, hidden = lg.c, lg.hidden
+    if hidden.requires_grad:
+        return _TokenLogpsFn.apply(hidden, model, c, c["labels"], -100)
+    tok, model._last_lp = model.engine.token_logps_forward(c, c["labels"], -100)
+    return tok
+
+
+def token_seq_off(model):
+    """[Bn + 1] int32 on the device: the rows of sequence b in the last token_logps(model, ...) are seq_off[b] .. seq_off[b + 1]"""
+    lp = getattr(model, "_last_lp", None)
+    if lp is None:
+        raise RuntimeError("token_seq_off: no token_logps(model, ...) has run yet")
+    return lp["seq_off"]
+
+
 def init_v_head(hidden_size: int, strategy=None, initializer_range: float = 0.2, seed: int = 0):
     """trl ValueHead + _init_weights: `None` keeps nn.Linear's default (weight and bias ~ U(-1/sqrt(H), 1/sqrt(H))), "normal" draws the
     weight from N(0, initializer_range) and zeroes the bias - on the host from `seed`, so every rank starts from the same head"""

@@ -1304,56 +1304,29 @@ class FixedKLController:
 KL_PENALTY_IDS = {"kl": 0, "abs": 1, "mse": 2}
 
 
-class VLPPOTrainer:
-    """The PPO optimisation step - trl==0.8.1 PPOTrainer.step as the reference's VLPPOTrainer (base/trainer.py) drives it, restated in
-    include/vlr.h ("PPO") and run on the HIP engine: no-grad rollout passes of the policy (log-probs, values) and of the reference
-    (the adapters switched off under LoRA, else a frozen copy made when none is given), rewards + GAE + whitening in
-    vlr_ppo_advantages, then ppo_epochs x minibatches of forward, vlr_ppo_loss, backward and one Adam step per backward batch.
+class VLOnlineRLTrainer:
+    """What the online-RL trainers (VLPPOTrainer, VLGRPOTrainer) share: tokenize_row and the shuffled batches, scoring by a separate reward
+    model, the logging seam, checkpoint / resume (weights, optimizer, the row order and whatever `_checkpoint_extra` adds), the
+    [query ; response] batch with its image inputs, and sampling through the model's own generate.  A subclass sets config, model,
+    reward_model, processor, tokenizer, data_collator, dataset, generation_kwargs, is_peft_model, accelerator, padding_value, state,
+    log_history and _data_gen in its __init__ (`_init_shared`), and provides step() and train()."""
 
-    tokenize_row, generate, scoring by a separate reward model, step, the train() loop and checkpoint / resume (weights, optimizer, kl_coef,
-    the permutation generator and the row order) are here; the entry point is vlrlhf/ppo.py.
+    IMAGE_KEYS = ("pixel_values",)      # what of a collated batch reaches the models as image input
 
-    Deliberate differences from trl: the image inputs reach every forward of the step (trl's prepare_model_inputs drops them); the
-    entropy statistics are left out (they need a pass over the vocabulary and carry no gradient); rollout and reference passes run in
-    eval mode (no adapter dropout, no NEFTune noise); world_size > 1 is refused, since whitening and the KL mean are per process in trl
-    and nothing here settles what they should be across ranks."""
-
-    def __init__(self, config=None, model=None, ref_model=None, reward_model=None, processor=None, dataset=None, data_collator=None,
-                 generation_kwargs=None):
-        # argument order = the reference's VLPPOTrainer
-        if config is None or model is None:
-            raise ValueError("VLPPOTrainer needs a config and a model")
-        if not hasattr(model, "v_head"):
-            raise ValueError("VLPPOTrainer needs a model with a value head (vlrlhf.base.model.VLModelWithValueHead)")
-        if int(getattr(config, "world_size", 1) or 1) > 1 or _world() > 1:
-            raise NotImplementedError("PPO on more than one GPU: whitening and the KL mean are per process in trl and the MI355X path "
-                                      "does not settle what they are across ranks")
-        if config.kl_penalty == "full":
-            raise NotImplementedError("kl_penalty='full' needs the [R][V] logits of the policy and the reference; 'kl', 'abs' and 'mse' are built")
+    def _init_shared(self, config, model, reward_model, processor, dataset, data_collator, generation_kwargs):
         self.config, self.model, self.reward_model = config, model, reward_model
         self.processor, self.dataset, self.data_collator = processor, dataset, data_collator
         self.tokenizer = processor.tokenizer if processor is not None else None
         self.generation_kwargs = dict(generation_kwargs or {})
         self.is_peft_model = bool(getattr(model, "is_peft_model", False))
-        if ref_model is None and not self.is_peft_model:      # trl: create_reference_model(model) when none is given
-            ref_model = model.pretrained_model.create_reference_model()
-        self.ref_model = ref_model
-        self.kl_ctl = (AdaptiveKLController(config.init_kl_coef, config.target, config.horizon) if config.adap_kl_ctrl
-                       else FixedKLController(config.init_kl_coef))
         self.accelerator = _Accelerator(model)
-        self._perm_gen = torch.Generator().manual_seed(int(config.seed))
         pad = getattr(self.tokenizer, "pad_token_id", None)
         self.padding_value = int(pad) if pad is not None else 0
         self.state = _State()
-        self._stored_metrics = defaultdict(lambda: defaultdict(list))
         self.log_history: List[dict] = []
-        self.time_phases = False      # tools/ppo_bench.py: HIP events around the rollout and the optimisation of step() -> last_timing
-        self.keep_rollout = False     # True: step() leaves its rollout tensors in last_rollout (diagnostics, the tests); off, nothing outlives the step
-        self.last_rollout = None
         self.dataset = self._tokenize_dataset(dataset)
         self._data_gen = torch.Generator().manual_seed(int(config.seed) + 1)      # the order of the rows, apart from the step's permutations
         self._epoch_data_state = self._data_gen.get_state().tolist()
-        model.engine.init_optimizer()
 
     # ------------------------------------------------------------------------------------------ data
     def _tokenize_dataset(self, ds):
@@ -1407,42 +1380,12 @@ class VLPPOTrainer:
         img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
         return self.reward_model.score(ids.to(dev), mask.to(dev), reward_cols=torch.tensor([n - 1 for n in lens]), **img).float().cpu()
 
-    # ------------------------------------------------------------------------------------------ loop
-    IMAGE_KEYS = ("pixel_values",)      # what of a collated batch reaches the models as image input
+    def _checkpoint_extra(self):
+        """what the trainer adds to trainer_state.json (JSON-ready)"""
+        return {}
 
-    def train(self, resume_from_checkpoint=None):
-        """reference :428-499: per batch - generate, decode, rebuild the conversations, score with the reward model, step, log (the
-        `log` seam; no wandb tables: the per_device_gamelog_size first rows are logged as text).  A batch whose scoring raises is
-        skipped.  config.save_steps > 0 writes a checkpoint every so many steps; resume_from_checkpoint continues one."""
-        resume = resume_from_checkpoint or getattr(self.config, "resume_from_checkpoint", None)
-        skip = 0
-        if resume:
-            skip = int(self.load_checkpoint(resume).get("batches_seen", 0))
-        self.batches_seen = 0
-        for batch in self.get_batches():
-            self.batches_seen += 1
-            if self.batches_seen <= skip:      # the rows a resumed run has already consumed (the row order is part of the checkpoint)
-                continue
-            queries = batch["input_ids"]
-            img = {k: batch[k] for k in self.IMAGE_KEYS if k in batch}
-            responses = self.generate(queries, return_prompt=False, batch_size=32, **img)      # reference :437-442
-            batch["response"] = self.tokenizer.batch_decode(responses, skip_special_tokens=True)
-            try:
-                scores = self.compute_scores(batch["query"], batch["response"], img)
-            except NotImplementedError:
-                raise
-            except Exception as e:      # reference: warn, print the responses, skip the batch
-                print(f"[ppo] WARNING: error when computing reward score, skipping this batch: {e!r}\n{batch['response']}", flush=True)
-                self.skipped_batches = getattr(self, "skipped_batches", 0) + 1
-                continue
-            stats = self.step(queries, responses, [float(x) for x in scores], **img)
-            k = self.config.per_device_gamelog_size
-            game = [dict(query=self.processor.remove_image_placeholder(q), response=r, reward=float(s))
-                    for q, r, s in zip(batch["query"][:k], batch["response"][:k], scores[:k])]
-            self.log(dict(stats, game_log=game))
-            if self.config.save_steps and self.state.global_step % self.config.save_steps == 0:
-                self.save_checkpoint()
-        return self.log_history
+    def _restore_extra(self, state, path):
+        """the inverse of _checkpoint_extra, after the weights are loaded and before the optimizer state is"""
 
     def log(self, logs):
         """the logging seam of the other trainers: one entry per step in log_history, printed on rank 0"""
@@ -1454,9 +1397,10 @@ class VLPPOTrainer:
 
     # ------------------------------------------------------------------------------------------ checkpoints
     def save_checkpoint(self, path=None):
-        """`output_dir/checkpoint-<step>/`: the weights (adapter + value head under LoRA, else the checkpoint + v_head.bin), the optimizer
-        state (fp32 master / m / v + step), and trainer_state.json with the step counter, kl_coef, the states of the permutation and
-        row-order generators, the batches consumed and the log history.  A directory is complete or absent."""
+        """`output_dir/checkpoint-<step>/`: the weights (the adapter under LoRA, else the checkpoint; a value-head model adds its head
+        to either), the optimizer state (fp32 master / m / v + step), and trainer_state.json with the step counter, the state of the
+        row-order generator, the batches consumed, the log history and the trainer's own `_checkpoint_extra` (PPO: kl_coef and the
+        permutation generator; GRPO: the sampling generator).  A directory is complete or absent."""
         import json
         import shutil
         from safetensors.torch import save_file
@@ -1465,23 +1409,25 @@ class VLPPOTrainer:
         tmp = path + ".tmp"
         shutil.rmtree(tmp, ignore_errors=True)
         os.makedirs(tmp)
-        self.model.save_pretrained(tmp)
+        if self.is_peft_model:      # (VLModelWithValueHead.save_pretrained does the same under LoRA, and adds its head)
+            self.model.save_adapter(tmp)
+        else:
+            self.model.save_pretrained(tmp)
         st = eng.optimizer_state()
         if st is not None:
             for k in ("master", "m", "v"):
                 save_file({k: st[k].detach().cpu()}, os.path.join(tmp, f"optimizer_{k}.safetensors"))
         hist = [{k: v for k, v in h.items()} for h in self.log_history]
         with open(os.path.join(tmp, "trainer_state.json"), "w") as f:
-            json.dump(dict(global_step=self.state.global_step, opt_step=eng.opt_step, kl_coef=float(self.kl_ctl.value),
-                           perm_generator=self._perm_gen.get_state().tolist(), data_generator_start=self._epoch_data_state,
+            json.dump(dict(global_step=self.state.global_step, opt_step=eng.opt_step, data_generator_start=self._epoch_data_state,
                            batches_seen=int(getattr(self, "batches_seen", 0)), lora_calls=getattr(eng, "_lora_calls", 0),
-                           batch_size=self.config.batch_size, log_history=hist), f)
+                           batch_size=self.config.batch_size, log_history=hist, **self._checkpoint_extra()), f)
         shutil.rmtree(path, ignore_errors=True)
         os.replace(tmp, path)
         return path
 
     def load_checkpoint(self, path):
-        """weights, optimizer, kl_coef, the permutation generator and the row order of a save_checkpoint directory -> its state dict"""
+        """weights, optimizer, the row order and the trainer's own `_restore_extra` of a save_checkpoint directory -> its state dict"""
         import json
         from safetensors.torch import load_file
         eng = self.model.engine
@@ -1497,14 +1443,12 @@ class VLPPOTrainer:
                 if fn.startswith("model") and fn.endswith(".safetensors"):
                     sd.update(load_file(os.path.join(path, fn)))
             eng.policy.load_state_dict(sd)
-            self.model.load_v_head(path)
+        self._restore_extra(state, path)
         if os.path.isfile(os.path.join(path, "optimizer_master.safetensors")):      # (the master copy carries the head too)
             bufs = {k: load_file(os.path.join(path, f"optimizer_{k}.safetensors"))[k] for k in ("master", "m", "v")}
             eng.load_optimizer_state(bufs["master"], bufs["m"], bufs["v"], state["opt_step"])
         if hasattr(eng, "_lora_calls"):
             eng._lora_calls = int(state.get("lora_calls", 0))
-        self.kl_ctl.value = float(state["kl_coef"])
-        self._perm_gen.set_state(torch.tensor(state["perm_generator"], dtype=torch.uint8))
         self._data_gen.set_state(torch.tensor(state["data_generator_start"], dtype=torch.uint8))
         self.state.global_step = int(state["global_step"])
         self.log_history = list(state.get("log_history", []))
@@ -1560,18 +1504,6 @@ class VLPPOTrainer:
                 raise ValueError(f"step: image input {k!r} has {len(v)} entries for {n} rows carrying {total} images")
         return out
 
-    def _reference_logps(self, ids, mask, labels, img):
-        """token log-probs [R] of the reference on the response rows, under no-grad"""
-        dev = self.accelerator.device
-        if self.ref_model is None:
-            with self.model.disable_adapter():
-                return self.model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
-        if hasattr(self.ref_model, "v_head"):
-            return self.ref_model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
-        out = self.ref_model(input_ids=ids.to(dev), attention_mask=mask.to(dev), labels=labels.to(dev), **img)
-        c = out.logits.c
-        return self.ref_model.engine.logps_forward(c, c["labels"], None, False, -100, reduce_seq=False)[1]["tok"]
-
     # ------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
     def generate(self, queries, return_prompt: bool = False, generation_kwargs=None, batch_size=None, **img):
@@ -1601,9 +1533,23 @@ class VLPPOTrainer:
             responses += self._generate_rows(queries[lo:hi], return_prompt, kw, part)
         return responses
 
-    def _generate_rows(self, queries, return_prompt, kw, img):
-        """one call of the model's generate on `queries` (cpu id rows), left-padded to the longest -> the responses, cut at their stop"""
+    @staticmethod
+    def _stop_rules(model, kw):
+        """(eos ids, stop-word id sequences) that end a row of `model` under the generation keywords `kw`, as its generate reads them"""
         from ..models.Llava import stop_sequences
+        gc = kw.get("generation_config")
+        eos = kw.get("eos_token_id")
+        if eos is None:
+            eos = getattr(gc, "eos_token_id", None)
+        if eos is None:
+            eos = model.config.get("eos_token_id", 2)
+        eos = set(eos) if isinstance(eos, (list, tuple)) else {int(eos)}
+        stops = [t.cpu().tolist() for t in stop_sequences(getattr(gc, "stop_words_ids", None), "cpu")]
+        return eos, stops
+
+    def _generate_rows(self, queries, return_prompt, kw, img, fanout=1):
+        """one call of the model's generate on `queries` (cpu id rows), left-padded to the longest -> the responses, cut at their stop.
+        fanout = the num_return_sequences of `kw`: generate returns fanout rows per query, row p * fanout + j continuing query p"""
         n, T0, dev = len(queries), max(int(q.numel()) for q in queries), self.accelerator.device
         ids = torch.full((n, T0), self.padding_value, dtype=torch.long)
         mask = torch.zeros(n, T0, dtype=torch.long)
@@ -1613,24 +1559,113 @@ class VLPPOTrainer:
         img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in img.items()}
         out = self.model.generate(input_ids=ids.to(dev), attention_mask=mask.to(dev), **kw, **img)
         gen = out[:, T0:].cpu()
-        gc = kw.get("generation_config")
-        eos = kw.get("eos_token_id")
-        if eos is None:
-            eos = getattr(gc, "eos_token_id", None)
-        if eos is None:
-            eos = self.model.config.get("eos_token_id", 2)
-        eos = set(eos) if isinstance(eos, (list, tuple)) else {int(eos)}
-        stops = [t.cpu().tolist() for t in stop_sequences(getattr(gc, "stop_words_ids", None), "cpu")]
+        eos, stops = VLOnlineRLTrainer._stop_rules(self.model, kw)
         responses = []
-        for i in range(n):
+        for i in range(n * fanout):
             row, end = gen[i].tolist(), gen.shape[1]
             for t, tok in enumerate(row):
                 if tok in eos or any(len(sq) <= t + 1 and row[t + 1 - len(sq): t + 1] == sq for sq in stops):
                     end = t + 1
                     break
             r = gen[i, :end].clone()
-            responses.append(torch.cat([queries[i], r]) if return_prompt else r)
+            responses.append(torch.cat([queries[i // fanout], r]) if return_prompt else r)
         return responses
+
+
+class VLPPOTrainer(VLOnlineRLTrainer):
+    """The PPO optimisation step - trl==0.8.1 PPOTrainer.step as the reference's VLPPOTrainer (base/trainer.py) drives it, restated in
+    include/vlr.h ("PPO") and run on the HIP engine: no-grad rollout passes of the policy (log-probs, values) and of the reference
+    (the adapters switched off under LoRA, else a frozen copy made when none is given), rewards + GAE + whitening in
+    vlr_ppo_advantages, then ppo_epochs x minibatches of forward, vlr_ppo_loss, backward and one Adam step per backward batch.
+
+    tokenize_row, generate, scoring by a separate reward model, step, the train() loop and checkpoint / resume (weights, optimizer, kl_coef,
+    the permutation generator and the row order) are here; the entry point is vlrlhf/ppo.py.
+
+    Deliberate differences from trl: the image inputs reach every forward of the step (trl's prepare_model_inputs drops them); the
+    entropy statistics are left out (they need a pass over the vocabulary and carry no gradient); rollout and reference passes run in
+    eval mode (no adapter dropout, no NEFTune noise); world_size > 1 is refused, since whitening and the KL mean are per process in trl
+    and nothing here settles what they should be across ranks."""
+
+    def __init__(self, config=None, model=None, ref_model=None, reward_model=None, processor=None, dataset=None, data_collator=None,
+                 generation_kwargs=None):
+        # argument order = the reference's VLPPOTrainer
+        if config is None or model is None:
+            raise ValueError("VLPPOTrainer needs a config and a model")
+        if not hasattr(model, "v_head"):
+            raise ValueError("VLPPOTrainer needs a model with a value head (vlrlhf.base.model.VLModelWithValueHead)")
+        if int(getattr(config, "world_size", 1) or 1) > 1 or _world() > 1:
+            raise NotImplementedError("PPO on more than one GPU: whitening and the KL mean are per process in trl and the MI355X path "
+                                      "does not settle what they are across ranks")
+        if config.kl_penalty == "full":
+            raise NotImplementedError("kl_penalty='full' needs the [R][V] logits of the policy and the reference; 'kl', 'abs' and 'mse' are built")
+        self._init_shared(config, model, reward_model, processor, dataset, data_collator, generation_kwargs)
+        if ref_model is None and not self.is_peft_model:      # trl: create_reference_model(model) when none is given
+            ref_model = model.pretrained_model.create_reference_model()
+        self.ref_model = ref_model
+        self.kl_ctl = (AdaptiveKLController(config.init_kl_coef, config.target, config.horizon) if config.adap_kl_ctrl
+                       else FixedKLController(config.init_kl_coef))
+        self._perm_gen = torch.Generator().manual_seed(int(config.seed))
+        self._stored_metrics = defaultdict(lambda: defaultdict(list))
+        self.time_phases = False      # tools/ppo_bench.py: HIP events around the rollout and the optimisation of step() -> last_timing
+        self.keep_rollout = False     # True: step() leaves its rollout tensors in last_rollout (diagnostics, the tests); off, nothing outlives the step
+        self.last_rollout = None
+        model.engine.init_optimizer()
+
+    def _checkpoint_extra(self):
+        return dict(kl_coef=float(self.kl_ctl.value), perm_generator=self._perm_gen.get_state().tolist())
+
+    def _restore_extra(self, state, path):
+        if not self.is_peft_model:      # (under LoRA load_adapter has read the head)
+            self.model.load_v_head(path)
+        self.kl_ctl.value = float(state["kl_coef"])
+        self._perm_gen.set_state(torch.tensor(state["perm_generator"], dtype=torch.uint8))
+
+    # ------------------------------------------------------------------------------------------ loop
+    def train(self, resume_from_checkpoint=None):
+        """reference :428-499: per batch - generate, decode, rebuild the conversations, score with the reward model, step, log (the
+        `log` seam; no wandb tables: the per_device_gamelog_size first rows are logged as text).  A batch whose scoring raises is
+        skipped.  config.save_steps > 0 writes a checkpoint every so many steps; resume_from_checkpoint continues one."""
+        resume = resume_from_checkpoint or getattr(self.config, "resume_from_checkpoint", None)
+        skip = 0
+        if resume:
+            skip = int(self.load_checkpoint(resume).get("batches_seen", 0))
+        self.batches_seen = 0
+        for batch in self.get_batches():
+            self.batches_seen += 1
+            if self.batches_seen <= skip:      # the rows a resumed run has already consumed (the row order is part of the checkpoint)
+                continue
+            queries = batch["input_ids"]
+            img = {k: batch[k] for k in self.IMAGE_KEYS if k in batch}
+            responses = self.generate(queries, return_prompt=False, batch_size=32, **img)      # reference :437-442
+            batch["response"] = self.tokenizer.batch_decode(responses, skip_special_tokens=True)
+            try:
+                scores = self.compute_scores(batch["query"], batch["response"], img)
+            except NotImplementedError:
+                raise
+            except Exception as e:      # reference: warn, print the responses, skip the batch
+                print(f"[ppo] WARNING: error when computing reward score, skipping this batch: {e!r}\n{batch['response']}", flush=True)
+                self.skipped_batches = getattr(self, "skipped_batches", 0) + 1
+                continue
+            stats = self.step(queries, responses, [float(x) for x in scores], **img)
+            k = self.config.per_device_gamelog_size
+            game = [dict(query=self.processor.remove_image_placeholder(q), response=r, reward=float(s))
+                    for q, r, s in zip(batch["query"][:k], batch["response"][:k], scores[:k])]
+            self.log(dict(stats, game_log=game))
+            if self.config.save_steps and self.state.global_step % self.config.save_steps == 0:
+                self.save_checkpoint()
+        return self.log_history
+
+    def _reference_logps(self, ids, mask, labels, img):
+        """token log-probs [R] of the reference on the response rows, under no-grad"""
+        dev = self.accelerator.device
+        if self.ref_model is None:
+            with self.model.disable_adapter():
+                return self.model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
+        if hasattr(self.ref_model, "v_head"):
+            return self.ref_model(ids.to(dev), mask.to(dev), labels.to(dev), **img)[0]
+        out = self.ref_model(input_ids=ids.to(dev), attention_mask=mask.to(dev), labels=labels.to(dev), **img)
+        c = out.logits.c
+        return self.ref_model.engine.logps_forward(c, c["labels"], None, False, -100, reduce_seq=False)[1]["tok"]
 
     # ------------------------------------------------------------------------------------------ step
     def step(self, queries, responses, scores, **img):
@@ -1738,6 +1773,321 @@ class VLPPOTrainer:
         if self.keep_rollout:
             self.last_rollout = dict(old_logp=old_logp, old_values=old_values, ref_logp=ref_logp, seq_off=seq_off, advantages=adv, returns=ret,
                                      kl_sums=kl_sums, minibatch_stats=mb_stats)
+        return stats
+
+
+GRPO_LOSS_TYPES = {"grpo": 0, "bnpo": 1, "dr_grpo": 2}
+
+
+@dataclasses.dataclass
+class GRPOConfig:
+    """Group Relative Policy Optimization: batch_size prompts (P) per step, num_generations samples (G) per prompt, P * G rows per
+    step(); mini_batch_size rows per forward, mini_batch_size * gradient_accumulation_steps rows per optimizer step; num_iterations
+    optimisation passes over one step's rows.  epsilon / epsilon_high bound the ratio at 1 - epsilon and 1 + epsilon_high (None:
+    epsilon); beta weighs the per-token KL estimate against the reference (0: no reference pass at all)."""
+    learning_rate: float = 1e-6
+    batch_size: int = 4
+    num_generations: int = 8
+    mini_batch_size: int = 8
+    gradient_accumulation_steps: int = 1
+    num_iterations: int = 1
+    beta: float = 0.04
+    epsilon: float = 0.2
+    epsilon_high: Optional[float] = None
+    loss_type: str = "grpo"
+    scale_rewards: bool = True
+    max_new_tokens: Optional[int] = None
+    max_grad_norm: Optional[float] = None
+    seed: int = 0
+    world_size: int = 1
+    use_lora: bool = False
+    gradient_checkpointing: bool = False
+    output_dir: Optional[str] = None
+    per_device_gamelog_size: int = 2
+    local_rank: int = -1
+    save_steps: int = 0
+    resume_from_checkpoint: Optional[str] = None
+
+    def __post_init__(self):
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size ({self.batch_size}) must be at least 1 prompt")
+        if self.num_generations < 2:
+            raise ValueError(f"num_generations ({self.num_generations}) must be at least 2: the advantage is the reward standardised inside "
+                             "its group")
+        self.rows = self.batch_size * self.num_generations
+        self.backward_batch_size = self.mini_batch_size * self.gradient_accumulation_steps
+        if self.mini_batch_size <= 0 or self.gradient_accumulation_steps <= 0 or self.rows % self.backward_batch_size:
+            raise ValueError(f"batch_size * num_generations ({self.rows}) must be a multiple of mini_batch_size * gradient_accumulation_steps "
+                             f"({self.backward_batch_size})")
+        if self.num_iterations < 1:
+            raise ValueError(f"num_iterations ({self.num_iterations}) must be at least 1")
+        if self.beta < 0:
+            raise ValueError(f"beta ({self.beta}) must not be negative")
+        if self.epsilon < 0 or (self.epsilon_high is not None and self.epsilon_high < 0):
+            raise ValueError(f"epsilon ({self.epsilon}) and epsilon_high ({self.epsilon_high}) must not be negative")
+        if self.loss_type not in GRPO_LOSS_TYPES:
+            raise ValueError(f"loss_type must be one of {sorted(GRPO_LOSS_TYPES)}, got {self.loss_type!r}")
+        if self.loss_type == "dr_grpo" and (self.max_new_tokens is None or self.max_new_tokens < 1):
+            raise ValueError("loss_type 'dr_grpo' divides by max_new_tokens: set it")
+        if self.per_device_gamelog_size > self.rows:
+            raise ValueError("per_device_gamelog_size should be less than batch_size * num_generations")
+
+
+class VLGRPOTrainer(VLOnlineRLTrainer):
+    """The GRPO step on the HIP engine (include/vlr.h "GRPO"): every prompt gets G samples from ONE call of the model's generate
+    (num_return_sequences = G: one prefill per prompt, one decode batch), every sample one scalar reward, the advantage is the reward
+    standardised inside its group (vlr_grpo_advantages), and the loss is the clipped per-token surrogate plus beta times a per-token KL
+    estimate against the reference (vlr_grpo_loss).  The policy is a PLAIN family wrapper: no value head, no GAE, no whitening across
+    the batch.  The no-grad passes are run only when their numbers are read: the old log-probs when a step's rows see more than one
+    optimizer step (num_iterations > 1, or more rows than one backward batch) - otherwise the kernel takes NULL, the ratio is exactly 1
+    and the gradient still flows - and the reference log-probs when beta != 0 (the adapters switched off under LoRA, else a frozen copy).
+
+    Deliberate differences from trl's GRPOTrainer: the rows of a step are walked in generation order, never permuted; the image inputs
+    are expanded per row, so the vision tower runs again on a repeated image; no entropy statistics; no-grad passes in eval mode;
+    scores come from a reward model (VLRewardModel.score) or from `reward_fn(queries_text, responses_text) -> list of floats`;
+    world_size > 1 is refused: it has never been run."""
+
+    def __init__(self, config=None, model=None, ref_model=None, reward_model=None, processor=None, dataset=None, data_collator=None,
+                 generation_kwargs=None, reward_fn=None):
+        if config is None or model is None:
+            raise ValueError("VLGRPOTrainer needs a config and a model")
+        if hasattr(model, "v_head"):
+            raise ValueError("VLGRPOTrainer trains a plain family wrapper (LlavaForRL, QwenVLForRL): GRPO has no value head")
+        if int(getattr(config, "world_size", 1) or 1) > 1 or _world() > 1:
+            raise NotImplementedError("GRPO on more than one GPU has never been run on the MI355X path")
+        if reward_model is not None and reward_fn is not None:
+            raise ValueError("You can only use one of reward_model and reward_fn")
+        self._init_shared(config, model, reward_model, processor, dataset, data_collator, generation_kwargs)
+        self.reward_fn = reward_fn
+        if ref_model is None and not self.is_peft_model and config.beta != 0:
+            ref_model = model.create_reference_model()
+            ref_model.eval()
+        self.ref_model = ref_model
+        self._sample_gen = torch.Generator(device=self.accelerator.device).manual_seed(int(config.seed) + 2)      # the sampler's own stream
+        self.time_phases = False      # tools/grpo_bench.py: HIP events around the no-grad passes and the optimisation of step() -> last_timing
+        self.keep_rollout = False     # True: step() leaves its tensors in last_rollout (diagnostics, the tests)
+        self.last_rollout = None
+        model.engine.init_optimizer()
+
+    def _checkpoint_extra(self):
+        return dict(sample_generator=self._sample_gen.get_state().tolist(), num_generations=self.config.num_generations)
+
+    def _restore_extra(self, state, path):
+        if int(state.get("num_generations", self.config.num_generations)) != self.config.num_generations:
+            raise ValueError(f"resume_from_checkpoint: {path} was written with num_generations={state['num_generations']}, this run has "
+                             f"{self.config.num_generations}")
+        self._sample_gen.set_state(torch.tensor(state["sample_generator"], dtype=torch.uint8))
+
+    # ------------------------------------------------------------------------------------------ rows of a group
+    def _expand_queries(self, queries):
+        """the P queries as the P * G rows see them: row p * G + j carries query p"""
+        G = self.config.num_generations
+        return [queries[i // G] for i in range(len(queries) * G)]
+
+    def _expand_images(self, queries, img):
+        """the image inputs of P prompts -> those of the P * G rows, in repeat_interleave order (the rules of _rows_images)"""
+        if not img:
+            return {}
+        G = self.config.num_generations
+        T = max(int(q.numel()) for q in queries)
+        ids = torch.full((len(queries), T), -1, dtype=torch.long)
+        for p, q in enumerate(queries):
+            ids[p, :q.numel()] = q.reshape(-1).cpu().long()
+        return self._rows_images(ids, img, [p for p in range(len(queries)) for _ in range(G)])
+
+    # ------------------------------------------------------------------------------------------ sampling
+    @torch.no_grad()
+    def generate(self, queries, generation_kwargs=None, **img):
+        """ONE call of the model's own generate for all P queries: do_sample=True, num_return_sequences=G (one prefill per prompt, the
+        samples decoded as one batch over the shared prompt cache where the model has it), the adapters live under LoRA
+        (merge_lora=False).  -> P * G responses, row p * G + j being sample j of query p, each cut after its first stop."""
+        kw = dict(self.generation_kwargs)
+        kw.update(generation_kwargs or {})
+        kw.update(do_sample=True, num_return_sequences=self.config.num_generations)
+        if kw.get("generation_config") is not None:      # the model's generate reads do_sample from the generation config first: sample there too
+            kw["generation_config"] = gc = copy.copy(kw["generation_config"])
+            gc.do_sample, gc.num_return_sequences = True, self.config.num_generations
+        kw.setdefault("generator", self._sample_gen)
+        if self.config.max_new_tokens is not None:
+            kw.setdefault("max_new_tokens", int(self.config.max_new_tokens))
+        if self.is_peft_model:
+            kw.setdefault("merge_lora", False)
+        queries = [q.reshape(-1).cpu().long() for q in queries]
+        return self._generate_rows(queries, False, kw, img, fanout=self.config.num_generations)
+
+    def _clipped_frac(self, responses):
+        """fraction of the responses that ran to max_new_tokens without meeting a stop"""
+        limit = self.config.max_new_tokens
+        if limit is None:
+            limit = getattr(self.generation_kwargs.get("generation_config"), "max_new_tokens", None)
+        if limit is None:
+            return 0.0
+        eos, stops = self._stop_rules(self.model, self.generation_kwargs)
+        cut = 0
+        for r in responses:
+            row = r.reshape(-1).tolist()
+            stopped = row[-1] in eos or any(len(sq) <= len(row) and row[len(row) - len(sq):] == sq for sq in stops)
+            cut += int(len(row) >= int(limit) and not stopped)
+        return cut / len(responses)
+
+    # ------------------------------------------------------------------------------------------ scoring
+    def score(self, queries_text, responses_text, img):
+        """one score per (query, response) row: the reward function when one was given, else the reward model (compute_scores)"""
+        if self.reward_fn is not None:
+            scores = [float(x) for x in self.reward_fn(queries_text, responses_text)]
+            if len(scores) != len(responses_text):
+                raise ValueError(f"reward_fn returned {len(scores)} scores for {len(responses_text)} responses")
+            return scores
+        if self.reward_model is None:
+            raise NotImplementedError("GRPO needs a reward source: a reward_model (VLRewardModel) or a reward_fn")
+        return [float(x) for x in self.compute_scores(queries_text, responses_text, img)]
+
+    # ------------------------------------------------------------------------------------------ loop
+    def train(self, resume_from_checkpoint=None):
+        """per batch of P prompts: generate P * G responses, decode, score, step, log; a batch whose scoring raises is skipped;
+        config.save_steps > 0 writes a checkpoint every so many steps, resume_from_checkpoint continues one"""
+        if self.reward_fn is None and self.reward_model is None:
+            raise NotImplementedError("GRPO needs a reward source: a reward_model (VLRewardModel) or a reward_fn")
+        resume = resume_from_checkpoint or getattr(self.config, "resume_from_checkpoint", None)
+        skip = 0
+        if resume:
+            skip = int(self.load_checkpoint(resume).get("batches_seen", 0))
+        self.batches_seen = 0
+        for batch in self.get_batches():
+            self.batches_seen += 1
+            if self.batches_seen <= skip:      # the rows a resumed run has already consumed (the row order is part of the checkpoint)
+                continue
+            queries = batch["input_ids"]
+            img = {k: batch[k] for k in self.IMAGE_KEYS if k in batch}
+            responses = self.generate(queries, **img)
+            q_text = self._expand_queries(batch["query"])
+            r_text = self.tokenizer.batch_decode(responses, skip_special_tokens=True)
+            try:
+                scores = self.score(q_text, r_text, self._expand_images(queries, img))
+            except NotImplementedError:
+                raise
+            except Exception as e:      # as in PPO: warn, print the responses, skip the batch
+                print(f"[grpo] WARNING: error when computing reward score, skipping this batch: {e!r}\n{r_text}", flush=True)
+                self.skipped_batches = getattr(self, "skipped_batches", 0) + 1
+                continue
+            stats = self.step(queries, responses, scores, **img)
+            k = self.config.per_device_gamelog_size
+            game = [dict(query=self.processor.remove_image_placeholder(q), response=r, reward=float(s))
+                    for q, r, s in zip(q_text[:k], r_text[:k], scores[:k])]
+            self.log(dict(stats, game_log=game))
+            if self.config.save_steps and self.state.global_step % self.config.save_steps == 0:
+                self.save_checkpoint()
+        return self.log_history
+
+    # ------------------------------------------------------------------------------------------ step
+    def _nograd_logps(self, which, ids, mask, labels, img):
+        """token log-probs [R] of the policy ("old") or of the reference ("ref") on the response rows, under no-grad in eval mode"""
+        from .model import token_logps
+        dev = self.accelerator.device
+        args = (ids.to(dev), mask.to(dev), labels.to(dev))
+        if which == "old":
+            return token_logps(self.model, *args, **img)
+        if self.ref_model is None:
+            with self.model.disable_adapter():
+                return token_logps(self.model, *args, **img)
+        return token_logps(self.ref_model, *args, **img)
+
+    def step(self, queries, responses, scores, **img):
+        """one GRPO step over P queries, their P * G responses (row p * G + j: sample j of query p) and P * G scores -> the stats dict.
+        `img`: the image inputs of the P queries as the model's forward takes them; they are expanded per row and reach every pass."""
+        from .model import token_logps
+        cfg, model, eng, dev = self.config, self.model, self.model.engine, self.accelerator.device
+        P, G, N = len(queries), cfg.num_generations, len(responses)
+        if P != cfg.batch_size:
+            raise ValueError(f"step: {P} queries do not match config.batch_size {cfg.batch_size}")
+        if N != P * G or len(scores) != N:
+            raise ValueError(f"step: {P} queries x num_generations {G} need {P * G} responses and scores, got {N} and {len(scores)}")
+        ids, mask, labels = self._build_batch(self._expand_queries(queries), responses)
+        img = self._expand_images(queries, img)
+        mbs, bbs = cfg.mini_batch_size, cfg.backward_batch_size
+        lens = [int(r.numel()) for r in responses]      # every response token is a labelled row (the first stop included)
+        seq_off = [0]
+        for L in lens:
+            seq_off.append(seq_off[-1] + L)
+        need_old = cfg.num_iterations > 1 or N > bbs
+        need_ref = cfg.beta != 0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.time_phases else None
+        if ev:
+            ev[0].record()
+        # ---- no-grad passes: eval mode, in chunks of mini_batch_size rows, only the ones whose numbers are read
+        old_logp, ref_logp = None, None
+        if need_old or need_ref:
+            was_training = model.training
+            model.eval()
+            old, ref = [], []
+            try:
+                with torch.no_grad():
+                    for lo in range(0, N, mbs):
+                        rows = list(range(lo, min(lo + mbs, N)))
+                        i_, m_, l_, g_ = ids[rows], mask[rows], labels[rows], self._rows_images(ids, img, rows)
+                        if need_old:
+                            old.append(self._nograd_logps("old", i_, m_, l_, g_).clone())
+                        if need_ref:
+                            ref.append(self._nograd_logps("ref", i_, m_, l_, g_).clone())
+            finally:
+                model.train(was_training)
+            old_logp = torch.cat(old) if need_old else None
+            ref_logp = torch.cat(ref) if need_ref else None
+            for t in (old_logp, ref_logp):
+                if t is not None and t.numel() != seq_off[-1]:
+                    raise RuntimeError(f"step: {t.numel()} response rows for {seq_off[-1]} response tokens")
+        # ---- advantages: the scores standardised inside their groups
+        scores_t = torch.tensor([float(x) for x in scores], dtype=torch.float32, device=dev)
+        adv, astats = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(4, dtype=torch.float32, device=dev)
+        _hip.call("vlr_grpo_advantages", scores_t, P, G, int(bool(cfg.scale_rewards)), adv, astats)
+        if ev:
+            ev[1].record()
+        # ---- optimisation: num_iterations passes over the rows in generation order
+        was_training = model.training
+        model.train()
+        upstream = 1.0 / cfg.gradient_accumulation_steps
+        eps_high = cfg.epsilon if cfg.epsilon_high is None else cfg.epsilon_high
+        mcl = int(cfg.max_new_tokens) if cfg.max_new_tokens is not None else 0
+        mb_stats = []
+        try:
+            for _ in range(cfg.num_iterations):
+                for b0 in range(0, N, bbs):
+                    eng.zero_grad()
+                    for m0 in range(b0, b0 + bbs, mbs):
+                        rows = list(range(m0, m0 + mbs))
+                        t0, t1 = seq_off[m0], seq_off[m0 + mbs]
+                        so = torch.tensor([x - t0 for x in seq_off[m0:m0 + mbs + 1]], dtype=torch.int32, device=dev)
+                        logp = token_logps(model, ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), **self._rows_images(ids, img, rows))
+                        if logp.numel() != t1 - t0:
+                            raise RuntimeError(f"step: {logp.numel()} response rows for {t1 - t0} response tokens")
+                        dlogp = torch.empty_like(logp)
+                        st = torch.empty(8, dtype=torch.float32, device=dev)
+                        _hip.call("vlr_grpo_loss", logp.detach(), old_logp[t0:t1] if need_old else None, ref_logp[t0:t1] if need_ref else None,
+                                  adv[m0:m0 + mbs], so, t1 - t0, mbs, float(cfg.epsilon), float(eps_high), float(cfg.beta),
+                                  GRPO_LOSS_TYPES[cfg.loss_type], mcl, upstream, dlogp, st)
+                        logp.backward(dlogp)
+                        mb_stats.append(st)
+                    eng.optimizer_step(cfg.learning_rate, 0.9, 0.999, 1e-8, 0.0, cfg.max_grad_norm)
+        finally:
+            model.train(was_training)
+        if ev:
+            ev[2].record()
+            torch.cuda.synchronize()
+            self.last_timing = dict(nograd_ms=ev[0].elapsed_time(ev[1]), optimisation_ms=ev[1].elapsed_time(ev[2]))
+        # ---- stats: one device-to-host copy
+        flat = torch.cat([torch.stack(mb_stats).mean(0), astats]).tolist()
+        ms, a = flat[:8], flat[8:]
+        stats = {
+            "grpo/loss": ms[0], "grpo/kl": ms[1], "grpo/ratio": ms[5],
+            "grpo/clip_ratio/low": ms[2], "grpo/clip_ratio/high": ms[3], "grpo/clip_ratio/region": ms[4],
+            "grpo/reward_mean": a[0], "grpo/reward_std": a[1], "grpo/frac_reward_zero_std": a[2],
+            "grpo/clipped_completions_frac": self._clipped_frac(responses),
+            "tokens/queries_len_mean": sum(float(q.numel()) for q in queries) / P, "tokens/responses_len_mean": sum(lens) / N,
+            "grpo/learning_rate": float(cfg.learning_rate),
+        }
+        self.state.global_step += 1
+        if self.keep_rollout:
+            self.last_rollout = dict(old_logp=old_logp, ref_logp=ref_logp, seq_off=seq_off, advantages=adv, adv_stats=astats, minibatch_stats=mb_stats)
         return stats
 
 

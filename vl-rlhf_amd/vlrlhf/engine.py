@@ -1547,29 +1547,21 @@ class LlavaHipEngine:
             t = self._ws[("row_range",)] = torch.arange(max(n, 4096), dtype=torch.int32, device=self.dev)
         return t[:n]
 
-    def ppo_forward(self, ctx, labels, label_pad=-100):
-        """per-token log-probs and values on the R response rows (the rows whose logits predict a label != label_pad; trl reads
-        values[:, :-1] under the same mask): the fused lm-head of logps_forward(reduce_seq=False) and vlr_rm_head_fwd with the value
-        head on the same gathered rows.  Returns (tok_logp [R] fp32, values [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the sequences."""
+    def token_logps_forward(self, ctx, labels, label_pad=-100):
+        """per-token log-probs on the R response rows (the rows whose logits predict a label != label_pad): the fused lm-head of
+        logps_forward(reduce_seq=False).  Needs no value head.  Returns (tok_logp [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the
+        sequences."""
         _, lp = self.logps_forward(ctx, labels, None, False, label_pad, reduce_seq=False)
-        R = lp["R"]
-        if R == 0:
-            raise ValueError("ppo_forward: no response token in this (mini)batch - every label is the padding label")
-        w, b, _, _ = self.v_head_views()
-        values = torch.empty(R, dtype=torch.float32, device=self.dev)
-        _hip.call("vlr_rm_head_fwd", lp["hg"], self.H, self._row_range(R), w, b, values, R, self.H)
-        return lp["tok"], values, lp
+        if lp["R"] == 0:
+            raise ValueError("token_logps_forward: no response token in this (mini)batch - every label is the padding label")
+        return lp["tok"], lp
 
-    def ppo_backward(self, lp, dlogp, dvalues):
-        """d tok_logp [R], d values [R] -> d hidden (dense [M,H], zero outside the response rows), the lm_head weight gradient (full
-        fine-tune) and the value head's gradients.  The lm-head backward is logps_backward's with every row its own sequence; the value
-        head adds g_r * w onto the same gathered d hg before the scatter (vlr_v_head_bwd)."""
+    def _token_logps_dhg(self, lp, dlogp):
+        """d tok_logp [R] -> the gathered d hg [R][H] and the lm_head weight gradient (full fine-tune): logps_backward's lm-head backward
+        with every row its own sequence, then the two lm-head GEMMs"""
         ctx = lp["ctx"]
-        M, H, V, R = ctx["M"], self.H, self.V, lp["R"]
-        if R == 0:
-            raise ValueError("ppo_backward: no response token in this (mini)batch")
+        H, V, R = self.H, self.V, lp["R"]
         acc = int(not self.grad_fresh)
-        dhidden = torch.zeros(M, H, dtype=BF16, device=self.dev)
         fused = bool(_hip.helper("vlr_lmhead_is_fused", R, V, H))
         lws = self._buf(("lmhead_ws", ctx["tag"], R), (int(_hip.lib().vlr_lmhead_workspace_bytes(R, V)),), torch.uint8)
         logits = None if fused else self._buf(("logits", ctx["tag"], R), (R, V), torch.float32)
@@ -1580,13 +1572,47 @@ class LlavaHipEngine:
         _hip.call("vlr_gemm_bf16", 1, dl, ctx["ws"].v["lm_head"], dhg, None, None, R, H, V, V, H, H, 0, 0, 0, 0)
         if self.lora is None:                 # under LoRA the lm_head is frozen (not a target module)
             _hip.call("vlr_gemm_bf16", 2, dl, lp["hg"], self.gv["lm_head"], None, None, V, H, R, V, H, H, 0, 0, acc, 0)
-        w, _, gw, gb = self.v_head_views()
-        vws = self._buf(("v_head_ws", R), (int(_hip.lib().vlr_v_head_bwd_workspace_bytes(R, H)),), torch.uint8)
-        _hip.call("vlr_v_head_bwd", lp["hg"], w, dvalues.to(torch.float32).contiguous(), dhg, gw, gb, acc, vws, R, H)
-        _hip.call("vlr_scatter_rows", dhg, lp["rows"], dhidden, R, H)
+        return dhg
+
+    def _scatter_dhg(self, lp, dhg, dhidden):
+        """the gathered d hg onto its rows of the dense d hidden, then the reducer hears of the lm_head bucket"""
+        _hip.call("vlr_scatter_rows", dhg, lp["rows"], dhidden, lp["R"], self.H)
         if self.reducer is not None and self.lora is None:
             self.reducer.bucket_ready("lm_head")
         return dhidden
+
+    def token_logps_backward(self, lp, dlogp):
+        """d tok_logp [R] -> d hidden (dense [M,H], zero outside the response rows) and the lm_head weight gradient (full fine-tune)"""
+        if lp["R"] == 0:
+            raise ValueError("token_logps_backward: no response token in this (mini)batch")
+        dhidden = torch.zeros(lp["ctx"]["M"], self.H, dtype=BF16, device=self.dev)
+        return self._scatter_dhg(lp, self._token_logps_dhg(lp, dlogp), dhidden)
+
+    def ppo_forward(self, ctx, labels, label_pad=-100):
+        """per-token log-probs and values on the R response rows (the rows whose logits predict a label != label_pad; trl reads
+        values[:, :-1] under the same mask): token_logps_forward and vlr_rm_head_fwd with the value head on the same gathered rows.
+        Returns (tok_logp [R] fp32, values [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the sequences."""
+        tok, lp = self.token_logps_forward(ctx, labels, label_pad)
+        R = lp["R"]
+        w, b, _, _ = self.v_head_views()
+        values = torch.empty(R, dtype=torch.float32, device=self.dev)
+        _hip.call("vlr_rm_head_fwd", lp["hg"], self.H, self._row_range(R), w, b, values, R, self.H)
+        return tok, values, lp
+
+    def ppo_backward(self, lp, dlogp, dvalues):
+        """d tok_logp [R], d values [R] -> d hidden (dense [M,H], zero outside the response rows), the lm_head weight gradient (full
+        fine-tune) and the value head's gradients.  The lm-head backward is token_logps_backward's; the value head adds g_r * w onto the
+        same gathered d hg before the scatter (vlr_v_head_bwd)."""
+        R, H = lp["R"], self.H
+        if R == 0:
+            raise ValueError("ppo_backward: no response token in this (mini)batch")
+        acc = int(not self.grad_fresh)
+        dhidden = torch.zeros(lp["ctx"]["M"], H, dtype=BF16, device=self.dev)
+        dhg = self._token_logps_dhg(lp, dlogp)
+        w, _, gw, gb = self.v_head_views()
+        vws = self._buf(("v_head_ws", R), (int(_hip.lib().vlr_v_head_bwd_workspace_bytes(R, H)),), torch.uint8)
+        _hip.call("vlr_v_head_bwd", lp["hg"], w, dvalues.to(torch.float32).contiguous(), dhg, gw, gb, acc, vws, R, H)
+        return self._scatter_dhg(lp, dhg, dhidden)
 
     def logits_mean(self, ctx, lo, hi):
         """mean over [lo:hi] sequences, all positions, all vocabulary entries of the logits = mean_rows(h . sum_v W_v)/V

@@ -16,10 +16,10 @@ from ... import _hip, gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine import BF16, LlavaHipEngine, WeightSet
 from ...utils.common import flatten_list
-from ..utils import ModelCoreMapper, PPOCore
+from ..utils import GRPOCore, ModelCoreMapper, PPOCore
 
 
 @dataclass
@@ -246,6 +246,7 @@ def stop_hit(generated, stops):
 
 class LlavaForRL(nn.Module):
     engine_cls = LlavaHipEngine
+    image_count_key = "image_token"      # engine cfg key of the id that marks one image in input_ids (the online-RL trainers cut image inputs by it)
 
     def __init__(self, cfg: dict, engine: Optional[LlavaHipEngine] = None, weights: Optional[WeightSet] = None,
                  trainable: bool = True):
@@ -956,6 +957,14 @@ class LlavaPPOTrainer(VLPPOTrainer):
 
 # The PPO record of this package.  ModelCoreMapper's value_model / ppo_collator / ppo_trainer slots stay None (models/utils.py says why).
 ppo_core = PPOCore(value_model=LlavaWithValueHead, collator=LlavaPPODataCollator, trainer=LlavaPPOTrainer)
+
+
+class LlavaGRPOTrainer(VLGRPOTrainer):
+    ...
+
+
+# The GRPO record: the policy is the plain wrapper, the queries are collated as PPO's are.
+grpo_core = GRPOCore(model=LlavaForRL, collator=LlavaPPODataCollator, trainer=LlavaGRPOTrainer)
 
 
 core_mapper = ModelCoreMapper(

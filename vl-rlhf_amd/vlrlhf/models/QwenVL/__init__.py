@@ -18,11 +18,11 @@ from ... import gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine_qwen import QwenVLHipEngine
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
-from ..utils import ModelCoreMapper, PPOCore
+from ..utils import GRPOCore, ModelCoreMapper, PPOCore
 
 IGNORE_TOKEN_ID = -100           # transformers LabelSmoother.ignore_index
 
@@ -85,6 +85,7 @@ def load_qwen_pixel_values(items, image_size: int = 448) -> torch.Tensor:
 
 class QwenVLForRL(LlavaForRL):
     engine_cls = QwenVLHipEngine
+    image_count_key = "image_start_id"
 
     def __init__(self, cfg: dict, engine=None, weights=None, trainable: bool = True):
         super().__init__(dict(cfg, family="qwen_vl"), engine=engine, weights=weights, trainable=trainable)
@@ -451,6 +452,14 @@ class QwenVLPPOTrainer(VLPPOTrainer):
 
 # The PPO record of this package.  ModelCoreMapper's value_model / ppo_collator / ppo_trainer slots stay None (models/utils.py says why).
 ppo_core = PPOCore(value_model=QwenVLWithValueHead, collator=QwenVLPPODataCollator, trainer=QwenVLPPOTrainer)
+
+
+class QwenVLGRPOTrainer(VLGRPOTrainer):
+    ...
+
+
+# The GRPO record: the policy is the plain wrapper, the queries are collated as PPO's are.
+grpo_core = GRPOCore(model=QwenVLForRL, collator=QwenVLPPODataCollator, trainer=QwenVLGRPOTrainer)
 
 
 core_mapper = ModelCoreMapper(

@@ -30,3 +30,11 @@ class PPOCore:
     value_model: Any
     collator: Any = None
     trainer: Any = None
+
+
+@dataclass
+class GRPOCore:
+    """GRPO's record (`grpo_core`, resolved by utils/auto_load.py GRPO_FAMILIES / MyAutoGRPOTrainer): the policy is the plain wrapper"""
+    model: Any
+    collator: Any = None
+    trainer: Any = None

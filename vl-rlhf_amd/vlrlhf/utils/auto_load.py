@@ -124,6 +124,27 @@ class MyAutoPPOCollator:
         return _ppo_slot(_architecture(model_name_or_path), "collator")(processor)
 
 
+GRPO_FAMILIES = ["Llava", "QwenVL"]      # the families whose plain wrapper samples several rows per prompt and has a reward model
+
+
+def _grpo_slot(architecture: str, slot: str):
+    """the GRPO record of a model package (`grpo_core`, models/utils.py GRPOCore)"""
+    nick = MODEL_NICKNAME_MAP[architecture]
+    if nick not in GRPO_FAMILIES:
+        raise NotImplementedError(f"{nick}: GRPO on the MI355X path covers {GRPO_FAMILIES} (LLaVA-1.5 and Qwen-VL) only")
+    return getattr(import_module(f".{nick}", "vlrlhf.models").grpo_core, slot)
+
+
+class MyAutoGRPOTrainer:
+    def __new__(cls, model_name_or_path, *args, **kwargs):
+        return _grpo_slot(_architecture(model_name_or_path), "trainer")(*args, **kwargs)
+
+
+class MyAutoGRPOCollator:
+    def __new__(cls, model_name_or_path, processor=None):
+        return _grpo_slot(_architecture(model_name_or_path), "collator")(processor)
+
+
 class MyAutoGenerationConfig:
     @classmethod
     def from_pretrained(cls, model_name_or_path):
