@@ -121,6 +121,24 @@ int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void* wgu, void
                          vlr_stream_t stream);
 int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
                       int peel_rows, int tail_row0, vlr_stream_t stream);
+/* The two fused products with OUTPUT ROW MAPS (additive: vlr_abi_version() does not move): what the epilogue computed for logical row m
+ * is stored at row c_rows[m] of the destination and, where c_twin[m] >= 0, at row c_twin[m] too - the same registers, one rounding.
+ * c_rows, c_twin: M device int32 each, valid destination rows (c_twin: or -1), not checked; no two logical rows may name the same
+ * destination row.  Destination rows that no entry names are not written.  pos, the bias and the rotation stay indexed by the logical
+ * row.  a_rows: an A-side map as above, or NULL (x read in place).  Launches, kernels, K order and values are those of
+ * vlr_gemm_qkv_rope_bias[_rows] / vlr_gemm_swiglu[_rows]: the result equals theirs followed by vlr_gather_rows, bit for bit.
+ * vlr_gemm_swiglu_dst: act alone goes through the maps (act_dst [.][I]); gate | up (store_gu) are written on the M logical rows of gu.
+ * Its mapped kernel exists with an A-side map only.
+ * Shapes the fused persistent kernel does not take (head_dim != 128, widths off its tiles, K < 256, unaligned operands; for SwiGLU also
+ * a_rows == NULL) fall back: the unmapped product into qkv_rows / act_rows [M rows], then vlr_gather_rows through dense_src [Md] (for
+ * every destination row the logical row that holds its value) into the Md destination rows - the fallback needs these three and an
+ * unmapped x, and reports an error without them.  The destination must not be x, gu or the fallback buffer. */
+int vlr_gemm_qkv_rope_bias_dst(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv_dst, const int* c_rows,
+                               const int* c_twin, void* qkv_rows, const int* dense_src, int Md, const int* pos, const float* cos_t,
+                               const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim, int max_pos,
+                               vlr_stream_t stream);
+int vlr_gemm_swiglu_dst(const void* x, const int* a_rows, const void* wgu, void* gu, void* act_dst, const int* c_rows, const int* c_twin,
+                        void* act_rows, const int* dense_src, int Md, int M, int I, int K, int ldx, int store_gu, vlr_stream_t stream);
 /* The same projections with the LoRA adapters of the group riding the K loop of the base GEMM (peft lora.Linear.forward,
  * result = base(x) + lora_B(lora_A(dropout(x))) * scaling; reference targets src/vlrlhf/models/Llava/__init__.py:273-286):
  * after the K tiles of x . W^T the kernel runs on into u . Bl^T, u [M][ldu] = scaling * dropout_t(x) A_t^T of the group's
@@ -568,6 +586,14 @@ int vlr_decoder_layer_fwd_compact_ex(const vlr_llama_cfg* cfg, const vlr_layer_w
                                      const int* pos_compact, const int* dense_src, const int* compact_rows, int Mc, int tail_rows,
                                      void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S, int keep_for_backward,
                                      vlr_stream_t stream);
+/* The same pass with the maps as a struct.  Where m->twin is given and the fused kernels take every row of the layer's shapes (head_dim
+ * 128, the 7B widths) the q|k|v + RoPE epilogue stores each kept row straight to its row of qkv_dense and a shared row to its dropped
+ * copy's too (vlr_gemm_qkv_rope_bias_dst): no row copy rebuilds the dense q|k|v and a->qkv is not written.  Elsewhere, and with
+ * m->twin == NULL, it is vlr_decoder_layer_fwd_compact_ex call for call.  Every value written equals that function's, bit for bit.
+ * m->dense_own is not read.  keep_for_backward = 0: the no-grad reference pass (vlr_decoder_layer_fwd_compact). */
+int vlr_decoder_layer_fwd_compact_maps(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a, const void* x_in,
+                                       const vlr_row_maps* m, void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S,
+                                       int keep_for_backward, vlr_stream_t stream);
 /* The activations that pass left on Mc rows (`c`), copied to the dense layout (`d`: batch * S = M rows) through dense_src, so that the
  * unchanged vlr_decoder_layer_bwd runs on `d` and computes what it computes after a dense forward - the same bits wherever
  * vlr_decoder_layer_compact_exact says 1.  Copied: x_out, and with keep_for_backward = 1 also xn1, rstd1, x_mid, xn2, rstd2, gu, act.
@@ -596,12 +622,14 @@ int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weig
  * src[dense_src[m]] instead.
  * vlr_decoder_layer_fwd_compact_keep: vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1) writing
  *   - rstd1, x_mid, rstd2, gu, x_out on Mc rows into the layer's own set `a` (never copied),
- *   - xn1, xn2 straight to the M dense rows of `a` (vlr_rmsnorm_fwd_scatter; the fused projections read them through compact_rows) where
- *     the fused kernels take every row of the layer's shapes - elsewhere on Mc rows into `s` and copied through m->dense_src,
- *   - act on Mc rows into `s`, then copied to the M dense rows of `a` (with xn1, xn2 the K-side operands of the weight-gradient GEMMs),
- *   - q|k|v and attn densely into a->qkv / a->attn (s->qkv and s->attn take the Mc-row forms), lse into a->lse.
- * o_proj reads the dense attention rows through compact_rows where the persistent kernel takes it.  Of `s` only xn1, qkv, attn, xn2, act
- * are used; none of them may be the same buffer as its namesake in `a`.  m->dense_own is not read.
+ *   - xn1, xn2, act (the K-side operands of the weight-gradient GEMMs) and q|k|v straight to the M dense rows of `a` where the fused
+ *     kernels take every row of the layer's shapes: the scatter norms (vlr_rmsnorm_fwd_scatter) and the output maps of the two fused
+ *     epilogues (vlr_gemm_qkv_rope_bias_dst, vlr_gemm_swiglu_dst) store a shared row to both of its dense rows, the projections read
+ *     xn1 / xn2 through compact_rows and down_proj reads act the same way (vlr_gemm_res_rows).  No row is copied; s->xn1, s->qkv,
+ *     s->xn2 and s->act are NOT written on this route,
+ *   - elsewhere (toy widths; act also where down_proj cannot take the map) on Mc rows into `s` and copied through m->dense_src,
+ *   - attn densely into a->attn (s->attn takes the Mc-row form where o_proj cannot read the dense rows), lse into a->lse.
+ * Of `s` only xn1, qkv, attn, xn2, act are ever used; none of them may be the same buffer as its namesake in `a`.  m->dense_own is not read.
  * vlr_decoder_layer_bwd_src: vlr_decoder_layer_bwd call for call, in the same order, at M = batch * S rows, on such a set.  x_in holds
  * the KEPT rows of the layer's input (the previous layer's a->x_out, or the embedding rows gathered through compact_rows); both norm
  * backwards are the _src forms over src_rows = dense_src; the SwiGLU backward is vlr_gemm_swiglu_bwd_src into dgu [M][2I], a scratch

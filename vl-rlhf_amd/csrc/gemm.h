@@ -108,6 +108,13 @@ struct GemmParams {
     // row a_rows[m] of the buffer at A (M device ints, not checked; rows may repeat).  Read once per piece at tile setup and on the general
     // staging path (K tail, the next piece's first K tiles) - never in the steady-state K loop.  NULL: A is read in place.
     const int* a_rows;
+    // ---- output-side row maps of the fuse = 1 | 2 epilogues (template CROWS of gemm256p_kernel): logical output row m is stored at row
+    // c_rows[m] of the destination and, where c_twin[m] >= 0, at row c_twin[m] too - the same registers, the same single rounding (M device
+    // ints each, valid destination rows, not checked).  fuse = 2: C; fuse = 1: C2 (act) alone - gate | up (C) stay on the logical rows.
+    // pos, bias and the rotation stay indexed by the logical row.  Read once per output tile, one integer per lane and map.  NULL (both):
+    // stored in place.
+    const int* c_rows;
+    const int* c_twin;
 #ifdef VLR_GEMM_TRACE
     uint32_t* trace;         // diagnostics build only: set by the launchers of gemm256p.hip (vlr_gemm_set_trace), never by callers
     int epi_abl, trace_clk;

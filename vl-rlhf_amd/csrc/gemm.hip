@@ -703,6 +703,14 @@ struct ARowsScope {
     ARowsScope(const int* r, int tail0, int peel) { t_a_rows = r; t_a_tail0 = tail0; t_peel_rows = peel; }
     ~ARowsScope() { t_a_rows = nullptr; t_a_tail0 = -1; t_peel_rows = -1; }
 };
+// != NULL: the fused q|k|v + RoPE / gate|up + SwiGLU launches of this thread store through these output row maps (GemmParams::c_rows /
+// c_twin: q|k|v, or act, of logical row m lands at destination row t_c_rows[m] and, where t_c_twin[m] >= 0, at t_c_twin[m] too)
+static thread_local const int* t_c_rows = nullptr;
+static thread_local const int* t_c_twin = nullptr;
+struct CRowsScope {
+    CRowsScope(const int* r, const int* tw) { t_c_rows = r; t_c_twin = tw; }
+    ~CRowsScope() { t_c_rows = nullptr; t_c_twin = nullptr; }
+};
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st) {
     t_peel_rows = peel_rows;
@@ -831,6 +839,7 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     p.A1 = p.B1 = nullptr; p.C1 = nullptr; p.M1 = p.N1 = p.lda1 = p.ldb1 = p.ldc1 = 0;
     p.groups = 1; p.gA = p.gB = p.gC = 0; p.mask_on = 0; p.mask_seed = 0; p.mask_thr = 0; p.mask_ld = 0;
     p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0; p.a_rows = nullptr;
+    p.c_rows = nullptr; p.c_twin = nullptr;
     const int pi = vlr_prof_begin(layout, 2.0 * M * N * K, stream);
     if (t_a_rows) {       // A through a row map (vlr_gemm_res_rows): the persistent kernel for all rows but the caller-named peeled ones
         const int pr = t_peel_rows > 0 ? t_peel_rows : 0;
@@ -930,6 +939,7 @@ static GemmParams fused_params(const void* A, const void* B, void* C, int M, int
     p.A1 = p.B1 = nullptr; p.C1 = nullptr; p.M1 = p.N1 = p.lda1 = p.ldb1 = p.ldc1 = 0;
     p.groups = 1; p.gA = p.gB = p.gC = 0; p.mask_on = 0; p.mask_seed = 0; p.mask_thr = 0; p.mask_ld = 0;
     p.mask_bits = nullptr; p.gMask = 0; p.drop_bits = nullptr; p.rowskip = nullptr; p.ktlist = nullptr; p.seg_skip = nullptr; p.seg_keep = 0; p.a_rows = nullptr;
+    p.c_rows = nullptr; p.c_twin = nullptr;
     return p;
 }
 
@@ -993,6 +1003,8 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
     p.fuse = 1; p.store_c = store_gu; p.C2 = act; p.ldc2 = I;
     VLR_REQUIRE(!t_a_rows || !seg, "vlr_gemm_swiglu: no row map on a launch with an adapter segment");
     p.a_rows = t_a_rows;
+    VLR_REQUIRE(!t_c_rows || !seg, "vlr_gemm_swiglu: no output row map on a launch with an adapter segment");
+    p.c_rows = t_c_rows; p.c_twin = t_c_twin;
     seg_set(p, sg, &skp, 0);
     int done = 0;
     const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * M1 * 2 * I * K, stream);    // per-layout totals of the bench line (the fallback rows below are counted by gemm_impl)
@@ -1009,6 +1021,7 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
         GemmParams p2 = fused_params((const bf16_t*)x + (size_t)done * ldx, wgu, (bf16_t*)gu + (size_t)done * 2 * I, M - done, 2 * I, K, ldx, K, 2 * I);
         p2.fuse = 1; p2.store_c = store_gu; p2.C2 = (bf16_t*)act + (size_t)done * I; p2.ldc2 = I;
         if (t_a_rows) { p2.A = (const bf16_t*)x; p2.a_rows = t_a_rows + done; }
+        if (t_c_rows) { p2.C2 = act; p2.c_rows = t_c_rows + done; p2.c_twin = t_c_twin + done; }
         if (seg) { SegArgs s2 = *sg; s2.u = (const bf16_t*)sg->u + (size_t)done * sg->ldu; seg_set(p2, &s2, &skp, done); }
         const int pj_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * (M - done) * 2 * I * K, stream);
         const bool took2_ = seg ? vlr_gemm256p_seg_try_launch(p2, stream) : vlr_gemm256p_fused_try_launch(p2, stream);
@@ -1019,7 +1032,7 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu, void* act,
             done = M;
         }
     }
-    VLR_REQUIRE(done == M || !t_a_rows, "vlr_gemm_swiglu_rows: the fused kernel does not take M=%d I=%d K=%d with a row map", M, I, K);
+    VLR_REQUIRE(done == M || (!t_a_rows && !t_c_rows), "vlr_gemm_swiglu_rows: the fused kernel does not take M=%d I=%d K=%d with a row map", M, I, K);
     if (done < M) {       // remaining rows: plain GEMM (+ the adapter GEMMs) + SwiGLU kernel
         const bf16_t* xa = (const bf16_t*)x + (size_t)done * ldx;
         bf16_t* gur = (bf16_t*)gu + (size_t)done * 2 * I;
@@ -1065,6 +1078,8 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
         p.bias = (const bf16_t*)bias;
         VLR_REQUIRE(!t_a_rows || !seg, "vlr_gemm_qkv_rope: no row map on a launch with an adapter segment");
         p.a_rows = t_a_rows;
+        VLR_REQUIRE(!t_c_rows || !seg, "vlr_gemm_qkv_rope: no output row map on a launch with an adapter segment");
+        p.c_rows = t_c_rows; p.c_twin = t_c_twin;
         seg_set(p, sg, &skp, 0);
         const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * M1 * N * K, stream);
         const bool took_ = seg ? vlr_gemm256p_seg_try_launch(p, stream) : vlr_gemm256p_fused_try_launch(p, stream);
@@ -1080,6 +1095,7 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
         p2.fuse = 2; p2.pos = pos + done; p2.rope_cos = cos_t; p2.rope_sin = sin_t; p2.max_pos = max_pos; p2.rope_cols = rope_cols;
         p2.bias = (const bf16_t*)bias;
         if (t_a_rows) { p2.A = (const bf16_t*)x; p2.a_rows = t_a_rows + done; }
+        if (t_c_rows) { p2.C = qkv; p2.c_rows = t_c_rows + done; p2.c_twin = t_c_twin + done; }
         if (seg) { SegArgs s2 = *sg; s2.u = (const bf16_t*)sg->u + (size_t)done * sg->ldu; seg_set(p2, &s2, &skp, done); }
         const int pj_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * (M - done) * N * K, stream);
         const bool took2_ = seg ? vlr_gemm256p_seg_try_launch(p2, stream) : vlr_gemm256p_fused_try_launch(p2, stream);
@@ -1090,7 +1106,7 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv, const 
             done = M;
         }
     }
-    VLR_REQUIRE(done == M || !t_a_rows, "vlr_gemm_qkv_rope_rows: the fused kernel does not take M=%d N=%d K=%d with a row map", M, N, K);
+    VLR_REQUIRE(done == M || (!t_a_rows && !t_c_rows), "vlr_gemm_qkv_rope_rows: the fused kernel does not take M=%d N=%d K=%d with a row map", M, N, K);
     if (done < M) {
         bf16_t* qr = (bf16_t*)qkv + (size_t)done * N;
         int rc = gemm_impl(0, (const bf16_t*)x + (size_t)done * ldx, wqkv, qr, bias, nullptr, M - done, N, K, ldx, K, N, 0, 0, 0, 0, 1.0f, stream);
@@ -1125,6 +1141,53 @@ extern "C" int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void
     VLR_REQUIRE(a_rows, "vlr_gemm_swiglu_rows: null row map");
     const ARowsScope scope(a_rows, -1, -1);
     return gemm_swiglu_impl(x, wgu, gu, act, M, I, K, ldx, store_gu, nullptr, stream);
+}
+// The two fused forward products with OUTPUT row maps (include/vlr.h): q|k|v, or act, of logical row m is stored at row c_rows[m] of the
+// destination and, where c_twin[m] >= 0, at row c_twin[m] too - the launches, kernels and values of the entry points above, only the
+// address of a store differs.  Shapes the fused kernel does not take: the unmapped call into `*_rows` [M rows] and vlr_gather_rows
+// through dense_src into the Md destination rows.
+extern "C" int vlr_gather_rows(const void* src, const int* idx, void* dst, int M, int N, hipStream_t stream);
+int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
+extern "C" int vlr_gemm_qkv_rope_bias_dst(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv_dst, const int* c_rows,
+                                          const int* c_twin, void* qkv_rows, const int* dense_src, int Md, const int* pos, const float* cos_t,
+                                          const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim, int max_pos,
+                                          hipStream_t stream) {
+    VLR_REQUIRE(x && wqkv && qkv_dst, "vlr_gemm_qkv_rope_bias_dst: null operand");
+    VLR_REQUIRE(c_rows && c_twin, "vlr_gemm_qkv_rope_bias_dst: null output row map");
+    VLR_REQUIRE(qkv_dst != x && qkv_dst != qkv_rows, "vlr_gemm_qkv_rope_bias_dst: the destination must not be the source or the fallback rows");
+    VLR_REQUIRE(M > 0 && N > 0 && K > 0 && ldx > 0, "vlr_gemm_qkv_rope_bias_dst: bad shape M=%d N=%d K=%d", M, N, K);
+    const bool takes = head_dim == 128 && (!bias || !((uintptr_t)bias & 7)) && vlr_internal_gemm256p_fused_takes(2, N, K, rope_cols) &&
+                       !(((uintptr_t)x | (uintptr_t)wqkv | (uintptr_t)qkv_dst) & 15) && ldx % 8 == 0 && N % 8 == 0;
+    if (takes) {
+        const ARowsScope scope(a_rows, -1, -1);
+        const CRowsScope cscope(c_rows, c_twin);
+        return gemm_qkv_rope_impl(x, wqkv, qkv_dst, pos, cos_t, sin_t, M, N, rope_cols, K, ldx, head_dim, max_pos, nullptr, bias, stream);
+    }
+    VLR_REQUIRE(qkv_rows && dense_src && Md > 0 && !a_rows, "vlr_gemm_qkv_rope_bias_dst: the fused kernel does not take M=%d N=%d K=%d: the fallback "
+                "needs qkv_rows, dense_src and an unmapped x", M, N, K);
+    int rc = gemm_qkv_rope_impl(x, wqkv, qkv_rows, pos, cos_t, sin_t, M, N, rope_cols, K, ldx, head_dim, max_pos, nullptr, bias, stream);
+    if (rc != VLR_OK) return rc;
+    return vlr_gather_rows(qkv_rows, dense_src, qkv_dst, Md, N, stream);
+}
+// act through the maps; gate | up (store_gu) stay on the M logical rows of gu.  The mapped kernel exists with an A-side map only
+extern "C" int vlr_gemm_swiglu_dst(const void* x, const int* a_rows, const void* wgu, void* gu, void* act_dst, const int* c_rows, const int* c_twin,
+                                   void* act_rows, const int* dense_src, int Md, int M, int I, int K, int ldx, int store_gu, hipStream_t stream) {
+    VLR_REQUIRE(x && wgu && gu && act_dst, "vlr_gemm_swiglu_dst: null operand");
+    VLR_REQUIRE(c_rows && c_twin, "vlr_gemm_swiglu_dst: null output row map");
+    VLR_REQUIRE(act_dst != x && act_dst != gu && act_dst != act_rows, "vlr_gemm_swiglu_dst: the destination must not be the source, gate | up or the fallback rows");
+    VLR_REQUIRE(M > 0 && I > 0 && K > 0 && ldx > 0, "vlr_gemm_swiglu_dst: bad shape M=%d I=%d K=%d", M, I, K);
+    const bool takes = a_rows && I % 8 == 0 && vlr_internal_gemm256p_fused_takes(1, 2 * I, K, 0) &&
+                       !(((uintptr_t)x | (uintptr_t)wgu | (uintptr_t)gu | (uintptr_t)act_dst) & 15) && ldx % 8 == 0;
+    if (takes) {
+        const ARowsScope scope(a_rows, -1, -1);
+        const CRowsScope cscope(c_rows, c_twin);
+        return gemm_swiglu_impl(x, wgu, gu, act_dst, M, I, K, ldx, store_gu, nullptr, stream);
+    }
+    VLR_REQUIRE(act_rows && dense_src && Md > 0 && !a_rows, "vlr_gemm_swiglu_dst: the fused kernel does not take M=%d I=%d K=%d: the fallback needs "
+                "act_rows, dense_src and an unmapped x", M, I, K);
+    int rc = gemm_swiglu_impl(x, wgu, gu, act_rows, M, I, K, ldx, store_gu, nullptr, stream);
+    if (rc != VLR_OK) return rc;
+    return vlr_gather_rows(act_rows, dense_src, act_dst, Md, I, stream);
 }
 // y [M][N] (fp32 when f32, else bf16) = a W^T + res: the residual projection (vlr_gemm_bf16 / vlr_gemm_bf16_f32res, NT, lda = ldb = K,
 // ldc = ldr = N).  peel_rows > 0: the LAST peel_rows logical rows go to the 128x128 split-K kernel and must stand as one contiguous run of

@@ -348,9 +348,11 @@ struct TileProb { const bf16_t* A; const bf16_t* B; void* C; int M, N, lda, ldb,
 // as one list of output tiles, the first problem's tiles first: the weight gradients of gate|up and down_proj are 5.375 + 2.69 rounds
 // of 256 tiles as two launches (6 + 3) and 8.06 as one (the host peels one tile row to the 128x128 kernel: 8).
 // AROWS: the K-contiguous A operand is read through GemmParams::a_rows (instantiations of their own: the unmapped kernels carry no test)
-template <bool A_KS, bool B_KS, int ABL = 0, bool CONT = false, int FUSE = 0, bool SEG = false, bool GRP = false, bool AROWS = false>
+// CROWS: the fuse = 1 | 2 epilogues store through GemmParams::c_rows / c_twin (again instantiations of their own)
+template <bool A_KS, bool B_KS, int ABL = 0, bool CONT = false, int FUSE = 0, bool SEG = false, bool GRP = false, bool AROWS = false, bool CROWS = false>
 __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_t* __restrict__ zero16) {
     static_assert(!AROWS || (!A_KS && !SEG && !GRP), "row map: K-contiguous A, no adapter segment, one problem");
+    static_assert(!CROWS || (CONT && (FUSE == 1 || FUSE == 2) && !SEG), "output row maps: the SwiGLU and RoPE epilogues, no adapter segment");
     static_assert(!GRP || (A_KS && B_KS && CONT && FUSE == 0 && !SEG), "grouped launches: TN, plain epilogue");
     static_assert(FUSE == 0 || (FUSE == 6 && !CONT && !A_KS && B_KS) || (FUSE != 6 && CONT && !A_KS && (FUSE == 3 || FUSE == 7 ? B_KS : !B_KS)),
                   "fused epilogues: continuous pipeline; 1, 2, 4, 5 NT, 3, 7 NN; 6 (dropout-accumulate) NN on the LDS-image epilogue");
@@ -916,6 +918,19 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
         const int I = tp.N >> 1;
         // chunk n = (row block r = (a, i), kind): kind 0 act, 1 gate, 2 up (NK = 1: act only - the no-grad passes); chunk n is put while
         // chunk n - 1 comes back from the patch (EPI_BF16_PUT)
+        // CROWS: the wave's rows of A half a are 64 consecutive logical rows - lane l loads the destination rows of row l of both halves
+        // once per tile, before the tile's first store (a load behind stores would wait for them: vmcnt counts in order), and a chunk
+        // fetches the pair of its row (i * 16 + lane / 4) through the LDS crossbar.  Four registers, no address is carried.
+        int crow[2] = {0, 0}, ctwin[2] = {-1, -1};
+        if constexpr (CROWS) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                int g = m0 + a * 128 + wr * 64 + lane;
+                g = g < tp.M ? g : tp.M - 1;
+                crow[a] = p.c_rows[g];
+                ctwin[a] = p.c_twin[g];
+            }
+        }
         auto body = [&](auto nkc) {
             constexpr int NK = decltype(nkc)::value;
             u32x4 pend[2];
@@ -942,7 +957,14 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
                     asm volatile("" : "+v"(ln));
                     const int gm = m0 + a * 128 + wr * 64 + i * 16 + (ln >> 2);
                     const int gn = n0 + wc * 32 + (ln & 3) * 8;
-                    if (gm < tp.M && gn + 8 <= I) {
+                    if constexpr (CROWS && kind == 0) {
+                        const int sel = (i * 16 + (ln >> 2)) << 2;
+                        const int d0 = __builtin_amdgcn_ds_bpermute(sel, crow[a]), d1 = __builtin_amdgcn_ds_bpermute(sel, ctwin[a]);
+                        if (gm < tp.M && gn + 8 <= I) {
+                            EPI_GST(u32x4, C2 + (size_t)d0 * p.ldc2 + gn, pend[c & 1]);
+                            if (d1 >= 0) EPI_GST(u32x4, C2 + (size_t)d1 * p.ldc2 + gn, pend[c & 1]);
+                        }
+                    } else if (gm < tp.M && gn + 8 <= I) {
                         if constexpr (kind == 0) EPI_GST(u32x4, C2 + (size_t)gm * p.ldc2 + gn, pend[c & 1]);
                         else EPI_GST(u32x4, C + (size_t)gm * tp.ldc + (kind - 1) * I + gn, pend[c & 1]);
                     }
@@ -1300,6 +1322,14 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
             static_for<0, 2>([&](auto ac) {
                 constexpr int a = decltype(ac)::value;
                 f32x4 cs[4][2], sn[4][2];
+                // CROWS: lane l loads the destination rows of row l of this half's 64 (see the SwiGLU epilogue), next to the positions
+                int crow = 0, ctwin = -1;
+                if constexpr (CROWS) {
+                    int g = m0 + a * 128 + wr * 64 + lane;
+                    g = g < tp.M ? g : tp.M - 1;
+                    crow = p.c_rows[g];
+                    ctwin = p.c_twin[g];
+                }
                 if constexpr (ROT) {
                     int ps[4];
 #pragma unroll
@@ -1339,7 +1369,19 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
                                 y2[4 * k + e] = x2;
                             }
                         }
-                    if (gm < tp.M) {
+                    if constexpr (CROWS) {
+                        const int sel = (i * 16 + er8) << 2;
+                        const int d0 = __builtin_amdgcn_ds_bpermute(sel, crow), d1 = __builtin_amdgcn_ds_bpermute(sel, ctwin);
+                        if (gm < tp.M) {
+                            const u32x4 w1 = pack8(y1), w2 = pack8(y2);
+                            EPI_GST(u32x4, C + (size_t)d0 * tp.ldc + hc, w1);
+                            EPI_GST(u32x4, C + (size_t)d0 * tp.ldc + hc + 64, w2);
+                            if (d1 >= 0) {
+                                EPI_GST(u32x4, C + (size_t)d1 * tp.ldc + hc, w1);
+                                EPI_GST(u32x4, C + (size_t)d1 * tp.ldc + hc + 64, w2);
+                            }
+                        }
+                    } else if (gm < tp.M) {
                         EPI_GST(u32x4, C + (size_t)gm * tp.ldc + hc, pack8(y1));
                         EPI_GST(u32x4, C + (size_t)gm * tp.ldc + hc + 64, pack8(y2));
                     }
@@ -1667,10 +1709,22 @@ bool vlr_gemm256p_fused_try_launch(const GemmParams& p_in, hipStream_t stream) {
     if (p.fuse == 2 && (p.N % PT != 0 || p.rope_cols % PT != 0)) return false;
     if (p.fuse == 1 && ((p.N >> 1) % 8 != 0 || p.ldc2 % 8 != 0 || ((uintptr_t)p.C2 & 15))) return false;
     if ((((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 15) || p.lda % 8 != 0 || p.ldb % 8 != 0 || p.ldc % 8 != 0) return false;
+    if ((p.c_rows || p.c_twin) && (!p.c_rows || !p.c_twin || (p.fuse == 1 && !p.a_rows))) return false;      // both maps; SwiGLU exists with an A-side map only
     sched_prepare(p);
     TRACE_SET(p);
     const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
-    if (p.a_rows) {
+    if (p.c_rows || p.c_twin) {       // output row maps: q|k|v + RoPE with and without an A-side map, SwiGLU with one (the routes of layers.cpp)
+        static bool attr_c = false;
+        if (!attr_c) {
+            attr_c = true;
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 2, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 2, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+            hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 1, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        }
+        if (p.fuse == 2 && p.a_rows) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 2, false, false, true, true>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+        else if (p.fuse == 2) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 2, false, false, false, true>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+        else hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 1, false, false, true, true>), dim3(grid), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    } else if (p.a_rows) {
         static bool attr_r = false;
         if (!attr_r) {
             attr_r = true;

@@ -70,8 +70,9 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
 }
 // Row-compact layer: the row-wise operators run on the Mc kept rows of a batch whose other rows
 // duplicate a kept one (the shared prompt of a DPO pair: causal attention makes the rejected sequence's prompt rows equal the chosen
-// sequence's in every layer).  Attention alone sees the dense [batch * S] layout, rebuilt by a row copy through dense_src and compacted
-// again through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
+// sequence's in every layer).  Attention alone sees the dense [batch * S] layout: the q|k|v epilogue stores a shared row to both of its
+// dense rows (output row maps; a row copy through dense_src where the fused kernel does not take the shape or no twin map is given), and
+// the attention rows are read back through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st);      // gemm.hip: proj_res with the rows of the 128x128 kernel named by the caller
 // gemm.hip: the three forward NT products with the A operand read through an M-side row map; gemm256p.hip: what a launch would pick
@@ -82,6 +83,12 @@ extern "C" int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void
                                     int store_gu, hipStream_t stream);
 extern "C" int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
                                  int peel_rows, int tail_row0, hipStream_t stream);
+extern "C" int vlr_gemm_qkv_rope_bias_dst(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv_dst, const int* c_rows,
+                                          const int* c_twin, void* qkv_rows, const int* dense_src, int Md, const int* pos, const float* cos_t,
+                                          const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim, int max_pos,
+                                          hipStream_t stream);
+extern "C" int vlr_gemm_swiglu_dst(const void* x, const int* a_rows, const void* wgu, void* gu, void* act_dst, const int* c_rows, const int* c_twin,
+                                   void* act_rows, const int* dense_src, int Md, int M, int I, int K, int ldx, int store_gu, hipStream_t stream);
 int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32);
 int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
 // 1: the fused q|k|v + RoPE and gate|up + SwiGLU kernels take every row of this layer's shapes - what a row map on their A operand needs
@@ -93,10 +100,15 @@ static int fused_take_all(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, 
 // peeled rows are the last dense rows (else, and always with attn_in_place = 0, they are compacted into a->attn first).
 // twin != NULL: xn1 / xn2 are written to the DENSE rows of a->xn1 / a->xn2 (and a shared row's dropped copy) by the scatter norms and the
 // fused projections read them through compact_rows - the caller has asked fused_take_all
+// dst_twin != NULL (the caller has asked fused_take_all): the q|k|v + RoPE epilogue stores a kept row straight to its dense row of
+// qkv_dense, and a shared row to its dropped copy's too (output maps compact_rows / dst_twin) - a->qkv is not written and no row copy
+// rebuilds the dense layout.  Else: q|k|v on Mc rows into a->qkv, expanded through dense_src.
+// act_dense (needs twin and dst_twin): the SwiGLU epilogue stores act to the DENSE rows of a->act the same way and down_proj reads the kept
+// rows through compact_rows, as o_proj reads the attention rows - the caller has asked act_in_place
 static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a, const void* x_in,
                              const int* pos_compact, const int* dense_src, const int* compact_rows, const int* twin, int attn_in_place,
                              int Mc, int tail_rows, void* qkv_dense, void* attn_dense, const int* key_mask, int batch, int S,
-                             int keep_for_backward, vlr_stream_t st) {
+                             int keep_for_backward, vlr_stream_t st, const int* dst_twin = nullptr, int act_dense = 0) {
     VLR_REQUIRE(cfg && w && a && x_in && pos_compact && dense_src && compact_rows && qkv_dense && attn_dense,
                 "vlr_decoder_layer_fwd_compact: null argument");
     const int H = cfg->hidden, I = cfg->inter, M = batch * S;
@@ -112,17 +124,26 @@ static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
     // into dropped rows cannot be reproduced: the launch then splits as its own row count suggests
     const int dense_peel = vlr_gemm_peel_rows(M, H);
     const int peel_rows = dense_peel <= tail_rows ? dense_peel : -1;
+    VLR_REQUIRE(!act_dense || (twin && dst_twin), "vlr_decoder_layer_fwd_compact: act on the dense rows needs both twin maps");
     if (twin) {
         CHECK(rf ? vlr_rmsnorm_fwd_f32_scatter((const float*)x_in, w->ln1, a->xn1, a->rstd1, compact_rows, twin, Mc, H, cfg->rms_eps, st)
                  : vlr_rmsnorm_fwd_scatter(x_in, w->ln1, a->xn1, a->rstd1, compact_rows, twin, Mc, H, cfg->rms_eps, st));
-        CHECK(vlr_gemm_qkv_rope_bias_rows(a->xn1, compact_rows, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N,
-                                          Nq + Nkv, H, H, cfg->head_dim, cfg->max_pos, st));
     } else {
         CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, Mc, H, cfg->rms_eps, st));
-        CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H,
-                                     cfg->head_dim, cfg->max_pos, st));
     }
-    CHECK(vlr_gather_rows(a->qkv, dense_src, qkv_dense, M, N, st));              // dense row m = compact row dense_src[m]
+    if (dst_twin) {
+        CHECK(vlr_gemm_qkv_rope_bias_dst(a->xn1, twin ? compact_rows : nullptr, w->wqkv, w->bqkv, qkv_dense, compact_rows, dst_twin, nullptr, nullptr,
+                                         0, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H, cfg->head_dim, cfg->max_pos, st));
+    } else {
+        if (twin) {
+            CHECK(vlr_gemm_qkv_rope_bias_rows(a->xn1, compact_rows, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N,
+                                              Nq + Nkv, H, H, cfg->head_dim, cfg->max_pos, st));
+        } else {
+            CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, N, Nq + Nkv, H, H,
+                                         cfg->head_dim, cfg->max_pos, st));
+        }
+        CHECK(vlr_gather_rows(a->qkv, dense_src, qkv_dense, M, N, st));              // dense row m = compact row dense_src[m]
+    }
     CHECK(vlr_attn_fwd_gqa(qkv_dense, off(qkv_dense, Nq), off(qkv_dense, (size_t)Nq + Nkv), N, attn_dense, Nq, a->lse, key_mask, batch, S,
                            cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
     // o_proj straight from the dense attention rows: the rows the 128x128 kernel gets are the last rows of both layouts (peel_rows >= 0:
@@ -136,6 +157,12 @@ static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
     if (twin) {
         CHECK(rf ? vlr_rmsnorm_fwd_f32_scatter((const float*)a->x_mid, w->ln2, a->xn2, a->rstd2, compact_rows, twin, Mc, H, cfg->rms_eps, st)
                  : vlr_rmsnorm_fwd_scatter(a->x_mid, w->ln2, a->xn2, a->rstd2, compact_rows, twin, Mc, H, cfg->rms_eps, st));
+        if (act_dense) {
+            CHECK(vlr_gemm_swiglu_dst(a->xn2, compact_rows, w->wgu, a->gu, a->act, compact_rows, dst_twin, nullptr, nullptr, 0, Mc, I, H, H,
+                                      keep_for_backward ? 1 : 0, st));
+            // down_proj straight from the dense act rows; the peeled rows are the last rows of both layouts (act_in_place)
+            return vlr_gemm_res_rows(rf, a->act, compact_rows, w->wdown, a->x_out, a->x_mid, Mc, H, I, peel_rows, M - peel_rows, st);
+        }
         CHECK(vlr_gemm_swiglu_rows(a->xn2, compact_rows, w->wgu, a->gu, a->act, Mc, I, H, H, keep_for_backward ? 1 : 0, st));
     } else {
         CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, Mc, H, cfg->rms_eps, st));
@@ -160,6 +187,20 @@ extern "C" int vlr_decoder_layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr
                                              int S, vlr_stream_t st) {
     return layer_fwd_compact(cfg, w, a, x_in, pos_compact, dense_src, compact_rows, nullptr, 1, Mc, tail_rows, qkv_dense, attn_dense,
                              key_mask, batch, S, 0, st);
+}
+// vlr_decoder_layer_fwd_compact_ex with the maps as a struct: where m->twin is given and the fused kernels take the layer's shapes, q|k|v is
+// stored straight to qkv_dense by the projection's epilogue (a->qkv is not written); every value is vlr_decoder_layer_fwd_compact_ex's
+extern "C" int vlr_decoder_layer_fwd_compact_maps(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
+                                                  const void* x_in, const vlr_row_maps* m, void* qkv_dense, void* attn_dense,
+                                                  const int* key_mask, int batch, int S, int keep_for_backward, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && a && x_in && m, "vlr_decoder_layer_fwd_compact_maps: null argument");
+    VLR_REQUIRE(m->compact_rows && m->dense_src && m->pos_compact, "vlr_decoder_layer_fwd_compact_maps: null row map");
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    VLR_REQUIRE(kvh > 0 && cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact_maps: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim;
+    const int* dst_twin = m->twin && fused_take_all(cfg, w, Nq + 2 * Nkv, Nq, Nkv) ? m->twin : nullptr;
+    return layer_fwd_compact(cfg, w, a, x_in, m->pos_compact, m->dense_src, m->compact_rows, nullptr, keep_for_backward ? 0 : 1, m->Mc,
+                             m->tail_rows, qkv_dense, attn_dense, key_mask, batch, S, keep_for_backward, st, dst_twin, 0);
 }
 // What vlr_decoder_layer_fwd_compact_ex left on Mc rows (`c`), copied to the dense layout (`d`, batch * S rows) through dense_src: a
 // dropped row takes its twin's values, which ARE its values - the dense backward then runs unchanged on `d` and computes what it
@@ -188,8 +229,11 @@ extern "C" int vlr_layer_acts_expand(const vlr_llama_cfg* cfg, const vlr_layer_a
 }
 // vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1) for a backward that reads the kept rows in place (vlr_decoder_layer_bwd_src):
 // what only row-wise consumers read - rstd1, x_mid, rstd2, gate | up, x_out - is written on Mc rows into the layer's own set `a` and
-// never copied; the operands of the weight-gradient GEMMs, whose mapped dimension would be K - xn1, xn2, act - are written on Mc rows
-// into the scratch set `s` and copied to the dense rows of `a`.  q|k|v, attn and lse land densely in `a`, as in the expand route
+// never copied; the operands of the weight-gradient GEMMs, whose mapped dimension would be K - xn1, xn2, act - exist on the M dense rows
+// of `a`.  Where the fused kernels take every row of the layer's shapes (the 7B widths) their producers write them there - the scatter
+// norms, and the SwiGLU epilogue through its output maps, with down_proj reading the kept rows through compact_rows - and the q|k|v
+// epilogue writes a->qkv densely too: nothing is copied and of `s` only s->attn may be written.  Elsewhere (toy widths) they are written
+// on Mc rows into `s` and copied.  attn and lse land densely in `a`, as in the expand route
 extern "C" int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                                                   const vlr_layer_acts* s, const void* x_in, const vlr_row_maps* m, const int* key_mask,
                                                   int batch, int S, vlr_stream_t st) {
@@ -207,15 +251,20 @@ extern "C" int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, cons
     // where the fused projections take every row (the 7B shapes; fused_take_all) the norms write xn1 / xn2 to their dense rows and the
     // projections read them through compact_rows; elsewhere they are written on Mc rows into `s` and copied
     const int dense_xn = m->twin && fused_take_all(cfg, w, Nq + 2 * Nkv, Nq, Nkv);
+    // act on its dense rows: down_proj must take the row map - the persistent kernel for all rows but the dense launch's peeled ones, which
+    // then have to be the last rows of both layouts (as for o_proj in layer_fwd_compact)
+    const int dense_peel = vlr_gemm_peel_rows(M, H);
+    const int act_in_place = dense_xn && H > 512 && dense_peel <= m->tail_rows && dense_peel < m->Mc &&
+                             vlr_internal_gemm256p_res_variant(m->Mc - dense_peel, H, I, cfg->resid_f32) != 0;
     const vlr_layer_acts t = {dense_xn ? a->xn1 : s->xn1, a->rstd1, s->qkv, s->attn, a->lse, a->x_mid, dense_xn ? a->xn2 : s->xn2, a->rstd2,
-                              a->gu, s->act, a->x_out};
+                              a->gu, act_in_place ? a->act : s->act, a->x_out};
     CHECK(layer_fwd_compact(cfg, w, &t, x_in, m->pos_compact, m->dense_src, m->compact_rows, dense_xn ? m->twin : nullptr, 1, m->Mc,
-                            m->tail_rows, a->qkv, a->attn, key_mask, batch, S, 1, st));
+                            m->tail_rows, a->qkv, a->attn, key_mask, batch, S, 1, st, dense_xn ? m->twin : nullptr, act_in_place));
     if (!dense_xn) {
         CHECK(vlr_gather_rows(s->xn1, m->dense_src, a->xn1, M, H, st));
         CHECK(vlr_gather_rows(s->xn2, m->dense_src, a->xn2, M, H, st));
     }
-    CHECK(vlr_gather_rows(s->act, m->dense_src, a->act, M, I, st));
+    if (!act_in_place) CHECK(vlr_gather_rows(s->act, m->dense_src, a->act, M, I, st));
     return VLR_OK;
 }
 // gemm256p.hip: the kernel a launch would pick, as host arithmetic

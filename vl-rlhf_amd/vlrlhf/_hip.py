@@ -165,6 +165,9 @@ _SIGS = {
     "vlr_gemm_qkv_rope_bias_rows": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "vlr_gemm_swiglu_rows": [P, P, P, P, P, I, I, I, I, I, P],
     "vlr_gemm_res_rows": [I, P, P, P, P, P, I, I, I, I, I, P],
+    "vlr_gemm_qkv_rope_bias_dst": [P, P, P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, P],
+    "vlr_gemm_swiglu_dst": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "vlr_decoder_layer_fwd_compact_maps": [P, P, P, P, P, P, P, P, I, I, I, P],
     "vlr_gemm_swiglu_bwd_src": [P, P, P, P, P, P, I, I, I, P],
     "vlr_decoder_layer_fwd_compact_keep": [P, P, P, P, P, P, P, I, I, P],
     "vlr_decoder_layer_bwd_src": [P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, P],

@@ -996,10 +996,12 @@ class LlavaHipEngine:
             src, mask, pos = (e[k].reshape(Bn, S) for k in ("src", "mask", "pos"))
             P = prefix_dedup.shared_prefix_lengths(prefix_dedup.source_key(src, ids), mask, pos).tolist()
             rows, dsrc = prefix_dedup.build_row_maps(P, S)
+            twin = prefix_dedup.build_twin(rows, dsrc).to(self.dev)      # (the q|k|v epilogue stores a shared row to both of its dense rows)
             rows, dsrc = rows.to(self.dev), dsrc.to(self.dev)
             # tail: the last dense rows, all kept (the rows past the last pair's shared prefix) - vlr_decoder_layer_fwd_compact
-            plan = dict(P=P, shared=sum(P), M=M, Mc=M - sum(P), tail=S - P[-1], compact_rows=rows, dense_src=dsrc,
+            plan = dict(P=P, shared=sum(P), M=M, Mc=M - sum(P), tail=S - P[-1], compact_rows=rows, dense_src=dsrc, twin=twin,
                         pos=pos.reshape(-1)[rows.long()].contiguous())
+            plan["struct"] = _hip.RowMaps(rows.data_ptr(), dsrc.data_ptr(), None, twin.data_ptr(), plan["pos"].data_ptr(), plan["Mc"], plan["tail"])
             if meta is not None:
                 meta["prefix_dedup"] = plan
         if plan["shared"] == 0 or plan["shared"] < self.prefix_dedup_min_share * plan["M"]:
@@ -1088,8 +1090,8 @@ class LlavaHipEngine:
         """_forward_layers_compact_expand without the copies a row-wise consumer does not need (vlr_decoder_layer_fwd_compact_keep):
         rstd1, x_mid, rstd2, gate | up and x_out stay on the kept rows, in the first Mc rows of the layer's own activation set, and the
         backward reads them through plan["dense_src"] (vlr_decoder_layer_bwd_src); xn1, xn2 and act - the K-side operands of the
-        weight-gradient GEMMs - exist densely: the norms write xn1 / xn2 to their dense rows and the fused projections read them through
-        plan["compact_rows"] (where the fused kernels take the shape; else they are copied), act is copied.  The final norm runs on the kept rows and `hidden` is expanded.
+        weight-gradient GEMMs - exist densely: the norms write xn1 / xn2 to their dense rows, the fused projections read them through
+        plan["compact_rows"] and the SwiGLU epilogue stores act to its dense rows (where the fused kernels take the shape; else they are copied).  The final norm runs on the kept rows and `hidden` is expanded.
         -> (hidden [M] dense, rstd_f [Mc], x_last [Mc], acts, x0_c [Mc]).  The same bits as the expand route, step for step."""
         M, Mc, H = plan["M"], plan["Mc"], self.H
         w16 = 2 if x0.dtype == torch.float32 else 1                  # (row copy: fp32 rows = 2H 16-bit columns)
@@ -1114,8 +1116,8 @@ class LlavaHipEngine:
 
     def _layer_fwd_compact_call(self, ws, l, a, x, e, plan, qkv_d, attn_d, Bn, S, keep):
         """one decoder layer forward of the row-compact policy pass into the activation set `a` (keep: also write what only the backward reads)"""
-        _hip.call("vlr_decoder_layer_fwd_compact_ex", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], x, plan["pos"],
-                  plan["dense_src"], plan["compact_rows"], plan["Mc"], plan["tail"], qkv_d, attn_d, e["mask"], Bn, S, int(keep))
+        _hip.call("vlr_decoder_layer_fwd_compact_maps", self.llama_cfg, self.layer_weights(ws, l, e["tag"]), a["struct"], x, plan["struct"],
+                  qkv_d, attn_d, e["mask"], Bn, S, int(keep))
 
     def _forward_layers_compact(self, ws, e, plan, x0, Bn, S, tag):
         """the decoder layers and the final norm of a no-grad pass on the kept rows of `plan`; -> (hidden [M, H] dense, rstd_f, x_last)
@@ -1130,8 +1132,8 @@ class LlavaHipEngine:
         attn_d = self._buf((tag, "dedup_attn", Bn, S), (M, self.Nq))
         for l in range(self.L):
             a = self._layer_acts(tag + "/scratch", l % 2, Bn, S)
-            _hip.call("vlr_decoder_layer_fwd_compact", self.llama_cfg, self.layer_weights(ws, l, tag), a["struct"], x, plan["pos"], dsrc, rows,
-                      Mc, plan["tail"], qkv_d, attn_d, e["mask"], Bn, S)
+            _hip.call("vlr_decoder_layer_fwd_compact_maps", self.llama_cfg, self.layer_weights(ws, l, tag), a["struct"], x, plan["struct"],
+                      qkv_d, attn_d, e["mask"], Bn, S, 0)
             x = a["x_out"]
         hidden_c = self._buf((tag, "dedup_hidden", Bn, S), (M, H))
         rstd_f = self._buf((tag, "rstd_f", M), (M,), torch.float32)

@@ -58,6 +58,18 @@ def build_row_maps(P: Sequence[int], S: int) -> Tuple[torch.Tensor, torch.Tensor
     return compact_rows.int(), dense_src.int()
 
 
+def build_twin(compact_rows: torch.Tensor, dense_src: torch.Tensor) -> torch.Tensor:
+    """twin int32 [Mc] of a pair of row maps: the dense index of the dropped row that reads kept row j (dense_src names j and the row is
+    not kept), -1 for a kept row that stands for itself alone.  A kept row has at most one dropped copy (the rejected sequence's)."""
+    M, Mc = int(dense_src.numel()), int(compact_rows.numel())
+    kept = torch.zeros(M, dtype=torch.bool)
+    kept[compact_rows.long()] = True
+    dropped = torch.nonzero(~kept).reshape(-1)
+    twin = torch.full((Mc,), -1, dtype=torch.int64)
+    twin[dense_src.long()[dropped]] = dropped
+    return twin.int()
+
+
 def build_policy_plan(P: Sequence[int], S: int) -> dict:
     """Row maps of the row-compact POLICY pass (forward and backward) of B = len(P) pairs of S merged positions; CPU tensors.
     The last pair's prefix is lowered by up to 7 rows (never below 0; what it lacks is taken from the pair before it) so that
