@@ -382,6 +382,33 @@ int vlr_lmhead_logps_bwd(const void* hg, const void* w_lm, const int* tgt, const
                          const float* dlogps, int average, void* dlogits, void* workspace, float* logits_ws, int R, int V, int H,
                          vlr_stream_t stream);
 
+/* The same two passes with the POLICY ENTROPY of every row (additive entry points: vlr_abi_version() does not move; what PPO and GRPO
+ * log, mask by and regularise with).  H_r = -sum_v p_v log p_v = lse_r - sum_v p_v z_v of row r's softmax, fp32.
+ * vlr_lmhead_logps_entropy_fwd: the contract of vlr_lmhead_logps_fwd + entropy [R].  Fused (vlr_lmhead_is_fused, the same predicate):
+ *      every wave leaves a TRIPLE per row and 64-column part in `workspace` (vlr_lmhead_entropy_workspace_bytes) - (m, s, t) with m the
+ *      part's maximum, s = sum e^(z - m), t = sum e^(z - m) (z - m) over the part's columns < V (every term of t is <= 0: nothing
+ *      cancels) - and the lane that owns the target column stores the raw target logit.  A second kernel folds the parts of a row in a
+ *      fixed order, without atomics: M = max m_i, S = sum s_i e^(m_i - M), T = sum e^(m_i - M) (t_i + (m_i - M) s_i), lse = M + log S,
+ *      H = log S - T / S.  tok_logp and lse are BIT-IDENTICAL to vlr_lmhead_logps_fwd on the same inputs (the same partial maxima and
+ *      sums, the same fold order): a caller switches entropy on without moving a log-prob.  Otherwise `logits_ws` ([R][V] fp32)
+ *      carries the logits through vlr_logp_ent_rows, which walks a row in vlr_logp_rows's order (the same bit-equality).
+ * vlr_lmhead_logps_entropy_bwd: dlogp and dent are per-row fp32 [R] (no seq_off: one row per "sequence"); with p = exp(z - lse_r)
+ *      dlogits[r][v] = bf16(dlogp_r ([v == tgt_r] - p) - dent_r (p ((z - lse_r) + H_r))), the parentheses give the order of
+ *      evaluation, rounded once, 16-byte stores.  d H_r / d z_v = -p_v (log p_v + H_r).  Where the second product is zero the first
+ *      term is stored as it is, so with dent all zero the result is BIT-IDENTICAL to vlr_lmhead_logps_bwd(nseq = R, seq_off = 0..R,
+ *      average = 0), the sign of a zero included.  `workspace` non-NULL selects the fused route where it applies (it is not written);
+ *      otherwise `logits_ws` and vlr_dlogits_ent_rows. */
+long vlr_lmhead_entropy_workspace_bytes(int R, int V);
+int vlr_lmhead_logps_entropy_fwd(const void* hg, const void* w_lm, const int* tgt, float* tok_logp, float* lse, float* entropy,
+                                 void* workspace, float* logits_ws, int R, int V, int H, vlr_stream_t stream);
+int vlr_lmhead_logps_entropy_bwd(const void* hg, const void* w_lm, const int* tgt, const float* lse, const float* entropy,
+                                 const float* dlogp, const float* dent, void* dlogits, void* workspace, float* logits_ws, int R, int V,
+                                 int H, vlr_stream_t stream);
+int vlr_logp_ent_rows(const float* logits, const int* tgt, int R, int V, long ld, float* tok_logp, float* lse, float* entropy,
+                      vlr_stream_t stream);
+int vlr_dlogits_ent_rows(const float* logits, const int* tgt, const float* lse, const float* entropy, const float* dlogp,
+                         const float* dent, int R, int V, long ld, void* dlogits, long ldd, vlr_stream_t stream);
+
 /* ---- supervised fine-tuning: the causal-LM cross-entropy `loss` of the model wrappers' forward(labels=...) (reference
  *      Llava/__init__.py:246-257, LlavaNext/__init__.py:322-331, modeling_qwen.py:839-842, InternLMXC2/__init__.py:211-219) = the mean of
  *      -log p(label) over the selected rows of the WHOLE batch, on the tok_logp / lse of vlr_lmhead_logps_fwd.
@@ -481,6 +508,20 @@ int vlr_grpo_advantages(const float* scores, int P, int G, int scale_rewards, fl
 int vlr_grpo_loss(const float* logp, const float* old_logp, const float* ref_logp, const float* adv_seq, const int* seq_off, int R, int n,
                   double eps_low, double eps_high, float beta, int loss_type, int max_completion_length, float upstream, float* dlogp,
                   float* stats, vlr_stream_t stream);
+
+/* vlr_grpo_loss_ent: vlr_grpo_loss with the policy entropy of every token (additive entry point).  entropy [R] fp32 (H_t of
+ *      vlr_lmhead_logps_entropy_fwd), keep [R] bytes (0 / 1; NULL = every token kept: trl's top_entropy_quantile mask), entropy_coef:
+ *      l_t = keep_t (clipped surrogate + beta KL term) - entropy_coef H_t.  The normaliser of every loss_type is vlr_grpo_loss's:
+ *      "grpo" still divides by the full len_s, as trl does when it masks by entropy.  dlogp = vlr_grpo_loss's gradient x keep_t;
+ *      dent_t = -entropy_coef x upstream x (token t's normaliser weight: 1 / (n len_s), 1 / R or 1 / (n max_completion_length)).
+ *      stats[10]: [0..7] as vlr_grpo_loss ([0] the loss above), [8] the token-mean of H, [9] the fraction of tokens kept.  stats[1..5]
+ *      (KL mean, clip fractions, mean ratio) REMAIN MEANS OVER ALL R TOKENS, kept or not.  entropy may be NULL when entropy_coef == 0
+ *      (H reads as 0, stats[8] = 0).  With keep = NULL and entropy_coef = 0, dlogp and stats[0..7] are vlr_grpo_loss's bits.  The same
+ *      single workgroup, wave per sequence and fixed reduction orders. */
+int vlr_grpo_loss_ent(const float* logp, const float* old_logp, const float* ref_logp, const float* adv_seq, const int* seq_off, int R,
+                      int n, double eps_low, double eps_high, float beta, int loss_type, int max_completion_length, float upstream,
+                      const float* entropy, const unsigned char* keep, float entropy_coef, float* dlogp, float* dent, float* stats,
+                      vlr_stream_t stream);
 
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d

@@ -546,6 +546,66 @@ __global__ __launch_bounds__(256) void dlogits_rows_kernel(const float* __restri
         *reinterpret_cast<u32x4*>(dl + (long)i * ldd + c) = pack8(v);
     }
 }
+// logp_rows_kernel with the row entropy H = lse - sum_v p_v z_v: the same walk, the same statements for the maximum and the sum (lse and
+// tok_logp are logp_rows_kernel's bits) and beside them t = sum e^(z - m) (z - m); moving the maximum from m to m' rescales
+// t' = e^(m - m') (t + (m - m') s) with the s of before the move.  H = log S - T / S, T <= 0 term by term.
+__global__ __launch_bounds__(256) void logp_ent_rows_kernel(const float* __restrict__ logits, const int* __restrict__ tgt, int V, long ld,
+                                                            float* __restrict__ tok_logp, float* __restrict__ lse, float* __restrict__ ent) {
+    __shared__ float red[16];
+    const int i = blockIdx.x;
+    const float* l = logits + (long)i * ld;
+    float m = -INFINITY, s = 0.f, t = 0.f;
+    for (int c = threadIdx.x * 4; c < V; c += 256 * 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(l + c);
+        const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (mx > m) {
+            if (m > -INFINITY) t = __expf(m - mx) * fmaf(m - mx, s, t);
+            s *= __expf(m - mx);
+            m = mx;
+        }
+        s += __expf(v[0] - m) + __expf(v[1] - m) + __expf(v[2] - m) + __expf(v[3] - m);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t = fmaf(__expf(v[e] - m), v[e] - m, t);
+    }
+    const float M = block_max(m, red);
+    t = (m == -INFINITY) ? 0.f : __expf(m - M) * fmaf(m - M, s, t);
+    s = (m == -INFINITY) ? 0.f : s * __expf(m - M);
+    s = block_sum(s, red);
+    t = block_sum(t, red);
+    if (threadIdx.x == 0) {
+        const float ls = logf(s);
+        const float z = M + ls;
+        lse[i] = z;
+        tok_logp[i] = l[tgt[i]] - z;
+        ent[i] = ls - t / s;
+    }
+}
+// dlogits[i][v] = dlogp_i * ([v == tgt_i] - p) - dent_i * (p * ((logits[i][v] - lse_i) + H_i)), p = exp(logits[i][v] - lse_i)  (bf16 out);
+// a zero second product leaves dlogits_rows_kernel's bits (x - 0 would turn a -0 into +0)
+__global__ __launch_bounds__(256) void dlogits_ent_rows_kernel(const float* __restrict__ logits, const int* __restrict__ tgt,
+                                                               const float* __restrict__ lse, const float* __restrict__ ent,
+                                                               const float* __restrict__ dlogp, const float* __restrict__ dent, int V, long ld,
+                                                               bf16_t* __restrict__ dl, long ldd) {
+    const int i = blockIdx.x;
+    const float g = dlogp[i], de = dent[i], h = ent[i];
+    const float* l = logits + (long)i * ld;
+    const float z = lse[i];
+    const int t = tgt[i];
+    for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
+        float v[8];
+        *reinterpret_cast<f32x4*>(v) = *reinterpret_cast<const f32x4*>(l + c);
+        *reinterpret_cast<f32x4*>(v + 4) = *reinterpret_cast<const f32x4*>(l + c + 4);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float zl = v[e] - z;
+            const float pe = __expf(zl);
+            const float t0 = g * ((c + e == t ? 1.f : 0.f) - pe);
+            const float t1 = de * (pe * (zl + h));
+            v[e] = t1 == 0.f ? t0 : t0 - t1;
+        }
+        *reinterpret_cast<u32x4*>(dl + (long)i * ldd + c) = pack8(v);
+    }
+}
 // logps[b] = sum_{i in seq b} tok_logp[i]  (/ count when average)
 __global__ __launch_bounds__(256) void seq_sum_kernel(const float* __restrict__ tok, const int* __restrict__ seq_off,
                                                       int average, float* __restrict__ out) {
@@ -787,6 +847,20 @@ extern "C" int vlr_dlogits_rows(const float* logits, const int* tgt, const float
     hipLaunchKernelGGL(dlogits_rows_kernel, dim3(R), dim3(256), 0, st, logits, tgt, lse, seq_off, nseq, dlogps, average, V,
                        ld, (bf16_t*)dlogits, ldd);
     return vlr_check_launch("vlr_dlogits_rows");
+}
+extern "C" int vlr_logp_ent_rows(const float* logits, const int* tgt, int R, int V, long ld, float* tok_logp, float* lse, float* entropy,
+                                 hipStream_t st) {
+    VLR_REQUIRE(logits && tgt && tok_logp && lse && entropy, "vlr_logp_ent_rows: null operand");
+    VLR_REQUIRE(R > 0 && V % 4 == 0 && ld % 4 == 0, "vlr_logp_ent_rows: bad shape R=%d V=%d", R, V);
+    hipLaunchKernelGGL(logp_ent_rows_kernel, dim3(R), dim3(256), 0, st, logits, tgt, V, ld, tok_logp, lse, entropy);
+    return vlr_check_launch("vlr_logp_ent_rows");
+}
+extern "C" int vlr_dlogits_ent_rows(const float* logits, const int* tgt, const float* lse, const float* entropy, const float* dlogp,
+                                    const float* dent, int R, int V, long ld, void* dlogits, long ldd, hipStream_t st) {
+    VLR_REQUIRE(logits && tgt && lse && entropy && dlogp && dent && dlogits, "vlr_dlogits_ent_rows: null operand");
+    VLR_REQUIRE(R > 0 && V % 8 == 0 && ld % 4 == 0 && ldd % 8 == 0, "vlr_dlogits_ent_rows: bad shape");
+    hipLaunchKernelGGL(dlogits_ent_rows_kernel, dim3(R), dim3(256), 0, st, logits, tgt, lse, entropy, dlogp, dent, V, ld, (bf16_t*)dlogits, ldd);
+    return vlr_check_launch("vlr_dlogits_ent_rows");
 }
 extern "C" int vlr_seq_sum(const float* tok_logp, const int* seq_off, int nseq, int average, float* out,
                            hipStream_t st) {

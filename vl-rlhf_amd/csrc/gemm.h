@@ -46,6 +46,14 @@ struct GemmParams {
     //    of the row's sequence (/ count when averaging)
     float* f0;
     float* f1;
+    //  8 lm-head log-probs + entropy, forward: fuse 4 with a third partial per row and 64-column part - (m, s, t), m the part's maximum,
+    //    s = sum e^(z - m), t = sum e^(z - m) (z - m) (every term <= 0), columns >= N masked in all three -> part[row][tile_n * 4 + wc][3];
+    //    m and s are fuse 4's bits.  lmhead_ent_fold_kernel (gemm.hip) folds them into lse, tok_logp and the entropy.
+    //  9 lm-head log-probs + entropy, backward: C (bf16 [R][V]) = f1[row] * ([col == target] - p) - f3[row] * (p * ((z - f0[row]) + f2[row])),
+    //    p = exp(z - f0[row]); f0 = lse, f1 = d logp, f2 = entropy, f3 = d entropy, all per row.  Where the second product is zero the
+    //    first term is stored as it is (fuse 5's bits, the sign of a zero included).
+    const float* f2;
+    const float* f3;
     // ---- adapter segment (LoRA, NT only; template SEG of gemm256p_kernel): the K loop runs on past K into a second pair of
     // operands, C = A B^T + A2 B2^T with B2 block-diagonal over the output blocks [0,seg_b0) [seg_b0,seg_b1) [seg_b1,N):
     //   A2 [M][lda2] = s * dropout_t(x) A_t^T of the group's targets side by side (K2 columns each), B2 [N][ldb2] = lora_B rows.
@@ -155,3 +163,5 @@ bool vlr_gemm256p_swiglu_bwd_try_launch(const GemmParams& p, hipStream_t stream)
 // fuse = 4 | 5: the lm-head GEMM with the log-softmax statistics / the logits gradient in its epilogue
 bool vlr_gemm256p_lmhead_try_launch(const GemmParams& p, hipStream_t stream);
 int vlr_gemm256p_lmhead_parts(int V);      // partial (max, sum) pairs per row the fuse = 4 epilogue writes
+// fuse = 8 | 9: the same two launches with the row entropy (partial triples per row: vlr_gemm256p_lmhead_parts) / its gradient term
+bool vlr_gemm256p_lmhead_ent_try_launch(const GemmParams& p, hipStream_t stream);

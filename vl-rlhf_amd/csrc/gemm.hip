@@ -832,7 +832,7 @@ static int gemm_impl_ex(int layout, const void* A, const void* B, void* C, const
     p.alpha = alpha;
     p.splitk = 1; p.kchunk = 0; p.part = nullptr;
     p.fuse = 0; p.store_c = 1; p.C2 = nullptr; p.ldc2 = 0; p.pos = nullptr; p.rope_cos = p.rope_sin = nullptr; p.max_pos = 0; p.rope_cols = 0;
-    p.f0 = p.f1 = nullptr;
+    p.f0 = p.f1 = nullptr; p.f2 = p.f3 = nullptr;
     p.A2 = p.B2 = nullptr; p.lda2 = p.ldb2 = p.K2 = 0; p.seg_b0 = p.seg_b1 = 0x7fffffff; p.drop_key = 0; p.drop_thr = 0; p.drop_ld = 0;
     p.res_f32 = residual ? res_f32 : 0;
     p.sched = 0;
@@ -933,7 +933,7 @@ static GemmParams fused_params(const void* A, const void* B, void* C, int M, int
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = 0;
     p.act = 0; p.accumulate = 0; p.out_f32 = 0; p.flags = 0; p.alpha = 1.f; p.splitk = 1; p.kchunk = 0; p.part = nullptr;
     p.fuse = 0; p.store_c = 1; p.C2 = nullptr; p.ldc2 = 0; p.pos = nullptr; p.rope_cos = p.rope_sin = nullptr; p.max_pos = 0; p.rope_cols = 0;
-    p.f0 = p.f1 = nullptr;
+    p.f0 = p.f1 = nullptr; p.f2 = p.f3 = nullptr;
     p.A2 = p.B2 = nullptr; p.lda2 = p.ldb2 = p.K2 = 0; p.seg_b0 = p.seg_b1 = 0x7fffffff; p.drop_key = 0; p.drop_thr = 0; p.drop_ld = 0; p.res_f32 = 0;
     p.sched = 0;
     p.A1 = p.B1 = nullptr; p.C1 = nullptr; p.M1 = p.N1 = p.lda1 = p.ldb1 = p.ldc1 = 0;
@@ -1486,4 +1486,89 @@ extern "C" int vlr_lmhead_logps_bwd(const void* hg, const void* w_lm, const int*
     int rc = gemm_impl(0, hg, w_lm, logits_ws, nullptr, nullptr, R, V, H, H, H, V, 0, 0, 0, 1, 1.0f, stream);
     if (rc != VLR_OK) return rc;
     return vlr_dlogits_rows(logits_ws, tgt, lse, seq_off, nseq, dlogps, average, R, V, V, dlogits, V, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same two passes with the row entropy H = -sum_v p_v log p_v = lse - sum_v p_v z_v (include/vlr.h).  Forward: the fuse = 8 epilogue
+// writes (m, s, t) per row and 64-column part, t = sum e^(z - m) (z - m); with M = max m_i the fold is
+//   S = sum s_i e^(m_i - M),   T = sum e^(m_i - M) (t_i + (m_i - M) s_i),   lse = M + log S,   H = log S - T / S
+// (T <= 0 term by term: the two parts of H are both >= 0).  M and S are lmhead_fold_kernel's statements on the same partial values, so
+// lse and tok_logp are vlr_lmhead_logps_fwd's bits.  Backward: fuse = 9 (gemm.h).  Shapes the persistent kernel does not take go
+// through the fp32 logits buffer and the row kernels of dpo_ops.hip.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int vlr_logp_ent_rows(const float* logits, const int* tgt, int R, int V, long ld, float* tok_logp, float* lse, float* entropy,
+                                 hipStream_t st);
+extern "C" int vlr_dlogits_ent_rows(const float* logits, const int* tgt, const float* lse, const float* entropy, const float* dlogp,
+                                    const float* dent, int R, int V, long ld, void* dlogits, long ldd, hipStream_t st);
+
+__global__ __launch_bounds__(64) void lmhead_ent_fold_kernel(const float* __restrict__ parts, int nparts, const float* __restrict__ tok_raw,
+                                                             float* __restrict__ tok_logp, float* __restrict__ lse, float* __restrict__ ent) {
+    const int r = blockIdx.x, l = threadIdx.x;
+    const float* pr = parts + (size_t)r * nparts * 3;
+    float m = -INFINITY;
+    for (int i = l; i < nparts; i += 64) m = fmaxf(m, pr[3 * i]);
+    m = wave_max(m);
+    float s = 0.f, t = 0.f;
+    for (int i = l; i < nparts; i += 64) {
+        const float mi = pr[3 * i];
+        if (mi > -INFINITY) {
+            s += pr[3 * i + 1] * __expf(mi - m);
+            t += __expf(mi - m) * fmaf(mi - m, pr[3 * i + 1], pr[3 * i + 2]);
+        }
+    }
+    s = wave_sum(s);                       // fixed order: deterministic
+    t = wave_sum(t);
+    if (l == 0) {
+        const float ls = logf(s);
+        const float z = m + ls;
+        lse[r] = z;
+        tok_logp[r] = tok_raw[r] - z;
+        ent[r] = ls - t / s;
+    }
+}
+
+extern "C" long vlr_lmhead_entropy_workspace_bytes(int R, int V) { return ((long)R * vlr_gemm256p_lmhead_parts(V) * 3 + 2L * R) * 4; }
+
+extern "C" int vlr_lmhead_logps_entropy_fwd(const void* hg, const void* w_lm, const int* tgt, float* tok_logp, float* lse, float* entropy,
+                                            void* workspace, float* logits_ws, int R, int V, int H, hipStream_t stream) {
+    VLR_REQUIRE(hg && w_lm && tgt && tok_logp && lse && entropy, "vlr_lmhead_logps_entropy_fwd: null operand");
+    VLR_REQUIRE(R > 0 && V % 8 == 0 && H % 8 == 0, "vlr_lmhead_logps_entropy_fwd: bad shape R=%d V=%d H=%d", R, V, H);
+    if (workspace && vlr_lmhead_is_fused(R, V, H)) {
+        const int nparts = vlr_gemm256p_lmhead_parts(V);
+        float* parts = (float*)workspace;
+        float* tok_raw = parts + (size_t)R * nparts * 3;
+        GemmParams p = fused_params(hg, w_lm, nullptr, R, V, H, H, H, V);
+        p.fuse = 8; p.pos = tgt; p.C2 = parts; p.f1 = tok_raw;
+        const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * R * V * H, stream);
+        const bool took_ = vlr_gemm256p_lmhead_ent_try_launch(p, stream);
+        vlr_prof_end(took_ ? pi_ : -1, stream);
+        if (took_) {
+            hipLaunchKernelGGL(lmhead_ent_fold_kernel, dim3(R), dim3(64), 0, stream, (const float*)parts, nparts, (const float*)tok_raw, tok_logp, lse,
+                               entropy);
+            return vlr_check_launch("vlr_lmhead_logps_entropy_fwd(fused)");
+        }
+    }
+    VLR_REQUIRE(logits_ws, "vlr_lmhead_logps_entropy_fwd: this shape needs the fp32 logits buffer [R][V]");
+    int rc = gemm_impl(0, hg, w_lm, logits_ws, nullptr, nullptr, R, V, H, H, H, V, 0, 0, 0, 1, 1.0f, stream);
+    if (rc != VLR_OK) return rc;
+    return vlr_logp_ent_rows(logits_ws, tgt, R, V, V, tok_logp, lse, entropy, stream);
+}
+
+extern "C" int vlr_lmhead_logps_entropy_bwd(const void* hg, const void* w_lm, const int* tgt, const float* lse, const float* entropy,
+                                            const float* dlogp, const float* dent, void* dlogits, void* workspace, float* logits_ws, int R,
+                                            int V, int H, hipStream_t stream) {
+    VLR_REQUIRE(hg && w_lm && tgt && lse && entropy && dlogp && dent && dlogits, "vlr_lmhead_logps_entropy_bwd: null operand");
+    VLR_REQUIRE(R > 0 && V % 8 == 0 && H % 8 == 0, "vlr_lmhead_logps_entropy_bwd: bad shape R=%d V=%d H=%d", R, V, H);
+    if (workspace && vlr_lmhead_is_fused(R, V, H)) {
+        GemmParams p = fused_params(hg, w_lm, dlogits, R, V, H, H, H, V);
+        p.fuse = 9; p.pos = tgt; p.f0 = const_cast<float*>(lse); p.f1 = const_cast<float*>(dlogp); p.f2 = entropy; p.f3 = dent;
+        const int pi_ = vlr_prof_begin(VLR_K_GEMM_NT, 2.0 * R * V * H, stream);
+        const bool took_ = vlr_gemm256p_lmhead_ent_try_launch(p, stream);
+        vlr_prof_end(took_ ? pi_ : -1, stream);
+        if (took_) return vlr_check_launch("vlr_lmhead_logps_entropy_bwd(fused)");
+    }
+    VLR_REQUIRE(logits_ws, "vlr_lmhead_logps_entropy_bwd: this shape needs the fp32 logits buffer [R][V]");
+    int rc = gemm_impl(0, hg, w_lm, logits_ws, nullptr, nullptr, R, V, H, H, H, V, 0, 0, 0, 1, 1.0f, stream);
+    if (rc != VLR_OK) return rc;
+    return vlr_dlogits_ent_rows(logits_ws, tgt, lse, entropy, dlogp, dent, R, V, V, dlogits, V, stream);
 }

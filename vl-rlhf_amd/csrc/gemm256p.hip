@@ -355,7 +355,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
     static_assert(!CROWS || (CONT && (FUSE == 1 || FUSE == 2) && !SEG), "output row maps: the SwiGLU and RoPE epilogues, no adapter segment");
     static_assert(!GRP || (A_KS && B_KS && CONT && FUSE == 0 && !SEG), "grouped launches: TN, plain epilogue");
     static_assert(FUSE == 0 || (FUSE == 6 && !CONT && !A_KS && B_KS) || (FUSE != 6 && CONT && !A_KS && (FUSE == 3 || FUSE == 7 ? B_KS : !B_KS)),
-                  "fused epilogues: continuous pipeline; 1, 2, 4, 5 NT, 3, 7 NN; 6 (dropout-accumulate) NN on the LDS-image epilogue");
+                  "fused epilogues: continuous pipeline; 1, 2, 4, 5, 8, 9 NT, 3, 7 NN; 6 (dropout-accumulate) NN on the LDS-image epilogue");
     static_assert(!SEG || (!A_KS && !B_KS && FUSE <= 2), "adapter segment: NT, plain / SwiGLU / RoPE epilogues");
     constexpr int NW = FUSE == 1 ? 128 : PT;      // output columns (of the gate half, for SwiGLU) per workgroup tile
     extern __shared__ __attribute__((aligned(16))) char smem[];   // P_LDS_BYTES
@@ -1038,6 +1038,93 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmParams p, const bf16_
                         const int gn0 = n0 + b * 128 + wc * 32 + j * 16 + 4 * lq_;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) d[j][e] = g * ((gn0 + e == tg ? 1.f : 0.f) - __expf(acc[a][i][b][j][e] - z));
+                    }
+                    const int gn = n0 + b * 128 + wc * 32 + widen_col(lq_);
+                    const u32x4 w = widen_pair(d[0], d[1]);
+                    if (gm < tp.M && gn + 8 <= tp.N) EPI_GST(u32x4, C + (size_t)gm * tp.ldc + gn, w);
+                }
+            }
+    } else if constexpr (CONT && FUSE == 8) {
+        // lm-head forward with entropy: FUSE 4's partials (the same maxima and sums, bit for bit) + t = sum e^(z - m) (z - m) over the
+        // same columns, from the exponential the sum already formed; every term is <= 0.  A part with no column < N stores (-inf, 0, 0).
+        const int lm_ = lane & 15, lq_ = lane >> 4;
+        const int nparts = tiles_n * 4;
+        const int part = (n0 / PT) * 4 + wc;
+        float* __restrict__ parts = reinterpret_cast<float*>(p.C2);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int gm = m0 + a * 128 + wr * 64 + i * 16 + lm_;
+                const int tg = gm < tp.M ? p.pos[gm] : -1;
+                float mx = -INFINITY;
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int gn = n0 + b * 128 + wc * 32 + j * 16 + 4 * lq_;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float v = acc[a][i][b][j][e];
+                            if (gn + e < tp.N) mx = fmaxf(mx, v);
+                            if (gn + e == tg) p.f1[gm] = v;               // exactly one lane of one workgroup owns the target column
+                        }
+                    }
+                mx = fmaxf(mx, __shfl_xor(mx, 16));
+                mx = fmaxf(mx, __shfl_xor(mx, 32));
+                float sm = 0.f, tt = 0.f;
+                if (mx > -INFINITY) {
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int gn = n0 + b * 128 + wc * 32 + j * 16 + 4 * lq_;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (gn + e < tp.N) {
+                                    const float d = acc[a][i][b][j][e] - mx;
+                                    const float ex = __expf(d);
+                                    sm += ex;
+                                    tt = fmaf(ex, d, tt);
+                                }
+                        }
+                }
+                sm += __shfl_xor(sm, 16);
+                sm += __shfl_xor(sm, 32);
+                tt += __shfl_xor(tt, 16);
+                tt += __shfl_xor(tt, 32);
+                if (lq_ == 0 && gm < tp.M) {
+                    float* o = parts + ((size_t)gm * nparts + part) * 3;
+                    o[0] = mx; o[1] = sm; o[2] = tt;
+                }
+            }
+    } else if constexpr (CONT && FUSE == 9) {
+        // lm-head backward with the entropy term: FUSE 5's value minus de_row * (p * ((z - lse_row) + H_row)) with the same p; a zero
+        // second product leaves FUSE 5's bits (x - 0 would turn a -0 into +0).  Rounded once, 16-byte stores.
+        bf16_t* C = reinterpret_cast<bf16_t*>(tp.C);
+        const int lm_ = lane & 15, lq_ = lane >> 4;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int gm = m0 + a * 128 + wr * 64 + i * 16 + lm_;
+                const int gmc = gm < tp.M ? gm : tp.M - 1;
+                const int tg = p.pos[gmc];
+                const float z = p.f0[gmc], g = p.f1[gmc], hr = p.f2[gmc], de = p.f3[gmc];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    f32x4 d[2];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int gn0 = n0 + b * 128 + wc * 32 + j * 16 + 4 * lq_;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float zl = acc[a][i][b][j][e] - z;
+                            const float pe = __expf(zl);
+                            const float t0 = g * ((gn0 + e == tg ? 1.f : 0.f) - pe);
+                            const float t1 = de * (pe * (zl + hr));
+                            d[j][e] = t1 == 0.f ? t0 : t0 - t1;
+                        }
                     }
                     const int gn = n0 + b * 128 + wc * 32 + widen_col(lq_);
                     const u32x4 w = widen_pair(d[0], d[1]);
@@ -1891,6 +1978,32 @@ bool vlr_gemm256p_lmhead_try_launch(const GemmParams& p_in, hipStream_t stream) 
     const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
     if (p.fuse == 4) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 4>), dim3(n_cu), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     else hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 5>), dim3(n_cu), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    vlr_prof_end(pi, stream);
+    return true;
+}
+
+// fuse = 8 | 9: the predicate and the launch geometry of vlr_gemm256p_lmhead_try_launch, instantiations of their own
+bool vlr_gemm256p_lmhead_ent_try_launch(const GemmParams& p_in, hipStream_t stream) {
+    GemmParams p = p_in;
+    static bool attr = false;
+    if (!attr) {
+        attr = true;
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm256p_kernel<false, false, 0, true, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, CONT_LDS_BYTES);
+    }
+    if (p.fuse != 8 && p.fuse != 9) return false;
+    bf16_t* zero16 = gemm256p_zero16();
+    if (!zero16) return false;
+    const int n_cu = gemm256p_n_cu();
+    const int ntiles = ((p.M + PT - 1) / PT) * ((p.N + PT - 1) / PT);
+    if (ntiles <= n_cu || persist_grid(ntiles, n_cu) != n_cu || p.K < 4 * PK) return false;      // (vlr_lmhead_is_fused, gemm.hip, states the same predicate)
+    if ((((uintptr_t)p.A | (uintptr_t)p.B) & 15) || p.lda % 8 != 0 || p.ldb % 8 != 0 || p.N % 8 != 0) return false;
+    if (p.fuse == 9 && (p.ldc % 8 != 0 || ((uintptr_t)p.C & 15) || !p.f2 || !p.f3)) return false;
+    sched_prepare(p);
+    TRACE_SET(p);
+    const int pi = vlr_prof_begin(VLR_K_GEMM256P, 2.0 * p.M * p.N * p.K, stream);
+    if (p.fuse == 8) hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 8>), dim3(n_cu), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
+    else hipLaunchKernelGGL((gemm256p_kernel<false, false, 0, true, 9>), dim3(n_cu), dim3(512), CONT_LDS_BYTES, stream, p, (const bf16_t*)zero16);
     vlr_prof_end(pi, stream);
     return true;
 }

@@ -141,3 +141,96 @@ extern "C" int vlr_grpo_loss(const float* logp, const float* old_logp, const flo
                        (float)(1.0 - eps_low), (float)(1.0 + eps_high), beta, loss_type, inv_norm, upstream, dlogp, stats);
     return vlr_check_launch("vlr_grpo_loss");
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// vlr_grpo_loss_ent: grpo_loss_kernel's pass with the per-token entropy H_t, the keep mask and the bonus (include/vlr.h).  The statements
+// that form a token's loss and gradient are grpo_loss_kernel's; keep_t (1 or 0) multiplies them afterwards and the bonus is subtracted
+// last, so keep = NULL and entropy_coef = 0 leave every bit (x 1 and - 0 * H).  The KL, clip and ratio statistics count every token.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(GRPO_THREADS) void grpo_loss_ent_kernel(const float* __restrict__ logp, const float* __restrict__ old_logp,
+                                                                     const float* __restrict__ ref_logp, const float* __restrict__ adv_seq,
+                                                                     const int* __restrict__ seq_off, int R, int n, float lo, float hi,
+                                                                     float beta, int loss_type, float inv_norm, float upstream,
+                                                                     const float* __restrict__ entropy, const unsigned char* __restrict__ keep,
+                                                                     float coef, float* __restrict__ dlogp, float* __restrict__ dent,
+                                                                     float* __restrict__ stats) {
+    __shared__ float red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float s_l = 0.f, s_kl = 0.f, s_lo = 0.f, s_hi = 0.f, s_ratio = 0.f, s_h = 0.f, s_keep = 0.f;      // this lane's token sums
+    float s_seq = 0.f;                                                       // wave-uniform: sum of the wave's sequence means (loss_type 0)
+    for (int s = wave; s < n; s += GRPO_WAVES) {
+        const int b = max(seq_off[s], 0), e = min(seq_off[s + 1], R);
+        if (e <= b) continue;      // (uniform over the wave)
+        const float A = adv_seq[s];
+        const float inv_len = 1.f / (float)(e - b);
+        const float g = upstream * (loss_type == 0 ? inv_norm * inv_len : inv_norm);
+        float sl = 0.f;
+        for (int i = b + lane; i < e; i += 64) {
+            const float lp = logp[i];
+            const float r = expf(lp - (old_logp ? old_logp[i] : lp));
+            const float rc = fminf(fmaxf(r, lo), hi);
+            const float u = r * A, c = rc * A;
+            const float du = u, dc = (r >= lo && r <= hi) ? u : 0.f;      // d ratio / d logp = ratio
+            float l = -fminf(u, c);
+            float dl = -(u < c ? du : (c < u ? dc : 0.5f * (du + dc)));
+            if (beta != 0.f) {
+                const float d = ref_logp[i] - lp;
+                const float ed = expf(d);
+                const float k = ed - d - 1.f;
+                l = fmaf(beta, k, l);
+                dl = fmaf(beta, 1.f - ed, dl);
+                s_kl += k;
+            }
+            const bool kept = !keep || keep[i] != 0;
+            const float h = entropy ? entropy[i] : 0.f;
+            dlogp[i] = kept ? g * dl : 0.f;
+            if (dent) dent[i] = -(coef * g);
+            if (!kept) l = 0.f;
+            if (coef != 0.f) l -= coef * h;
+            sl += l;
+            s_lo += (r < lo && A < 0.f) ? 1.f : 0.f;
+            s_hi += (r > hi && A > 0.f) ? 1.f : 0.f;
+            s_ratio += r;
+            s_h += h;
+            s_keep += kept ? 1.f : 0.f;
+        }
+        s_l += sl;
+        if (loss_type == 0) s_seq += wave_sum(sl) * inv_len;
+    }
+    const float invR = 1.f / (float)R;
+    const float t_l = block_sum(s_l, red), t_seq = block_sum(lane == 0 ? s_seq : 0.f, red);
+    const float m_kl = block_sum(s_kl, red) * invR, m_lo = block_sum(s_lo, red) * invR, m_hi = block_sum(s_hi, red) * invR;
+    const float m_ratio = block_sum(s_ratio, red) * invR;
+    const float m_h = block_sum(s_h, red) * invR, m_keep = block_sum(s_keep, red) * invR;
+    if (tid == 0) {
+        stats[0] = (loss_type == 0 ? t_seq : t_l) * inv_norm;
+        stats[1] = m_kl;
+        stats[2] = m_lo;
+        stats[3] = m_hi;
+        stats[4] = m_lo + m_hi;
+        stats[5] = m_ratio;
+        stats[6] = (float)R / (float)n;
+        stats[7] = 0.f;
+        stats[8] = m_h;
+        stats[9] = m_keep;
+    }
+}
+
+extern "C" int vlr_grpo_loss_ent(const float* logp, const float* old_logp, const float* ref_logp, const float* adv_seq, const int* seq_off,
+                                 int R, int n, double eps_low, double eps_high, float beta, int loss_type, int max_completion_length,
+                                 float upstream, const float* entropy, const unsigned char* keep, float entropy_coef, float* dlogp,
+                                 float* dent, float* stats, hipStream_t st) {
+    VLR_REQUIRE(logp && adv_seq && seq_off && dlogp && stats, "vlr_grpo_loss_ent: null operand");
+    VLR_REQUIRE(ref_logp || beta == 0.f, "vlr_grpo_loss_ent: null ref_logp with beta %g (the KL term needs the reference)", (double)beta);
+    VLR_REQUIRE((entropy && dent) || entropy_coef == 0.f, "vlr_grpo_loss_ent: null entropy / dent with entropy_coef %g", (double)entropy_coef);
+    VLR_REQUIRE(R >= 1 && n >= 1 && n <= R, "vlr_grpo_loss_ent: bad shape R=%d n=%d", R, n);
+    VLR_REQUIRE(eps_low >= 0. && eps_high >= 0., "vlr_grpo_loss_ent: negative clip range %g / %g", eps_low, eps_high);
+    VLR_REQUIRE(loss_type >= 0 && loss_type <= 2, "vlr_grpo_loss_ent: loss_type %d (0 grpo, 1 bnpo, 2 dr_grpo)", loss_type);
+    VLR_REQUIRE(loss_type != 2 || max_completion_length >= 1, "vlr_grpo_loss_ent: max_completion_length %d with loss_type 2 (dr_grpo)",
+                max_completion_length);
+    const float inv_norm = loss_type == 0 ? 1.f / (float)n : (loss_type == 1 ? 1.f / (float)R : 1.f / ((float)n * (float)max_completion_length));
+    hipLaunchKernelGGL(grpo_loss_ent_kernel, dim3(1), dim3(GRPO_THREADS), 0, st, logp, old_logp, ref_logp, adv_seq, seq_off, R, n,
+                       (float)(1.0 - eps_low), (float)(1.0 + eps_high), beta, loss_type, inv_norm, upstream, entropy, keep, entropy_coef, dlogp,
+                       dent, stats);
+    return vlr_check_launch("vlr_grpo_loss_ent");
+}

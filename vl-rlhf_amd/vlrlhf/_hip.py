@@ -134,6 +134,10 @@ _SIGS = {
     "vlr_seq_sum": [P, P, I, I, P, P],
     "vlr_lmhead_logps_fwd": [P, P, P, P, P, P, P, I, I, I, P],
     "vlr_lmhead_logps_bwd": [P, P, P, P, P, I, P, I, P, P, P, I, I, I, P],
+    "vlr_lmhead_logps_entropy_fwd": [P, P, P, P, P, P, P, P, I, I, I, P],
+    "vlr_lmhead_logps_entropy_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, P],
+    "vlr_logp_ent_rows": [P, P, I, I, L, P, P, P, P],
+    "vlr_dlogits_ent_rows": [P, P, P, P, P, P, I, I, L, P, L, P],
     "vlr_ce_mean_fwd": [P, I, P, P, P],
     "vlr_lmhead_ce_bwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P],
     "vlr_dpo_loss": [P, P, P, P, I, F, F, I, I, P, P, P, P, P, P, P, P],
@@ -146,6 +150,7 @@ _SIGS = {
     # GRPO (include/vlr.h "GRPO"): the group-standardised advantages, the clipped per-token loss with its gradient
     "vlr_grpo_advantages": [P, I, I, I, P, P, P],
     "vlr_grpo_loss": [P, P, P, P, P, I, I, D, D, F, I, I, F, P, P, P],
+    "vlr_grpo_loss_ent": [P, P, P, P, P, I, I, D, D, F, I, I, F, P, P, F, P, P, P, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],
     "vlr_decoder_layer_fwd": [P, P, P, P, P, P, I, I, P],
@@ -267,7 +272,7 @@ _INT_HELPERS = {
 
 _LONG_HELPERS = ["vlr_gemv_workspace_bytes", "vlr_attn_decode_workspace_bytes", "vlr_gemv_w4_workspace_bytes", "vlr_gemv_wide_workspace_bytes",
                  "vlr_gemv_wide_w4_workspace_bytes"]      # (int, int, int) -> long
-_LONG_HELPERS_N = {"vlr_v_head_bwd_workspace_bytes": 2, "vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5,
+_LONG_HELPERS_N = {"vlr_v_head_bwd_workspace_bytes": 2, "vlr_lmhead_entropy_workspace_bytes": 2, "vlr_gemv_lora_workspace_bytes": 4, "vlr_gemv_lora_u_bytes": 3, "vlr_attn_decode_shared_workspace_bytes": 5,
                    "vlr_gemv_wide_lora_workspace_bytes": 4, "vlr_gemv_wide_lora_u_bytes": 3}      # name -> number of int arguments, -> long
 
 

@@ -226,8 +226,8 @@ class _PpoHeadsFn(torch.autograd.Function):
     """hidden [M, H] -> (token log-probs [R], values [R]) on the response rows (engine.ppo_forward / ppo_backward) as one autograd node"""
 
     @staticmethod
-    def forward(ctx, hidden, model, c, labels, label_pad):
-        tok, values, lp = model.engine.ppo_forward(c, labels, label_pad)
+    def forward(ctx, hidden, model, c, labels, label_pad, entropy=False):
+        tok, values, lp = model.engine.ppo_forward(c, labels, label_pad, entropy)      # (the entropy is a statistic: read from lp, no gradient)
         ctx.lp, ctx.engine = lp, model.engine
         model._last_lp = lp
         return tok, values
@@ -238,7 +238,7 @@ class _PpoHeadsFn(torch.autograd.Function):
         zero = lambda: torch.zeros(R, dtype=torch.float32, device=ctx.engine.dev)      # noqa: E731
         dh = ctx.engine.ppo_backward(ctx.lp, zero() if dlogp is None else dlogp.contiguous(), zero() if dvalues is None else dvalues.contiguous())
         ctx.lp = None
-        return dh, None, None, None, None
+        return dh, None, None, None, None, None
 
 
 class _TokenLogpsFn(torch.autograd.Function):
@@ -258,19 +258,43 @@ class _TokenLogpsFn(torch.autograd.Function):
         return dh, None, None, None, None
 
 
-def token_logps(model, input_ids, attention_mask, labels, **img):
+class _TokenLogpsEntFn(torch.autograd.Function):
+    """hidden [M, H] -> (token log-probs [R], policy entropy [R]) on the response rows as one autograd node: the lm-head pass with the
+    entropy in its epilogue.  An entropy output that receives no gradient costs nothing in the backward (the existing lm-head backward
+    runs); one that does hands d entropy to the entropy backward."""
+
+    @staticmethod
+    def forward(ctx, hidden, model, c, labels, label_pad):
+        tok, lp = model.engine.token_logps_forward(c, labels, label_pad, entropy=True)
+        ctx.lp, ctx.engine = lp, model.engine
+        ctx.set_materialize_grads(False)
+        model._last_lp = lp
+        return tok, lp["entropy"]
+
+    @staticmethod
+    def backward(ctx, dlogp, dent):
+        if dlogp is None:
+            dlogp = torch.zeros(ctx.lp["R"], dtype=torch.float32, device=ctx.engine.dev)
+        dh = ctx.engine.token_logps_backward(ctx.lp, dlogp.contiguous(), None if dent is None else dent.contiguous())
+        ctx.lp = None
+        return dh, None, None, None, None
+
+
+def token_logps(model, input_ids, attention_mask, labels, return_entropy=False, **img):
     """-> token log-probs [R] fp32 of a PLAIN family wrapper (LlavaForRL, QwenVLForRL: no value head) on the R response rows - the
     positions whose logits predict a token with label != -100, sequence after sequence; token_seq_off(model) [Bn + 1] delimits them.
-    What GRPO trains on: the same forward as VLModelWithValueHead's, without the value head."""
+    What GRPO trains on: the same forward as VLModelWithValueHead's, without the value head.  return_entropy: -> (log-probs, entropy
+    [R] fp32 of each row's softmax over the vocabulary) from the same lm-head pass; the log-probs keep their bits and the entropy is
+    differentiable."""
     if labels is None:
         raise ValueError("token_logps needs labels (-100 outside the response): log-probs exist on the response rows only")
     out = model(input_ids=input_ids, attention_mask=attention_mask, labels=labels, **img)
     lg = out.logits
     c, hidden = lg.c, lg.hidden
     if hidden.requires_grad:
-        return _TokenLogpsFn.apply(hidden, model, c, c["labels"], -100)
-    tok, model._last_lp = model.engine.token_logps_forward(c, c["labels"], -100)
-    return tok
+        return (_TokenLogpsEntFn if return_entropy else _TokenLogpsFn).apply(hidden, model, c, c["labels"], -100)
+    tok, model._last_lp = model.engine.token_logps_forward(c, c["labels"], -100, entropy=return_entropy)
+    return (tok, model._last_lp["entropy"]) if return_entropy else tok
 
 
 def token_seq_off(model):
@@ -439,11 +463,12 @@ class VLModelWithValueHead(nn.Module):
         self.engine.zero_grad()
 
     # ---- forward ------------------------------------------------------------------------------------------
-    def forward(self, input_ids, attention_mask=None, labels=None, return_logits=False, **kwargs):
+    def forward(self, input_ids, attention_mask=None, labels=None, return_logits=False, return_entropy=False, **kwargs):
         """-> (token log-probs [R] fp32, None, values [R] fp32) on the R response rows: the positions whose logits predict a token with
         label != -100 (trl reads logprobs and values[:, :-1] under the same mask), sequence after sequence - `self.seq_off` [Bn + 1]
         delimits them.  The middle element is trl's `loss`, never computed.  return_logits=True puts the lazy [B, S, V] logits stand-in of
-        the base wrapper in the first slot instead (values still need labels)."""
+        the base wrapper in the first slot instead (values still need labels).  return_entropy=True appends the policy entropy [R] fp32
+        of the same rows (a statistic, detached: PPO has no entropy term), from the same lm-head pass."""
         for k in ("output_hidden_states", "return_dict", "use_cache", "past_key_values"):
             kwargs.pop(k, None)
         if labels is None and not return_logits:
@@ -455,9 +480,11 @@ class VLModelWithValueHead(nn.Module):
             return lg, None, None
         c, hidden = lg.c, lg.hidden
         if hidden.requires_grad:
-            tok, values = _PpoHeadsFn.apply(hidden, self, c, c["labels"], -100)
+            tok, values = _PpoHeadsFn.apply(hidden, self, c, c["labels"], -100, bool(return_entropy))
         else:
-            tok, values, self._last_lp = self.engine.ppo_forward(c, c["labels"], -100)
+            tok, values, self._last_lp = self.engine.ppo_forward(c, c["labels"], -100, bool(return_entropy))
+        if return_entropy:
+            return (lg if return_logits else tok), None, values, self._last_lp["entropy"]
         return (lg if return_logits else tok), None, values
 
     @property

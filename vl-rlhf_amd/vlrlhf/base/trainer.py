@@ -1266,6 +1266,10 @@ class PPOConfig:
     # not in the reference: a checkpoint every save_steps steps of train() (0: none) and the one to resume from
     save_steps: int = 0
     resume_from_checkpoint: Optional[str] = None
+    # trl's two entropy statistics (off: the step is launch for launch the one without them): "ppo/policy/entropy", the mean entropy of the
+    # policy's softmax over the minibatch's response rows (from the lm-head pass the log-probs come from), and "objective/entropy", the mean
+    # over the sequences of sum_t -old_logp_t.  No bonus: trl's PPO has none.
+    log_entropy: bool = False
 
     def __post_init__(self):
         self.backward_batch_size = self.mini_batch_size * self.gradient_accumulation_steps
@@ -1572,6 +1576,12 @@ class VLOnlineRLTrainer:
         return responses
 
 
+def sequence_neg_logp_mean(old_logp, seq_off):
+    """trl's "objective/entropy" (record_step_stats): the mean over the sequences of sum_t -old_logp_t, in fp64 on the host"""
+    x = old_logp.detach().double().cpu()
+    return sum(-float(x[seq_off[s]:seq_off[s + 1]].sum()) for s in range(len(seq_off) - 1)) / (len(seq_off) - 1)
+
+
 class VLPPOTrainer(VLOnlineRLTrainer):
     """The PPO optimisation step - trl==0.8.1 PPOTrainer.step as the reference's VLPPOTrainer (base/trainer.py) drives it, restated in
     include/vlr.h ("PPO") and run on the HIP engine: no-grad rollout passes of the policy (log-probs, values) and of the reference
@@ -1582,8 +1592,8 @@ class VLPPOTrainer(VLOnlineRLTrainer):
     the permutation generator and the row order) are here; the entry point is vlrlhf/ppo.py.
 
     Deliberate differences from trl: the image inputs reach every forward of the step (trl's prepare_model_inputs drops them); the
-    entropy statistics are left out (they need a pass over the vocabulary and carry no gradient); rollout and reference passes run in
-    eval mode (no adapter dropout, no NEFTune noise); world_size > 1 is refused, since whitening and the KL mean are per process in trl
+    entropy statistics are opt-in (PPOConfig.log_entropy: the pass over the vocabulary rides in the lm-head's epilogue); rollout and
+    reference passes run in eval mode (no adapter dropout, no NEFTune noise); world_size > 1 is refused, since whitening and the KL mean are per process in trl
     and nothing here settles what they should be across ranks."""
 
     def __init__(self, config=None, model=None, ref_model=None, reward_model=None, processor=None, dataset=None, data_collator=None,
@@ -1718,7 +1728,7 @@ class VLPPOTrainer(VLOnlineRLTrainer):
         # ---- optimisation (train mode for its passes; the caller's mode comes back afterwards)
         model.train()
         upstream = 1.0 / cfg.gradient_accumulation_steps
-        mb_stats = []
+        mb_stats, mb_ent = [], []
         try:
             for _ in range(cfg.ppo_epochs):
                 perm = torch.randperm(n, generator=self._perm_gen).tolist()
@@ -1730,7 +1740,12 @@ class VLPPOTrainer(VLOnlineRLTrainer):
                         Rm = tok_idx.numel()
                         if Rm < 2:
                             raise ValueError(f"step: a minibatch needs at least 2 response tokens, got {Rm}")
-                        logp, _, vpred = model(ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), **self._rows_images(ids, img, rows))
+                        if cfg.log_entropy:
+                            logp, _, vpred, ent = model(ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), return_entropy=True,
+                                                        **self._rows_images(ids, img, rows))
+                            mb_ent.append(ent.mean())
+                        else:
+                            logp, _, vpred = model(ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), **self._rows_images(ids, img, rows))
                         dlogp, dvpred = torch.empty_like(logp), torch.empty_like(vpred)
                         st = torch.empty(17, dtype=torch.float32, device=dev)
                         _hip.call("vlr_ppo_loss", logp.detach(), vpred.detach(), old_logp[tok_idx], old_values[tok_idx], adv[tok_idx], ret[tok_idx],
@@ -1768,6 +1783,9 @@ class VLPPOTrainer(VLOnlineRLTrainer):
             "tokens/queries_len_mean": sum(qlen) / n, "tokens/responses_len_mean": sum(rlen) / n,
             "ppo/learning_rate": float(cfg.learning_rate),
         }
+        if cfg.log_entropy:
+            stats["ppo/policy/entropy"] = float(torch.stack(mb_ent).mean())
+            stats["objective/entropy"] = sequence_neg_logp_mean(old_logp, seq_off)
         self.kl_ctl.update(a[0], cfg.batch_size)
         self.state.global_step += 1
         if self.keep_rollout:
@@ -1784,7 +1802,12 @@ class GRPOConfig:
     """Group Relative Policy Optimization: batch_size prompts (P) per step, num_generations samples (G) per prompt, P * G rows per
     step(); mini_batch_size rows per forward, mini_batch_size * gradient_accumulation_steps rows per optimizer step; num_iterations
     optimisation passes over one step's rows.  epsilon / epsilon_high bound the ratio at 1 - epsilon and 1 + epsilon_high (None:
-    epsilon); beta weighs the per-token KL estimate against the reference (0: no reference pass at all)."""
+    epsilon); beta weighs the per-token KL estimate against the reference (0: no reference pass at all).
+    The policy entropy, from the lm-head pass the log-probs come from (all three off by default: the step is then launch for launch the
+    one without them): log_entropy adds "grpo/entropy", the token-mean entropy of the training forward; top_entropy_quantile = q in
+    (0, 1] restricts the policy term to the tokens of a minibatch whose entropy is at least the (1 - q) quantile of the minibatch's
+    (trl's get_high_entropy_mask; 1: no mask) and adds "grpo/entropy_kept_frac"; entropy_coef subtracts entropy_coef * H_t from every
+    token's loss."""
     learning_rate: float = 1e-6
     batch_size: int = 4
     num_generations: int = 8
@@ -1807,10 +1830,15 @@ class GRPOConfig:
     local_rank: int = -1
     save_steps: int = 0
     resume_from_checkpoint: Optional[str] = None
+    log_entropy: bool = False
+    top_entropy_quantile: float = 1.0
+    entropy_coef: float = 0.0
 
     def __post_init__(self):
         if self.batch_size < 1:
             raise ValueError(f"batch_size ({self.batch_size}) must be at least 1 prompt")
+        if not 0.0 < float(self.top_entropy_quantile) <= 1.0:
+            raise ValueError(f"top_entropy_quantile ({self.top_entropy_quantile}) must lie in (0, 1]")
         if self.num_generations < 2:
             raise ValueError(f"num_generations ({self.num_generations}) must be at least 2: the advantage is the reward standardised inside "
                              "its group")
@@ -1833,6 +1861,13 @@ class GRPOConfig:
             raise ValueError("per_device_gamelog_size should be less than batch_size * num_generations")
 
 
+def high_entropy_mask(entropy, q):
+    """trl's get_high_entropy_mask over one minibatch's R tokens: keep [R] uint8 = entropy >= torch.quantile(entropy, 1 - q) (linear
+    interpolation; the entropy detached), on the tensor's device and without a host sync - a tie with the threshold is kept"""
+    h = entropy.detach().float()
+    return (h >= torch.quantile(h, 1.0 - float(q))).to(torch.uint8)
+
+
 class VLGRPOTrainer(VLOnlineRLTrainer):
     """The GRPO step on the HIP engine (include/vlr.h "GRPO"): every prompt gets G samples from ONE call of the model's generate
     (num_return_sequences = G: one prefill per prompt, one decode batch), every sample one scalar reward, the advantage is the reward
@@ -1843,7 +1878,8 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
     and the gradient still flows - and the reference log-probs when beta != 0 (the adapters switched off under LoRA, else a frozen copy).
 
     Deliberate differences from trl's GRPOTrainer: the rows of a step are walked in generation order, never permuted; the image inputs
-    are expanded per row, so the vision tower runs again on a repeated image; no entropy statistics; no-grad passes in eval mode;
+    are expanded per row, so the vision tower runs again on a repeated image; no-grad passes in eval mode; the entropy mask's quantile
+    is taken per minibatch (top_entropy_quantile);
     scores come from a reward model (VLRewardModel.score) or from `reward_fn(queries_text, responses_text) -> list of floats`;
     world_size > 1 is refused: it has never been run."""
 
@@ -2011,6 +2047,8 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
             seq_off.append(seq_off[-1] + L)
         need_old = cfg.num_iterations > 1 or N > bbs
         need_ref = cfg.beta != 0
+        q_ent, coef_ent = float(cfg.top_entropy_quantile), float(cfg.entropy_coef)
+        use_ent = bool(cfg.log_entropy) or q_ent < 1.0 or coef_ent != 0.0      # any of the three: the lm-head pass with the entropy
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.time_phases else None
         if ev:
             ev[0].record()
@@ -2048,7 +2086,7 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
         upstream = 1.0 / cfg.gradient_accumulation_steps
         eps_high = cfg.epsilon if cfg.epsilon_high is None else cfg.epsilon_high
         mcl = int(cfg.max_new_tokens) if cfg.max_new_tokens is not None else 0
-        mb_stats = []
+        mb_stats, mb_ent = [], []
         try:
             for _ in range(cfg.num_iterations):
                 for b0 in range(0, N, bbs):
@@ -2057,15 +2095,35 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
                         rows = list(range(m0, m0 + mbs))
                         t0, t1 = seq_off[m0], seq_off[m0 + mbs]
                         so = torch.tensor([x - t0 for x in seq_off[m0:m0 + mbs + 1]], dtype=torch.int32, device=dev)
-                        logp = token_logps(model, ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), **self._rows_images(ids, img, rows))
+                        logp = token_logps(model, ids[rows].to(dev), mask[rows].to(dev), labels[rows].to(dev), return_entropy=use_ent,
+                                           **self._rows_images(ids, img, rows))
+                        ent = None
+                        if use_ent:
+                            logp, ent = logp
                         if logp.numel() != t1 - t0:
                             raise RuntimeError(f"step: {logp.numel()} response rows for {t1 - t0} response tokens")
                         dlogp = torch.empty_like(logp)
-                        st = torch.empty(8, dtype=torch.float32, device=dev)
-                        _hip.call("vlr_grpo_loss", logp.detach(), old_logp[t0:t1] if need_old else None, ref_logp[t0:t1] if need_ref else None,
-                                  adv[m0:m0 + mbs], so, t1 - t0, mbs, float(cfg.epsilon), float(eps_high), float(cfg.beta),
-                                  GRPO_LOSS_TYPES[cfg.loss_type], mcl, upstream, dlogp, st)
-                        logp.backward(dlogp)
+                        if not use_ent:
+                            st = torch.empty(8, dtype=torch.float32, device=dev)
+                            _hip.call("vlr_grpo_loss", logp.detach(), old_logp[t0:t1] if need_old else None, ref_logp[t0:t1] if need_ref else None,
+                                      adv[m0:m0 + mbs], so, t1 - t0, mbs, float(cfg.epsilon), float(eps_high), float(cfg.beta),
+                                      GRPO_LOSS_TYPES[cfg.loss_type], mcl, upstream, dlogp, st)
+                            logp.backward(dlogp)
+                        else:
+                            keep = None
+                            if q_ent < 1.0:      # trl's get_high_entropy_mask on the minibatch's tokens; stays on the device
+                                keep = high_entropy_mask(ent, q_ent)
+                            st = torch.empty(10, dtype=torch.float32, device=dev)
+                            dent = torch.empty_like(logp)
+                            _hip.call("vlr_grpo_loss_ent", logp.detach(), old_logp[t0:t1] if need_old else None,
+                                      ref_logp[t0:t1] if need_ref else None, adv[m0:m0 + mbs], so, t1 - t0, mbs, float(cfg.epsilon), float(eps_high),
+                                      float(cfg.beta), GRPO_LOSS_TYPES[cfg.loss_type], mcl, upstream, ent.detach(), keep, coef_ent, dlogp, dent, st)
+                            if self.keep_rollout:
+                                mb_ent.append((ent.detach(), keep))
+                            if coef_ent != 0.0:      # the bonus reaches the weights through the lm-head backward with the entropy term
+                                torch.autograd.backward([logp, ent], [dlogp, dent])
+                            else:
+                                logp.backward(dlogp)
                         mb_stats.append(st)
                     eng.optimizer_step(cfg.learning_rate, 0.9, 0.999, 1e-8, 0.0, cfg.max_grad_norm)
         finally:
@@ -2076,7 +2134,7 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
             self.last_timing = dict(nograd_ms=ev[0].elapsed_time(ev[1]), optimisation_ms=ev[1].elapsed_time(ev[2]))
         # ---- stats: one device-to-host copy
         flat = torch.cat([torch.stack(mb_stats).mean(0), astats]).tolist()
-        ms, a = flat[:8], flat[8:]
+        ms, a = flat[:-4], flat[-4:]
         stats = {
             "grpo/loss": ms[0], "grpo/kl": ms[1], "grpo/ratio": ms[5],
             "grpo/clip_ratio/low": ms[2], "grpo/clip_ratio/high": ms[3], "grpo/clip_ratio/region": ms[4],
@@ -2085,9 +2143,15 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
             "tokens/queries_len_mean": sum(float(q.numel()) for q in queries) / P, "tokens/responses_len_mean": sum(lens) / N,
             "grpo/learning_rate": float(cfg.learning_rate),
         }
+        if cfg.log_entropy:
+            stats["grpo/entropy"] = ms[8]
+        if q_ent < 1.0:
+            stats["grpo/entropy_kept_frac"] = ms[9]
         self.state.global_step += 1
         if self.keep_rollout:
             self.last_rollout = dict(old_logp=old_logp, ref_logp=ref_logp, seq_off=seq_off, advantages=adv, adv_stats=astats, minibatch_stats=mb_stats)
+            if use_ent:      # per minibatch: (entropy [R], keep [R] uint8 or None)
+                self.last_rollout["minibatch_entropy"] = mb_ent
         return stats
 
 

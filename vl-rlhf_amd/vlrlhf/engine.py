@@ -1397,9 +1397,10 @@ class LlavaHipEngine:
         return logits
 
     # ------------------------------------------------------------------------------------------------ log-probs
-    def logps_forward(self, ctx, labels, shared_mask=None, average=False, label_pad=-100, reduce_seq=True):
+    def logps_forward(self, ctx, labels, shared_mask=None, average=False, label_pad=-100, reduce_seq=True, entropy=False):
         """get_batch_logps on the lm-head restricted to the response rows (identical result: every other row is
-        multiplied by a zero mask in the reference, base/trainer.py:185-188).  Returns (logps [Bn], lp_ctx)."""
+        multiplied by a zero mask in the reference, base/trainer.py:185-188).  Returns (logps [Bn], lp_ctx).  entropy: the lm-head pass
+        with the row entropy (vlr_lmhead_logps_entropy_fwd: the same log-probs bit for bit) -> lp_ctx["entropy"] [R]."""
         Bn, S, M, H, V = ctx["Bn"], ctx["S"], ctx["M"], self.H, self.V
         ws = ctx["ws"]
         if tuple(labels.shape) != (Bn, S):
@@ -1430,7 +1431,13 @@ class LlavaHipEngine:
         logits = None if fused else self._buf(("logits", ctx["tag"], R), (R, V), torch.float32)
         tok = torch.empty(R, dtype=torch.float32, device=self.dev)
         lse = torch.empty(R, dtype=torch.float32, device=self.dev)
-        _hip.call("vlr_lmhead_logps_fwd", hg, ws.v["lm_head"], tgt, tok, lse, lws, logits, R, V, H)
+        if entropy:
+            ews = self._buf(("lmhead_ent_ws", ctx["tag"], R), (int(_hip.lib().vlr_lmhead_entropy_workspace_bytes(R, V)),), torch.uint8)
+            ent = torch.empty(R, dtype=torch.float32, device=self.dev)
+            _hip.call("vlr_lmhead_logps_entropy_fwd", hg, ws.v["lm_head"], tgt, tok, lse, ent, ews, logits, R, V, H)
+            lp["entropy"] = ent
+        else:
+            _hip.call("vlr_lmhead_logps_fwd", hg, ws.v["lm_head"], tgt, tok, lse, lws, logits, R, V, H)
         if reduce_seq:
             _hip.call("vlr_seq_sum", tok, seq_off, Bn, int(average), logps)
         lp.update(hg=hg, lse=lse, tok=tok)
@@ -1549,18 +1556,19 @@ class LlavaHipEngine:
             t = self._ws[("row_range",)] = torch.arange(max(n, 4096), dtype=torch.int32, device=self.dev)
         return t[:n]
 
-    def token_logps_forward(self, ctx, labels, label_pad=-100):
+    def token_logps_forward(self, ctx, labels, label_pad=-100, entropy=False):
         """per-token log-probs on the R response rows (the rows whose logits predict a label != label_pad): the fused lm-head of
         logps_forward(reduce_seq=False).  Needs no value head.  Returns (tok_logp [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the
-        sequences."""
-        _, lp = self.logps_forward(ctx, labels, None, False, label_pad, reduce_seq=False)
+        sequences.  entropy: lp_ctx["entropy"] [R] fp32 beside lp_ctx["tok"], from the same lm-head pass; the log-probs keep their bits."""
+        _, lp = self.logps_forward(ctx, labels, None, False, label_pad, reduce_seq=False, entropy=entropy)
         if lp["R"] == 0:
             raise ValueError("token_logps_forward: no response token in this (mini)batch - every label is the padding label")
         return lp["tok"], lp
 
-    def _token_logps_dhg(self, lp, dlogp):
+    def _token_logps_dhg(self, lp, dlogp, dent=None):
         """d tok_logp [R] -> the gathered d hg [R][H] and the lm_head weight gradient (full fine-tune): logps_backward's lm-head backward
-        with every row its own sequence, then the two lm-head GEMMs"""
+        with every row its own sequence, then the two lm-head GEMMs.  dent [R]: the gradient of the row entropies as well
+        (vlr_lmhead_logps_entropy_bwd; the forward must have been asked for the entropy)"""
         ctx = lp["ctx"]
         H, V, R = self.H, self.V, lp["R"]
         acc = int(not self.grad_fresh)
@@ -1568,8 +1576,12 @@ class LlavaHipEngine:
         lws = self._buf(("lmhead_ws", ctx["tag"], R), (int(_hip.lib().vlr_lmhead_workspace_bytes(R, V)),), torch.uint8)
         logits = None if fused else self._buf(("logits", ctx["tag"], R), (R, V), torch.float32)
         dl = self._buf(("dlogits", R), (R, V))
-        _hip.call("vlr_lmhead_logps_bwd", lp["hg"], ctx["ws"].v["lm_head"], lp["tgt"], lp["lse"], self._row_range(R + 1), R,
-                  dlogp.to(torch.float32).contiguous(), 0, dl, lws, logits, R, V, H)
+        if dent is not None:
+            _hip.call("vlr_lmhead_logps_entropy_bwd", lp["hg"], ctx["ws"].v["lm_head"], lp["tgt"], lp["lse"], lp["entropy"],
+                      dlogp.to(torch.float32).contiguous(), dent.to(torch.float32).contiguous(), dl, lws, logits, R, V, H)
+        else:
+            _hip.call("vlr_lmhead_logps_bwd", lp["hg"], ctx["ws"].v["lm_head"], lp["tgt"], lp["lse"], self._row_range(R + 1), R,
+                      dlogp.to(torch.float32).contiguous(), 0, dl, lws, logits, R, V, H)
         dhg = torch.empty(R, H, dtype=BF16, device=self.dev)
         _hip.call("vlr_gemm_bf16", 1, dl, ctx["ws"].v["lm_head"], dhg, None, None, R, H, V, V, H, H, 0, 0, 0, 0)
         if self.lora is None:                 # under LoRA the lm_head is frozen (not a target module)
@@ -1583,18 +1595,20 @@ class LlavaHipEngine:
             self.reducer.bucket_ready("lm_head")
         return dhidden
 
-    def token_logps_backward(self, lp, dlogp):
-        """d tok_logp [R] -> d hidden (dense [M,H], zero outside the response rows) and the lm_head weight gradient (full fine-tune)"""
+    def token_logps_backward(self, lp, dlogp, dent=None):
+        """d tok_logp [R] (and d entropy [R]) -> d hidden (dense [M,H], zero outside the response rows) and the lm_head weight gradient
+        (full fine-tune)"""
         if lp["R"] == 0:
             raise ValueError("token_logps_backward: no response token in this (mini)batch")
         dhidden = torch.zeros(lp["ctx"]["M"], self.H, dtype=BF16, device=self.dev)
-        return self._scatter_dhg(lp, self._token_logps_dhg(lp, dlogp), dhidden)
+        return self._scatter_dhg(lp, self._token_logps_dhg(lp, dlogp, dent), dhidden)
 
-    def ppo_forward(self, ctx, labels, label_pad=-100):
+    def ppo_forward(self, ctx, labels, label_pad=-100, entropy=False):
         """per-token log-probs and values on the R response rows (the rows whose logits predict a label != label_pad; trl reads
         values[:, :-1] under the same mask): token_logps_forward and vlr_rm_head_fwd with the value head on the same gathered rows.
-        Returns (tok_logp [R] fp32, values [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the sequences."""
-        tok, lp = self.token_logps_forward(ctx, labels, label_pad)
+        Returns (tok_logp [R] fp32, values [R] fp32, lp_ctx); lp_ctx["seq_off"] delimits the sequences.  entropy: lp_ctx["entropy"] [R]
+        as in token_logps_forward (a statistic: PPO has no entropy gradient)."""
+        tok, lp = self.token_logps_forward(ctx, labels, label_pad, entropy)
         R = lp["R"]
         w, b, _, _ = self.v_head_views()
         values = torch.empty(R, dtype=torch.float32, device=self.dev)
