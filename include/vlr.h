@@ -523,6 +523,42 @@ int vlr_grpo_loss_ent(const float* logp, const float* old_logp, const float* ref
                       const float* entropy, const unsigned char* keep, float entropy_coef, float* dlogp, float* dent, float* stats,
                       vlr_stream_t stream);
 
+/* ---- sampling: the next token of every row of a generate batch, chosen on the device (additive entry point, vlr_abi_version() does
+ *      not move).  One launch per new token on the fp32 logits the lm-head left in HBM; nothing allocates, the logits are never written.
+ * vlr_sample_tokens: logits [B][ld] fp32 (ld >= V, 1 <= V < 2^24).  Per row r with unfinished[r] != 0, in this order:
+ *   1. repetition penalty (transformers RepetitionPenaltyLogitsProcessor; repetition_penalty > 0, 1 = none): every id of the row's
+ *      history - the T ids of prompt row r / prompt_div of prompt_ids [ceil(B / prompt_div)][prompt_ld] int64, pads included as
+ *      transformers does, and the first n_gen columns of row r of gen_ids [B][gen_ld] int64 - gets z = z < 0 ? z * pen : z / pen, ONCE
+ *      however often it occurs (a V-bit membership map in LDS: V <= 2^19 with a penalty; ids outside [0, V) are ignored).
+ *   2. temperature (> 0), when do_sample: z = z / temperature, an fp32 division.  1 and 2 are single correctly rounded fp32 operations.
+ *   3. top-k, when do_sample and 0 < top_k < V: keep z >= the k-th largest z; everything tied with the k-th is kept.
+ *   4. top-p, when do_sample and top_p < 1 (top_p in (0, 1]): over the survivors of 3, p = softmax(z); a token is kept iff the mass of
+ *      the tokens with STRICTLY greater z is < top_p.  This is transformers' TopPLogitsWarper (min_tokens_to_keep = 1) wherever no tie
+ *      straddles the cut, and keeps the whole tie group where one does (transformers cuts through it in sort order).
+ *   5. the draw, Gumbel-max over the kept set: tok = argmax_i (z_i + g_i), the lowest index on an exact tie; g_i = -log(-log u_i),
+ *      u_i = ((w_i >> 8) + 1/2) 2^-24, w_i = word i % 4 of Philox4x32-10 with the counter (i / 4, row_id, step, call) and the two halves
+ *      of `seed` as its key (low half first); row_id = row_ids[r], or r when row_ids is NULL.  A draw depends on (seed, call, row_id,
+ *      step, i) alone - not on B, the row's place in the launch or any reduction order.  The 24-bit uniform truncates the Gumbel
+ *      variate at +17.33 and -2.85 (a token whose probability is below e^-20 of the mode's is never drawn), which is the second
+ *      deliberate difference from transformers' inverse-CDF torch.multinomial.  Greedy (do_sample = 0): tok = argmax z after step 1
+ *      only, the lowest index on ties, the kept set is every column, no random numbers.
+ *   6. logp[r] = z_tok - logsumexp(z over the kept set): the score of transformers' compute_transition_scores.
+ *   7. next_tok[r] = tok (int32: what the decode step consumes) and out_ids[r * out_ld + step] = tok (int64: the caller's ids, which
+ *      may be gen_ids itself - history columns are read before the write); when tok is one of the n_eos <= 8 ids of eos_ids (device,
+ *      int32): unfinished[r] = 0 and finish_step[r] = step.  The eos itself is emitted.
+ *   A row with unfinished[r] == 0 gets pad in both places and logp 0, draws nothing, and its flags and kept row stay as they are.
+ *   kept (NULL in production; [B][V] bytes): 1 where the column survived the warpers, else 0.
+ *   One workgroup of 1024 threads per row; thresholds by 16-way bisection on the order-preserving integer image of z (counts for
+ *   top-k, masses for top-p: up to 9 passes over the row each, no sort, no workspace).  No floating-point atomics: every float sum
+ *   runs per thread over its 4-column groups in ascending order, then six xor butterflies, then the 16 waves in order - fixed by V and
+ *   the geometry, so two calls give the same bits.  Rows must hold at least one finite logit and no NaN.  Argument ranges are refused
+ *   before any launch. */
+int vlr_sample_tokens(const float* logits, int B, int V, int ld, int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, const int64_t* prompt_ids, int T, int prompt_ld, int prompt_div, const int64_t* gen_ids,
+                      int gen_ld, int n_gen, const int* eos_ids, int n_eos, int pad, uint64_t seed, uint32_t call, uint32_t step,
+                      const int* row_ids, unsigned char* unfinished, int* next_tok, int64_t* out_ids, int out_ld, float* logp,
+                      int* finish_step, unsigned char* kept, vlr_stream_t stream);
+
 /* ---- DPO loss, forward + backward (VLDPOTrainer.dpo_loss, base/trainer.py:244-301).
  * loss_type 0 sigmoid|ddpo, 1 hinge, 2 ipo, 3 kto_pair (losses has 2n entries).  dpc/dpr = d(sum_i g_i*loss_i)/d
  * policy_{chosen,rejected}_logps with g = grad_losses or 1/len(losses) when NULL (trl: loss = losses.mean()). */

@@ -251,20 +251,7 @@ __global__ __launch_bounds__(256) void merge_gather_f32_kernel(const int* __rest
 // NEFTune (transformers.trainer_utils.neftune_post_forward_hook): uniform noise on the TEXT rows of the merged embeddings, in place.
 // Counter-based: Philox4x32-10 (Salmon et al., SC'11) with counter = (column / 4, pre-merge token index b*T + t, call, pass) and the two
 // halves of `key` as its key, so a value depends on nothing but those - not on the launch geometry, not on the merged layout.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
-}
+// (philox4x32_10: common.h)
 // word -> noise: the top 24 bits r give h = r - (2^23 - 1/2) (exact in fp32: a half-integer below 2^23), n = h * scale rounded once.
 // scale = m 2^-23, so |n| < m, n is never 0 and the 2^24 values are symmetric about 0.  The sum x + n is a second, separate rounding:
 // contraction is switched off for the two operators below.  (Not __fmul_rn / __fadd_rn: hipcc's headers define them as the plain

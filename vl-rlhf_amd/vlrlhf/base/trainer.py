@@ -1270,6 +1270,9 @@ class PPOConfig:
     # policy's softmax over the minibatch's response rows (from the lm-head pass the log-probs come from), and "objective/entropy", the mean
     # over the sequences of sum_t -old_logp_t.  No bonus: trl's PPO has none.
     log_entropy: bool = False
+    # generate(sampler="device") with seed = config.seed + 2: one vlr_sample_tokens launch per token instead of the torch ops, the
+    # generation config's temperature / top_k honoured, a counter-based draw whose call counter rides in the checkpoint (off: unchanged)
+    device_sampler: bool = False
 
     def __post_init__(self):
         self.backward_batch_size = self.mini_batch_size * self.gradient_accumulation_steps
@@ -1387,6 +1390,27 @@ class VLOnlineRLTrainer:
     def _checkpoint_extra(self):
         """what the trainer adds to trainer_state.json (JSON-ready)"""
         return {}
+
+    def _sampling_model(self):
+        """the model whose generate samples (under a value head: the wrapped one), which owns the device sampler's call counter"""
+        return getattr(self.model, "pretrained_model", self.model)
+
+    def _device_sampler_kwargs(self, kw):
+        """config.device_sampler: generate's keywords for the device sampler, unless the caller set them"""
+        if getattr(getattr(self, "config", None), "device_sampler", False):
+            kw.setdefault("sampler", "device")
+            kw.setdefault("seed", int(self.config.seed) + 2)
+        return kw
+
+    def _sampler_state(self):
+        """the device sampler's part of the checkpoint: the count of sampled generate calls (the `call` word of its RNG counter)"""
+        if not getattr(self.config, "device_sampler", False):
+            return {}
+        return dict(sampler_calls=int(getattr(self._sampling_model(), "_sampler_calls", 0)))
+
+    def _restore_sampler_state(self, state):
+        if "sampler_calls" in state:
+            self._sampling_model()._sampler_calls = int(state["sampler_calls"])
 
     def _restore_extra(self, state, path):
         """the inverse of _checkpoint_extra, after the weights are loaded and before the optimizer state is"""
@@ -1523,6 +1547,7 @@ class VLOnlineRLTrainer:
         kw.update(generation_kwargs or {})
         if self.is_peft_model:
             kw.setdefault("merge_lora", False)
+        VLOnlineRLTrainer._device_sampler_kwargs(self, kw)
         queries = [q.reshape(-1).cpu().long() for q in queries]
         n = len(queries)
         if batch_size is None or int(batch_size) >= n:
@@ -1622,13 +1647,14 @@ class VLPPOTrainer(VLOnlineRLTrainer):
         model.engine.init_optimizer()
 
     def _checkpoint_extra(self):
-        return dict(kl_coef=float(self.kl_ctl.value), perm_generator=self._perm_gen.get_state().tolist())
+        return dict(kl_coef=float(self.kl_ctl.value), perm_generator=self._perm_gen.get_state().tolist(), **self._sampler_state())
 
     def _restore_extra(self, state, path):
         if not self.is_peft_model:      # (under LoRA load_adapter has read the head)
             self.model.load_v_head(path)
         self.kl_ctl.value = float(state["kl_coef"])
         self._perm_gen.set_state(torch.tensor(state["perm_generator"], dtype=torch.uint8))
+        self._restore_sampler_state(state)
 
     # ------------------------------------------------------------------------------------------ loop
     def train(self, resume_from_checkpoint=None):
@@ -1833,6 +1859,8 @@ class GRPOConfig:
     log_entropy: bool = False
     top_entropy_quantile: float = 1.0
     entropy_coef: float = 0.0
+    # generate(sampler="device") with seed = config.seed + 2 (see PPOConfig.device_sampler); off: the torch sampler on `_sample_gen`
+    device_sampler: bool = False
 
     def __post_init__(self):
         if self.batch_size < 1:
@@ -1906,13 +1934,15 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
         model.engine.init_optimizer()
 
     def _checkpoint_extra(self):
-        return dict(sample_generator=self._sample_gen.get_state().tolist(), num_generations=self.config.num_generations)
+        return dict(sample_generator=self._sample_gen.get_state().tolist(), num_generations=self.config.num_generations,
+                    **self._sampler_state())
 
     def _restore_extra(self, state, path):
         if int(state.get("num_generations", self.config.num_generations)) != self.config.num_generations:
             raise ValueError(f"resume_from_checkpoint: {path} was written with num_generations={state['num_generations']}, this run has "
                              f"{self.config.num_generations}")
         self._sample_gen.set_state(torch.tensor(state["sample_generator"], dtype=torch.uint8))
+        self._restore_sampler_state(state)
 
     # ------------------------------------------------------------------------------------------ rows of a group
     def _expand_queries(self, queries):
@@ -1944,6 +1974,7 @@ class VLGRPOTrainer(VLOnlineRLTrainer):
             kw["generation_config"] = gc = copy.copy(kw["generation_config"])
             gc.do_sample, gc.num_return_sequences = True, self.config.num_generations
         kw.setdefault("generator", self._sample_gen)
+        VLOnlineRLTrainer._device_sampler_kwargs(self, kw)
         if self.config.max_new_tokens is not None:
             kw.setdefault("max_new_tokens", int(self.config.max_new_tokens))
         if self.is_peft_model:

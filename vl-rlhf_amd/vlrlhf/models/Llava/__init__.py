@@ -244,6 +244,74 @@ def stop_hit(generated, stops):
     return hit
 
 
+class DeviceSampler:
+    """generate's per-token selection on the device (sampler="device"): ONE vlr_sample_tokens launch per new token (include/vlr.h
+    "sampling") does the logits-processor chain, the counter-based draw, the log-prob and the eos bookkeeping on the fp32 logits the
+    lm-head left in HBM.  Both routes of generate (KV cache and re-forward) select through select(); every buffer is allocated here,
+    once per call:
+      full [rows][limit] int64   prompt + generated ids; the kernel writes column T0 + step itself (no cat),
+      logp [limit - T0][rows]    the drawn tokens' log-probs, step-major so that one step's slice is contiguous (0 at pad positions),
+      unfinished [rows] uint8, finish [rows] int32 (the step at which a row finished, -1 while it runs), nxt [rows] int32 (what
+      decode_step consumes).
+    The penalty reads the prompt as `prompt` [rows / div][T0] through prompt_div = div (the num_return_sequences fan-out keeps one copy).
+    The RNG counter is (column / 4, row, step, call) under the key `seed`: a row's draw depends on its index in the expanded batch, the
+    step, the model's call counter and the seed - not on the batch around it.  Stop sequences are matched after the launch by stop_hit,
+    as on the torch path.  The host looks at `unfinished` every `sync_every` tokens only; result() trims to the column at which a
+    per-token check would have stopped, so the output is the same for every sync_every >= 1."""
+
+    def __init__(self, prompt, div, limit, do_sample, temperature, top_k, top_p, penalty, eos, pad, seed, call, stops=(), sync_every=8):
+        dev = prompt.device
+        P, T0 = prompt.shape
+        self.rows, self.T0, self.max_new, self.div = P * div, T0, limit - T0, div
+        self.prompt = prompt.contiguous()
+        self.full = torch.full((self.rows, limit), pad, dtype=torch.long, device=dev)
+        self.full[:, :T0] = prompt.repeat_interleave(div, 0) if div > 1 else prompt
+        self.gen = self.full[:, T0:]
+        self.logp = torch.zeros(max(self.max_new, 1), self.rows, dtype=torch.float32, device=dev)
+        self.unfinished = torch.ones(self.rows, dtype=torch.uint8, device=dev)
+        self.finish = torch.full((self.rows,), -1, dtype=torch.int32, device=dev)
+        self.nxt = torch.empty(self.rows, dtype=torch.int32, device=dev)
+        eos = sorted(int(e) for e in eos)
+        if len(eos) > 8:
+            raise ValueError(f'sampler="device" takes at most 8 eos ids, got {len(eos)}')
+        self.eos = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
+        self.n_eos = len(eos)
+        self.warp = (int(bool(do_sample)), float(temperature), int(top_k or 0), float(top_p), float(penalty))
+        self.pad, self.seed, self.call = int(pad), int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF
+        self.stops, self.keep = stops, max((s.numel() for s in stops), default=0)
+        self.sync_every = max(1, int(sync_every))
+        self.n = 0
+
+    def select(self, logits):
+        """logits fp32 [rows][V] (any row stride) -> the next tokens [rows] int32; column T0 + n of `full`, logp[n], unfinished and finish
+        are updated on the device"""
+        n = self.n
+        _hip.call("vlr_sample_tokens", logits, self.rows, logits.shape[1], logits.stride(0), *self.warp, self.prompt, self.T0, self.T0,
+                  self.div, self.gen, self.full.shape[1], n, self.eos, self.n_eos, self.pad, self.seed, self.call, n, None,
+                  self.unfinished, self.nxt, self.gen, self.full.shape[1], self.logp[n], self.finish, None)
+        self.n = n + 1
+        if self.stops:      # the stop tokens stay in the row; from the next position on it receives the pad id
+            hit = stop_hit(self.gen[:, max(0, self.n - self.keep):self.n], self.stops) & (self.unfinished != 0)
+            self.finish.masked_fill_(hit, n)
+            self.unfinished.masked_fill_(hit, 0)
+        return self.nxt
+
+    def done(self):
+        """the loop's end: the token budget, or (looked at every sync_every tokens: one host round trip) no row left unfinished"""
+        if self.n >= self.max_new:
+            return True
+        return self.n % self.sync_every == 0 and not bool(self.unfinished.any())
+
+    def result(self, output_logprobs=False):
+        """prompt + continuation ids [rows][T0 + cols] (and the log-probs [rows][cols]): cols = the column after which a per-token
+        check would have stopped - the last finish step + 1 when every row has finished, else all n"""
+        cols = self.n
+        if self.n and not bool(self.unfinished.any()):
+            cols = int(self.finish.max()) + 1
+        ids = self.full[:, :self.T0 + cols].contiguous()
+        return (ids, self.logp[:cols].t().contiguous()) if output_logprobs else ids
+
+
 class LlavaForRL(nn.Module):
     engine_cls = LlavaHipEngine
     image_count_key = "image_token"      # engine cfg key of the id that marks one image in input_ids (the online-RL trainers cut image inputs by it)
@@ -499,9 +567,10 @@ class LlavaForRL(nn.Module):
         return dict(generation_config=generation_config)
 
     @torch.no_grad()
-    def generate(self, input_ids=None, attention_mask=None, max_length=None, max_new_tokens=None, do_sample=False, temperature=1.0,
-                 top_k=50, top_p=1.0, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True,
-                 merge_lora=True, num_return_sequences=1, **img):
+    def generate(self, input_ids=None, attention_mask=None, max_length=None, max_new_tokens=None, do_sample=False, temperature=None,
+                 top_k=None, top_p=None, pad_token_id=None, eos_token_id=None, generation_config=None, generator=None, use_cache=True,
+                 merge_lora=True, num_return_sequences=1, sampler=None, repetition_penalty=None, seed=None, output_logprobs=False,
+                 sync_every=8, **img):
         """What the reference trainer's `get_batch_samples` calls (base/trainer.py:310-360: `model.generate(input_ids, attention_mask,
         max_length, do_sample=True, pad_token_id, **img_input_dict)`, transformers GenerationMixin defaults: temperature 1, top_k 50,
         top_p 1, use_cache True).  Prompts are LEFT-padded (trl's collator; the merge of the reference end-aligns such rows) and padded
@@ -538,8 +607,47 @@ class LlavaForRL(nn.Module):
           eos_token_id (int or list; the keyword wins), pad_token_id (the keyword wins), and stop_words_ids, a list of token-id lists: a
           row is finished once the tokens GENERATED in this call end with one of the sequences (the prompt never counts).  The stop
           tokens stay in the output and later positions receive the pad id, as after an eos.  Both routes and every fan-out check it with
-          tensor compares of the last k generated tokens (stop_hit): no host synchronisation beyond the loop's `unfinished.any()`."""
+          tensor compares of the last k generated tokens (stop_hit): no host synchronisation beyond the loop's `unfinished.any()`.
+
+        sampler = "torch" (default; also read from generation_config.sampler): the selection above, stock torch ops, temperature 1 /
+          top_k 50 / top_p 1 unless the keywords say otherwise (a generation_config's warper settings are NOT read on this path).
+        sampler = "device": the selection is one vlr_sample_tokens launch per token (DeviceSampler) on both routes, greedy included.
+          temperature / top_k / top_p / repetition_penalty come from the keyword, else from the generation_config, else 1 / 50 / 1 / 1;
+          out-of-range values raise ValueError in transformers' words.  repetition_penalty (transformers'
+          RepetitionPenaltyLogitsProcessor over the prompt ids, pads included, and the generated ones), seed (None: the generator's
+          initial seed, else torch.initial_seed()) and output_logprobs=True (-> (ids, logps [rows][new tokens]), the score transformers'
+          compute_transition_scores gives, 0 at pad positions) exist on this path only: with sampler="torch" they raise.  The draw is
+          counter-based (seed, self._sampler_calls, row p * n + j, step): the same prompt row draws the same tokens whatever the batch
+          around it; self._sampler_calls counts the device-sampled generate calls (save / restore it with a checkpoint).  The host
+          reads `unfinished` every sync_every tokens (1 = the per-token cadence); the output does not depend on it."""
         stop_words = None
+        if sampler is None:
+            sampler = getattr(generation_config, "sampler", None) or "torch"
+        if sampler not in ("torch", "device"):
+            raise ValueError(f'sampler has to be "torch" or "device", got {sampler!r}')
+        if sampler == "torch":
+            for name, given in (("repetition_penalty", repetition_penalty is not None and float(repetition_penalty) != 1.0),
+                                ("output_logprobs", bool(output_logprobs)), ("seed", seed is not None)):
+                if given:
+                    raise ValueError(f'{name} needs sampler="device": the torch sampler does not implement it')
+        else:
+            gc = generation_config
+            temperature = temperature if temperature is not None else getattr(gc, "temperature", None)
+            top_k = top_k if top_k is not None else getattr(gc, "top_k", None)
+            top_p = top_p if top_p is not None else getattr(gc, "top_p", None)
+            repetition_penalty = repetition_penalty if repetition_penalty is not None else getattr(gc, "repetition_penalty", None)
+        temperature = 1.0 if temperature is None else temperature
+        top_k = 50 if top_k is None else top_k
+        top_p = 1.0 if top_p is None else top_p
+        repetition_penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        if sampler == "device":
+            if not float(temperature) > 0:
+                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token scores "
+                                 "will be invalid.")
+            if not 0 < float(top_p) <= 1.0:
+                raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+            if not repetition_penalty > 0:
+                raise ValueError(f"`penalty` has to be a strictly positive float, but is {repetition_penalty}")
         if generation_config is not None:
             max_new_tokens = max_new_tokens if max_new_tokens is not None else getattr(generation_config, "max_new_tokens", None)
             do_sample = bool(getattr(generation_config, "do_sample", do_sample))
@@ -578,17 +686,36 @@ class LlavaForRL(nn.Module):
         was_training = self.training
         self.eval()
         lm_head = self.weights.v["lm_head"]
-        if use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128:
-            try:        # (fanout / stops are passed only when set: a call without them is today's call, argument for argument)
-                return self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img,
-                                             self.cached_lora_route(merge_lora), **({"fanout": fanout} if fanout > 1 else {}),
-                                             **({"stops": stops} if stops else {}))
+        cached = use_cache and getattr(self.engine, "supports_kv_cache", False) and self.engine.hd == 128
+        dsamp = None
+        if sampler == "device" and T0 >= limit and output_logprobs:      # nothing to generate: the ids as below, and no log-probs
+            self.train(was_training)
+            return (ids.repeat_interleave(fanout, 0) if fanout > 1 else ids), torch.zeros(B * fanout, 0, dtype=torch.float32, device=dev)
+        if sampler == "device" and T0 < limit:
+            if seed is None:
+                seed = generator.initial_seed() if generator is not None else torch.initial_seed()
+            call = getattr(self, "_sampler_calls", 0)
+            div = fanout if cached else 1      # the re-forward route expands the prompt rows below: nothing to share
+            dsamp = DeviceSampler(ids if div == fanout else ids.repeat_interleave(fanout, 0), div, limit, do_sample, temperature, top_k, top_p,
+                                  repetition_penalty, eos, pad, seed, call, stops, sync_every)
+            self._sampler_calls = call + 1
+        if cached:
+            try:        # (fanout / stops / sampler are passed only when set: a call without them is today's call, argument for argument)
+                out = self._generate_cached(ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img,
+                                            self.cached_lora_route(merge_lora), **({"fanout": fanout} if fanout > 1 else {}),
+                                            **({"stops": stops} if stops else {}), **({"sampler": dsamp} if dsamp is not None else {}))
+                return dsamp.result(output_logprobs) if dsamp is not None else out
             finally:
                 self.train(was_training)
         if fanout > 1:      # no shared cache on this route: the transformers expansion, sample j of prompt p at row p * n + j
             ids, mask = ids.repeat_interleave(fanout, 0), mask.repeat_interleave(fanout, 0)
             img = {k: self._expand_rows(v, B, fanout) for k, v in img.items()}
             B = B * fanout
+        if dsamp is not None:
+            try:
+                return self._generate_reforward_device(dsamp, mask, pad, img, lm_head).result(output_logprobs)
+            finally:
+                self.train(was_training)
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         try:
             while ids.shape[1] < limit and bool(unfinished.any()):
@@ -615,6 +742,24 @@ class LlavaForRL(nn.Module):
         finally:
             self.train(was_training)
         return ids
+
+    def _generate_reforward_device(self, ds, mask, pad, img, lm_head):
+        """the re-forward loop with the device sampler: the ids grow inside ds.full (the kernel writes each new column), the mask inside a
+        buffer allocated once; only the engine's input is assembled per token, as above"""
+        dev, B, T = self.engine.dev, ds.rows, ds.T0
+        fmask = torch.cat([mask, torch.ones(B, ds.max_new, dtype=mask.dtype, device=dev)], 1)
+        while True:
+            Tp = (T + 31) // 32 * 32
+            if Tp != T:                   # left padding: masked out, and the merged rows stay end-aligned
+                fill = torch.full((B, Tp - T), pad, dtype=torch.long, device=dev)
+                run_ids, run_mask = torch.cat([fill, ds.full[:, :T]], 1), torch.cat([torch.zeros_like(fill, dtype=fmask.dtype), fmask[:, :T]], 1)
+            else:
+                run_ids, run_mask = ds.full[:, :T].contiguous(), fmask[:, :T].contiguous()
+            out = self(input_ids=run_ids, attention_mask=run_mask, labels=None, use_cache=False, **img)
+            ds.select(self._last_logits(out.logits.c, B, lm_head))
+            T += 1
+            if ds.done():
+                return ds
 
     @staticmethod
     def _expand_rows(v, B, n):
@@ -647,12 +792,14 @@ class LlavaForRL(nn.Module):
             return "plain"
         return "merged" if (merge_lora and not self.is_packed) else "live"
 
-    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, fanout=1, stops=()):
+    def _generate_cached(self, ids, mask, limit, do_sample, temperature, top_k, top_p, pad, eos, generator, img, route, fanout=1, stops=(),
+                         sampler=None):
         """generate's KV-cache path: the prefill is the first iteration of the re-forward loop (same padded input, same lm-head
         call) with the K / V rows kept; each further token is one engine.decode_step.  route: cached_lora_route().
         stops: stop_sequences() of the generation config - a row whose generated tokens end with one is finished (stop_hit).
         fanout > 1 (num_return_sequences): the prefill fills the prompt segment of a SharedPromptKVCache, its logits are repeated
-        `fanout` times and the B * fanout samples decode over the shared prompt K / V."""
+        `fanout` times and the B * fanout samples decode over the shared prompt K / V.
+        sampler: a DeviceSampler - every selection is its one launch and the caller reads the result from it (None: the torch ops below)."""
         eng, dev = self.engine, self.engine.dev
         B, T = ids.shape
         unfinished = torch.ones(B * fanout, dtype=torch.bool, device=dev)
@@ -685,6 +832,12 @@ class LlavaForRL(nn.Module):
             logits = logits.repeat_interleave(fanout, 0)
             out = [ids.repeat_interleave(fanout, 0)]
         n = T
+        if sampler is not None:
+            while True:
+                nxt = sampler.select(logits)
+                if sampler.done():
+                    return sampler.full
+                logits = eng.decode_step(ws, nxt, cache)
         if stops:
             keep = max(s.numel() for s in stops)
             tail = torch.empty(B * fanout, 0, dtype=torch.long, device=dev)
