@@ -29,8 +29,12 @@ extern "C" int vlr_layers_join(vlr_stream_t stream) {
 static int norm_fwd(int f32, const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, hipStream_t st) {
     return f32 ? vlr_rmsnorm_fwd_f32((const float*)x, w, y, rstd, M, H, eps, st) : vlr_rmsnorm_fwd(x, w, y, rstd, M, H, eps, st);
 }
+// src_rows != NULL: x and rstd are read at src_rows[row] (the kept rows in place, vlr_decoder_layer_bwd_src)
 static int norm_bwd(int f32, const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
-                    int acc, void* ws, int M, int H, hipStream_t st) {
+                    int acc, void* ws, const int* src_rows, int M, int H, hipStream_t st) {
+    if (src_rows)
+        return f32 ? vlr_rmsnorm_bwd_f32_src(dy, (const float*)x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st)
+                   : vlr_rmsnorm_bwd_src(dy, x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st);
     return f32 ? vlr_rmsnorm_bwd_f32(dy, (const float*)x, w, rstd, dres, dx, dw, acc, ws, M, H, st)
                : vlr_rmsnorm_bwd(dy, x, w, rstd, dres, dx, dw, acc, ws, M, H, st);
 }
@@ -43,24 +47,47 @@ static int proj_res(int f32, const void* a, const void* W, void* y, const void* 
 static inline const char* off(const void* p, size_t elems) { return (const char*)p + elems * 2; }
 static inline char* off(void* p, size_t elems) { return (char*)p + elems * 2; }
 
+// The shapes of a layer pass over M = batch * S token rows: kvh key / value heads (grouped-query attention), the fused q|k|v row
+// [Nq | Nkv | Nkv] = N columns, rf = the fp32 residual stream
+struct LayerDims { int H, I, M, kvh, Nq, Nkv, N, rf; };
+static LayerDims dims_of(const vlr_llama_cfg* cfg, int M) {
+    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim;
+    return LayerDims{cfg->hidden, cfg->inter, M, kvh, Nq, Nkv, Nq + 2 * Nkv, cfg->resid_f32};
+}
+static int layer_dims(const char* who, const vlr_llama_cfg* cfg, int batch, int S, LayerDims* L) {
+    *L = dims_of(cfg, batch * S);
+    VLR_REQUIRE(L->kvh > 0 && cfg->heads % L->kvh == 0, "%s: heads %d is not a multiple of kv_heads %d", who, cfg->heads, L->kvh);
+    return VLR_OK;
+}
+// causal attention over the dense layout: qkv [M][N] holds the q | k | v column blocks (RoPE applied), attn / dattn are [M][Nq]
+static int attn_fwd(const vlr_llama_cfg* cfg, const LayerDims& L, const void* qkv, void* attn, float* lse, const int* key_mask, int batch,
+                    int S, hipStream_t st) {
+    return vlr_attn_fwd_gqa(qkv, off(qkv, L.Nq), off(qkv, (size_t)L.Nq + L.Nkv), L.N, attn, L.Nq, lse, key_mask, batch, S, cfg->heads, L.kvh,
+                            cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st);
+}
+static int attn_bwd(const vlr_llama_cfg* cfg, const LayerDims& L, const void* qkv, const void* attn, const void* dattn, const float* lse,
+                    float* delta, const int* key_mask, void* dqkv, int batch, int S, hipStream_t st) {
+    return vlr_attn_bwd_gqa(qkv, off(qkv, L.Nq), off(qkv, (size_t)L.Nq + L.Nkv), L.N, attn, dattn, L.Nq, lse, delta, key_mask, dqkv,
+                            off(dqkv, L.Nq), off(dqkv, (size_t)L.Nq + L.Nkv), L.N, batch, S, cfg->heads, L.kvh, cfg->head_dim, 1,
+                            1.0f / sqrtf((float)cfg->head_dim), st);
+}
+
 // keep_for_backward = 0 (no-grad reference / evaluation pass): tensors only the backward reads (gate | up) are not written
 extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                                         const void* x_in, const int* pos, const int* key_mask, int batch, int S,
                                         int keep_for_backward, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && a && x_in && pos, "vlr_decoder_layer_fwd: null argument");
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_fwd: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    const int rf = cfg->resid_f32;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd", cfg, batch, S, &L));
+    const auto [H, I, M, kvh, Nq, Nkv, N, rf] = L;
     CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, M, H, cfg->rms_eps, st));
     // q|k|v projection with RoPE applied to the fp32 accumulators in the GEMM epilogue (plain GEMM + rope kernel for the rows /
     // shapes the persistent kernel does not take)
     // (a bias of the fused projection - Qwen c_attn - is added to the accumulators before the rotation)
     CHECK(vlr_gemm_qkv_rope_bias(a->xn1, w->wqkv, w->bqkv, a->qkv, pos, cfg->rope_cos, cfg->rope_sin, M, N, Nq + Nkv, H, H, cfg->head_dim,
                                  cfg->max_pos, st));
-    CHECK(vlr_attn_fwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, Nq, a->lse, key_mask, batch, S,
-                           cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    CHECK(attn_fwd(cfg, L, a->qkv, a->attn, a->lse, key_mask, batch, S, st));
     CHECK(proj_res(rf, a->attn, w->wo, a->x_mid, x_in, M, H, Nq, st));
     CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
     // gate|up projection with act = silu(gate) * up computed in the epilogue
@@ -75,26 +102,14 @@ extern "C" int vlr_decoder_layer_fwd_ex(const vlr_llama_cfg* cfg, const vlr_laye
 // the attention rows are read back through compact_rows; every other call is the entry point of vlr_decoder_layer_fwd_ex at Mc rows.
 int vlr_internal_gemm_res_peel(int f32, const void* a, const void* W, void* y, const void* res, int M, int N, int K, int peel_rows,
                                hipStream_t st);      // gemm.hip: proj_res with the rows of the 128x128 kernel named by the caller
-// gemm.hip: the three forward NT products with the A operand read through an M-side row map; gemm256p.hip: what a launch would pick
-extern "C" int vlr_gemm_qkv_rope_bias_rows(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv, const int* pos,
-                                           const float* cos_t, const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim,
-                                           int max_pos, hipStream_t stream);
-extern "C" int vlr_gemm_swiglu_rows(const void* x, const int* a_rows, const void* wgu, void* gu, void* act, int M, int I, int K, int ldx,
-                                    int store_gu, hipStream_t stream);
-extern "C" int vlr_gemm_res_rows(int f32, const void* a, const int* a_rows, const void* W, void* y, const void* res, int M, int N, int K,
-                                 int peel_rows, int tail_row0, hipStream_t stream);
-extern "C" int vlr_gemm_qkv_rope_bias_dst(const void* x, const int* a_rows, const void* wqkv, const void* bias, void* qkv_dst, const int* c_rows,
-                                          const int* c_twin, void* qkv_rows, const int* dense_src, int Md, const int* pos, const float* cos_t,
-                                          const float* sin_t, int M, int N, int rope_cols, int K, int ldx, int head_dim, int max_pos,
-                                          hipStream_t stream);
-extern "C" int vlr_gemm_swiglu_dst(const void* x, const int* a_rows, const void* wgu, void* gu, void* act_dst, const int* c_rows, const int* c_twin,
-                                   void* act_rows, const int* dense_src, int Md, int M, int I, int K, int ldx, int store_gu, hipStream_t stream);
+// gemm256p.hip: the kernel a launch would pick, as host arithmetic
 int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32);
 int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
+double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip: rounds vlr_gemm_bf16_tn_pair saves over two launches on the compute CUs of the moment
 // 1: the fused q|k|v + RoPE and gate|up + SwiGLU kernels take every row of this layer's shapes - what a row map on their A operand needs
-static int fused_take_all(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, int N, int Nq, int Nkv) {
-    return cfg->head_dim == 128 && (!w->bqkv || !((uintptr_t)w->bqkv & 7)) && vlr_internal_gemm256p_fused_takes(2, N, cfg->hidden, Nq + Nkv) &&
-           vlr_internal_gemm256p_fused_takes(1, 2 * cfg->inter, cfg->hidden, 0);
+static int fused_take_all(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const LayerDims& L) {
+    return cfg->head_dim == 128 && (!w->bqkv || !((uintptr_t)w->bqkv & 7)) && vlr_internal_gemm256p_fused_takes(2, L.N, L.H, L.Nq + L.Nkv) &&
+           vlr_internal_gemm256p_fused_takes(1, 2 * L.I, L.H, 0);
 }
 // attn_in_place: o_proj reads the kept rows of attn_dense through compact_rows where the persistent kernel takes the launch and the
 // peeled rows are the last dense rows (else, and always with attn_in_place = 0, they are compacted into a->attn first).
@@ -111,13 +126,11 @@ static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
                              int keep_for_backward, vlr_stream_t st, const int* dst_twin = nullptr, int act_dense = 0) {
     VLR_REQUIRE(cfg && w && a && x_in && pos_compact && dense_src && compact_rows && qkv_dense && attn_dense,
                 "vlr_decoder_layer_fwd_compact: null argument");
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
-    VLR_REQUIRE(batch > 0 && S > 0 && Mc > 0 && Mc <= M, "vlr_decoder_layer_fwd_compact: %d compact rows of %d x %d dense rows", Mc, batch, S);
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
+    VLR_REQUIRE(batch > 0 && S > 0 && Mc > 0 && Mc <= batch * S, "vlr_decoder_layer_fwd_compact: %d compact rows of %d x %d dense rows", Mc, batch, S);
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd_compact", cfg, batch, S, &L));
+    const auto [H, I, M, kvh, Nq, Nkv, N, rf] = L;
     VLR_REQUIRE(tail_rows >= 0 && tail_rows <= Mc, "vlr_decoder_layer_fwd_compact: %d tail rows of %d compact rows", tail_rows, Mc);
-    const int rf = cfg->resid_f32;
     // the two residual projections give their last tile rows to the 128x128 split-K kernel, which sums in another order than the
     // persistent kernel: the rows the DENSE launch peels are peeled here too (they are the last rows of both layouts when they lie
     // inside the kept tail), no others - each row is computed by the kernel the dense pass computes it in.  A dense peel that reaches
@@ -144,8 +157,7 @@ static int layer_fwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* 
         }
         CHECK(vlr_gather_rows(a->qkv, dense_src, qkv_dense, M, N, st));              // dense row m = compact row dense_src[m]
     }
-    CHECK(vlr_attn_fwd_gqa(qkv_dense, off(qkv_dense, Nq), off(qkv_dense, (size_t)Nq + Nkv), N, attn_dense, Nq, a->lse, key_mask, batch, S,
-                           cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
+    CHECK(attn_fwd(cfg, L, qkv_dense, attn_dense, a->lse, key_mask, batch, S, st));
     // o_proj straight from the dense attention rows: the rows the 128x128 kernel gets are the last rows of both layouts (peel_rows >= 0:
     // they lie in the kept tail) and reach it by a plain pointer
     if (attn_in_place && H > 512 && peel_rows >= 0 && peel_rows < Mc && vlr_internal_gemm256p_res_variant(Mc - peel_rows, H, Nq, rf) != 0) {
@@ -195,10 +207,9 @@ extern "C" int vlr_decoder_layer_fwd_compact_maps(const vlr_llama_cfg* cfg, cons
                                                   const int* key_mask, int batch, int S, int keep_for_backward, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && a && x_in && m, "vlr_decoder_layer_fwd_compact_maps: null argument");
     VLR_REQUIRE(m->compact_rows && m->dense_src && m->pos_compact, "vlr_decoder_layer_fwd_compact_maps: null row map");
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(kvh > 0 && cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact_maps: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim;
-    const int* dst_twin = m->twin && fused_take_all(cfg, w, Nq + 2 * Nkv, Nq, Nkv) ? m->twin : nullptr;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd_compact_maps", cfg, batch, S, &L));
+    const int* dst_twin = m->twin && fused_take_all(cfg, w, L) ? m->twin : nullptr;
     return layer_fwd_compact(cfg, w, a, x_in, m->pos_compact, m->dense_src, m->compact_rows, nullptr, keep_for_backward ? 0 : 1, m->Mc,
                              m->tail_rows, qkv_dense, attn_dense, key_mask, batch, S, keep_for_backward, st, dst_twin, 0);
 }
@@ -206,7 +217,6 @@ extern "C" int vlr_decoder_layer_fwd_compact_maps(const vlr_llama_cfg* cfg, cons
 // dropped row takes its twin's values, which ARE its values - the dense backward then runs unchanged on `d` and computes what it
 // computes after a dense forward.  q|k|v, attn and lse are not copied: the compact forward was given d->qkv / d->attn as its dense
 // scratch and d->lse as its lse.  keep_for_backward = 0 (a checkpointed pass): x_out alone
-extern "C" int vlr_gather_f32(const float* src, const int* idx, float* dst, int n, hipStream_t st);
 extern "C" int vlr_layer_acts_expand(const vlr_llama_cfg* cfg, const vlr_layer_acts* c, const vlr_layer_acts* d, const int* dense_src,
                                      int M, int keep_for_backward, vlr_stream_t st) {
     VLR_REQUIRE(cfg && c && d && dense_src && M > 0, "vlr_layer_acts_expand: null argument");
@@ -245,12 +255,11 @@ extern "C" int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, cons
                 "vlr_decoder_layer_fwd_compact_keep: the scratch set must not alias the layer's set");
     const int H = cfg->hidden, I = cfg->inter, M = batch * S;
     VLR_REQUIRE(H % 8 == 0 && I % 8 == 0, "vlr_decoder_layer_fwd_compact_keep: hidden %d and inter %d must be multiples of 8", H, I);
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(kvh > 0 && cfg->heads % kvh == 0, "vlr_decoder_layer_fwd_compact_keep: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd_compact_keep", cfg, batch, S, &L));
     // where the fused projections take every row (the 7B shapes; fused_take_all) the norms write xn1 / xn2 to their dense rows and the
     // projections read them through compact_rows; elsewhere they are written on Mc rows into `s` and copied
-    const int dense_xn = m->twin && fused_take_all(cfg, w, Nq + 2 * Nkv, Nq, Nkv);
+    const int dense_xn = m->twin && fused_take_all(cfg, w, L);
     // act on its dense rows: down_proj must take the row map - the persistent kernel for all rows but the dense launch's peeled ones, which
     // then have to be the last rows of both layouts (as for o_proj in layer_fwd_compact)
     const int dense_peel = vlr_gemm_peel_rows(M, H);
@@ -267,17 +276,12 @@ extern "C" int vlr_decoder_layer_fwd_compact_keep(const vlr_llama_cfg* cfg, cons
     if (!act_in_place) CHECK(vlr_gather_rows(s->act, m->dense_src, a->act, M, I, st));
     return VLR_OK;
 }
-// gemm256p.hip: the kernel a launch would pick, as host arithmetic
-int vlr_internal_gemm256p_res_variant(int M, int N, int K, int res_f32);
-int vlr_internal_gemm256p_fused_takes(int fuse, int N, int K, int rope_cols);
 extern "C" int vlr_decoder_layer_compact_exact(const vlr_llama_cfg* cfg, int batch, int S, int Mc, int tail_rows) {
     if (!cfg || batch <= 0 || S <= 0) return 0;
     const long Ml = (long)batch * S;
     if (Ml > 0x7fffffffL || Mc <= 0 || Mc > Ml || tail_rows < 0 || tail_rows > Mc) return 0;
-    const int M = (int)Ml, H = cfg->hidden, I = cfg->inter;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
+    const auto [H, I, M, kvh, Nq, Nkv, N, rf] = dims_of(cfg, (int)Ml);
     if (H <= 0 || I <= 0 || kvh <= 0 || cfg->heads % kvh != 0) return 0;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
     // q|k|v + RoPE and gate|up + SwiGLU: the fused kernel takes every row of any row count (its peeled tile rows run the same kernel), or
     // none - then the plain GEMM's route depends on the row count
     if (cfg->head_dim != 128 || !vlr_internal_gemm256p_fused_takes(2, N, H, Nq + Nkv) || !vlr_internal_gemm256p_fused_takes(1, 2 * I, H, 0))
@@ -293,47 +297,6 @@ extern "C" int vlr_decoder_layer_compact_exact(const vlr_llama_cfg* cfg, int bat
         if (vd == 0 || vd != vlr_internal_gemm256p_res_variant(Mc - peel, H, K, cfg->resid_f32)) return 0;
     }
     return 1;
-}
-// Backward of vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1): vlr_decoder_layer_bwd with every row-wise call at Mc rows, the
-// attention backward alone on the dense layout (include/vlr.h)
-double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip
-extern "C" int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
-                                             const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const vlr_row_maps* m,
-                                             const vlr_dense_scratch* d, const void* x_in, const void* dx_out, void* dx_in,
-                                             const int* key_mask, int batch, int S, vlr_stream_t st) {
-    VLR_REQUIRE(cfg && w && g && a && ws && m && d && x_in && dx_out && dx_in, "vlr_decoder_layer_bwd_compact: null argument");
-    VLR_REQUIRE(m->compact_rows && m->dense_src && m->dense_own && m->twin && m->pos_compact, "vlr_decoder_layer_bwd_compact: null row map");
-    VLR_REQUIRE(d->qkv && d->attn && d->dattn && d->dqkv, "vlr_decoder_layer_bwd_compact: null dense scratch");
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S, Mc = m->Mc;
-    VLR_REQUIRE(batch > 0 && S > 0 && Mc > 0 && Mc <= M, "vlr_decoder_layer_bwd_compact: %d compact rows of %d x %d dense rows", Mc, batch, S);
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    VLR_REQUIRE(cfg->heads % kvh == 0, "vlr_decoder_layer_bwd_compact: heads %d is not a multiple of kv_heads %d", cfg->heads, kvh);
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    // ---- MLP
-    CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, Mc, I, H, st));
-    CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, Mc, accumulate, st));
-    CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, Mc, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, Mc, H, st));
-    // ---- attention
-    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;      // (vlr_decoder_layer_bwd's rule, unchanged)
-    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, Mc, H, Nq, Nq, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, Mc, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
-    // a shared row's d attn is the sum of both branches' gradients already (downstream of it the two copies were one row): it enters at
-    // the chosen copy, the dropped copy gets dO = 0 - there delta = 0 and dS = P (dP - delta) = 0 exactly
-    CHECK(vlr_expand_rows_zero(ws->dattn, m->dense_own, d->dattn, M, Nq, st));
-    CHECK(vlr_gather_rows(a->qkv, m->dense_src, d->qkv, M, N, st));
-    CHECK(vlr_gather_rows(a->attn, m->dense_src, d->attn, M, Nq, st));
-    CHECK(vlr_attn_bwd_gqa(d->qkv, off(d->qkv, Nq), off(d->qkv, (size_t)Nq + Nkv), N, d->attn, d->dattn, Nq, a->lse, ws->delta,
-                           key_mask, d->dqkv, off(d->dqkv, Nq), off(d->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
-                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    // the rejected response rows' dK / dV on the prompt keys landed on the dropped rows: added to the chosen twin (fp32, one rounding)
-    CHECK(vlr_fold_rows(d->dqkv, m->compact_rows, m->twin, ws->dqkv, Mc, N, st));
-    CHECK(vlr_rope_heads(ws->dqkv, m->pos_compact, cfg->rope_cos, cfg->rope_sin, Mc, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, Mc, 0, st));
-    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, Mc, N, H, H, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, Mc, H, N, N, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, Mc, H, st));
-    return VLR_OK;
 }
 extern "C" int vlr_decoder_layer_fwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_acts* a,
                                      const void* x_in, const int* pos, const int* key_mask, int batch, int S,
@@ -524,74 +487,122 @@ extern "C" int vlr_decoder_layer_decode_shared(const vlr_llama_cfg* cfg, const v
     return layer_decode("vlr_decoder_layer_decode_shared", cfg, w, q4, ws, x_inout, pos, nullptr, nullptr, nullptr, 0, 0, 0, st, lora, lws, kv);
 }
 
-double vlr_internal_tn_pair_saves(int M0, int N0, int M1, int N1);      // gemm.hip: rounds vlr_gemm_bf16_tn_pair saves over two launches on the compute CUs of the moment
+// ---- the backward of one decoder layer: ONE sequence (SwiGLU backward, dW pair, dgrad, norm, dW_o, dgrad, attention backward, RoPE
+// transpose, dW_qkv, dgrad, norm) for every driver.  What differs between them is data:
+//   g     NULL: the base weights are frozen, no weight gradient is computed
+//   ad    NULL: no adapters; else the adapter terms of the four linear groups (below)
+//   rows  where the rows the pass reads lie (RowLayout)
+// An adapter object answers down() - is the down projection adapted - and add(k, x, dy, lddy, dx, dx_fresh): the adapter terms of
+// linear group k (0: q|k|v, 1: o, 2: gate|up, 3: down) with input x and output gradient dy [M][lddy] - its adapter gradients, and its
+// input-gradient term added to dx, which holds dy W (dx_fresh = 1: WRITTEN to dx; the caller adds dy W afterwards).  LoraBwd and
+// Lora2Bwd (with the adapter passes below) are the two implementations; NoAdapter is the type of an absent one
+struct NoAdapter {
+    bool down() const { return false; }
+    int add(int, const void*, const void*, int, void*, int) const { return VLR_OK; }
+};
+// all NULL: every tensor on its M = batch * S dense rows.
+// src_rows + dgu (after vlr_decoder_layer_fwd_compact_keep): the two norm backwards read x_in / rstd1 and x_mid / rstd2 at src_rows[row],
+//   the SwiGLU backward reads gate | up there and writes [d gate | d up] to the dense scratch dgu [M][2I], which the weight-gradient
+//   pair and the dgrad read in place of a->gu
+// m + d (after vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1)): every row-wise call at m->Mc rows, the attention backward alone
+//   on the dense layout, in the scratch d (include/vlr.h); `pos` is m->pos_compact
+// (no driver maps rows under an adapter: the adapter products read their operands densely)
+struct RowLayout { const int* src_rows; void* dgu; const vlr_row_maps* m; const vlr_dense_scratch* d; };
+template <class Adapter>
+static int layer_bwd(const vlr_llama_cfg* cfg, const LayerDims& L, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                     const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const Adapter* ad, const RowLayout& rows, const void* x_in,
+                     const void* dx_out, void* dx_in, const int* pos, const int* key_mask, int batch, int S, hipStream_t st) {
+    const auto [H, I, M, kvh, Nq, Nkv, N, rf] = L;
+    const vlr_row_maps* m = rows.m;
+    const vlr_dense_scratch* d = rows.d;
+    const int* src_rows = rows.src_rows;
+    const int Mr = m ? m->Mc : M;                           // rows of the row-wise calls
+    void* gu = src_rows ? rows.dgu : a->gu;                 // [d gate | d up] once the SwiGLU backward has run
+    // ---- MLP
+    if (src_rows) {
+        CHECK(vlr_gemm_swiglu_bwd_src(dx_out, w->wdown, a->gu, src_rows, gu, ws->dact, Mr, I, H, st));
+    } else if (ad && ad->down()) {      // adapter terms of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue
+        // and those terms as its addend - no separate pass over [M][2I]
+        // history: SLOWER than the three separate kernels in round 3 (38.8 ms against 25.5 + 7.7 per step: the addend is a third 16-byte
+        // load stream in an epilogue that already reads gate | up), equal in round 4 after the epilogue staging, 1.7 ms FASTER in round 5
+        // (482.3 against 484.1 ms, same box, twice each): the default now - no swiglu_bwd_kernel launch under LoRA
+        CHECK(ad->add(3, a->act, dx_out, H, ws->dact, 1));
+        CHECK(vlr_gemm_swiglu_bwd_add(dx_out, w->wdown, a->gu, ws->dact, ws->dact, Mr, I, H, st));   // gu now holds [dgate | dup]
+    } else {
+        CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, Mr, I, H, st));   // gu now holds [dgate | dup]; d act is not materialised
+    }
+    // dW_gate|up and dW_down as ONE persistent launch: 1376 + 688 output tiles are 8.06 rounds of 256 CUs together, 6 + 3 apart
+    if (g) CHECK(vlr_gemm_bf16_tn_pair(gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, Mr, accumulate, st));
+    CHECK(vlr_gemm_bf16(1, gu, w->wgu, ws->dxn, nullptr, nullptr, Mr, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
+    if (ad) CHECK(ad->add(2, a->xn2, gu, 2 * I, ws->dxn, 0));
+    CHECK(norm_bwd(rf, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g ? g->ln2 : nullptr, g ? accumulate : 0, ws->norm_ws, src_rows,
+                   Mr, H, st));
+    // ---- attention
+    // dW_o is one round of 256 tiles on its own; together with dW_qkv it would be 768 + 256 = 4 whole rounds of ONE persistent launch
+    // (vlr_gemm_bf16_tn_pair below; both operands - dx_mid, attn - stay untouched until the end of this call).  Measured NEUTRAL in round 5
+    // (565.9 vs 565.9 ms, same box, twice each) on the whole chip; with CUs left to RCCL (240-CU rounds: 4 + 2 apart, 5 together) it saves a
+    // round - so: paired when the joint launch saves at least a quarter round on the CUs the launches have now.  That was measured on the
+    // adapter-free layer: under an adapter the two launches stay apart
+    const bool pair_o = g && !ad && !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;
+    if (g && !pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, Mr, H, Nq, Nq, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, Mr, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
+    if (ad) CHECK(ad->add(1, a->attn, ws->dx_mid, H, ws->dattn, 0));
+    if (m) {
+        // a shared row's d attn is the sum of both branches' gradients already (downstream of it the two copies were one row): it enters at
+        // the chosen copy, the dropped copy gets dO = 0 - there delta = 0 and dS = P (dP - delta) = 0 exactly
+        CHECK(vlr_expand_rows_zero(ws->dattn, m->dense_own, d->dattn, M, Nq, st));
+        CHECK(vlr_gather_rows(a->qkv, m->dense_src, d->qkv, M, N, st));
+        CHECK(vlr_gather_rows(a->attn, m->dense_src, d->attn, M, Nq, st));
+        CHECK(attn_bwd(cfg, L, d->qkv, d->attn, d->dattn, a->lse, ws->delta, key_mask, d->dqkv, batch, S, st));
+        // the rejected response rows' dK / dV on the prompt keys landed on the dropped rows: added to the chosen twin (fp32, one rounding)
+        CHECK(vlr_fold_rows(d->dqkv, m->compact_rows, m->twin, ws->dqkv, Mr, N, st));
+    } else {
+        CHECK(attn_bwd(cfg, L, a->qkv, a->attn, ws->dattn, a->lse, ws->delta, key_mask, ws->dqkv, batch, S, st));
+    }
+    // transpose of the rotation on the q and k column blocks ((Nq + Nkv) / head_dim consecutive heads)
+    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, Mr, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
+    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, Mr, 0, st));
+    else if (g) CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, Mr, N, H, H, 0, 0, accumulate, 0, st));
+    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, Mr, H, N, N, H, H, 0, 0, 0, 0, st));
+    if (ad) CHECK(ad->add(0, a->xn1, ws->dqkv, N, ws->dxn, 0));
+    CHECK(norm_bwd(rf, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g ? g->ln1 : nullptr, g ? accumulate : 0, ws->norm_ws, src_rows, Mr, H,
+                   st));
+    return VLR_OK;
+}
 extern "C" int vlr_decoder_layer_bwd(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g,
                                      int accumulate, const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws,
                                      const void* x_in, const void* dx_out, void* dx_in, const int* pos,
                                      const int* key_mask, int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && g && a && ws && x_in && dx_out && dx_in && pos, "vlr_decoder_layer_bwd: null argument");
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    // ---- MLP
-    CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]; d act is not materialised
-    // dW_gate|up and dW_down as ONE persistent launch: 1376 + 688 output tiles are 8.06 rounds of 256 CUs together, 6 + 3 apart
-    CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
-    CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, M, H, st));
-    // ---- attention
-    // dW_o is one round of 256 tiles on its own; together with dW_qkv it would be 768 + 256 = 4 whole rounds of ONE persistent launch
-    // (vlr_gemm_bf16_tn_pair below; both operands - dx_mid, attn - stay untouched until the end of this call).  Measured NEUTRAL in round 5
-    // (565.9 vs 565.9 ms, same box, twice each) on the whole chip; with CUs left to RCCL (240-CU rounds: 4 + 2 apart, 5 together) it saves a
-    // round - so: paired when the joint launch saves at least a quarter round on the CUs the launches have now
-    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;
-    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
-    CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
-                           key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
-                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    // transpose of the rotation on the q and k column blocks ((Nq + Nkv) / head_dim consecutive heads)
-    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, M, 0, st));
-    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, M, H, st));
-    return VLR_OK;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_bwd", cfg, batch, S, &L));
+    return layer_bwd(cfg, L, w, g, accumulate, a, ws, (const NoAdapter*)nullptr, RowLayout{}, x_in, dx_out, dx_in, pos, key_mask, batch, S, st);
 }
-// vlr_decoder_layer_bwd after vlr_decoder_layer_fwd_compact_keep, call for call, in the same order and at M = batch * S rows: the two
-// norm backwards read x_in / rstd1 and x_mid / rstd2 at src_rows[row], the SwiGLU backward reads gate | up there and writes
-// [d gate | d up] to the dense scratch dgu [M][2I], which the weight-gradient pair and the dgrad read in place of a->gu
-static int norm_bwd_src(int f32, const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx, void* dw,
-                        int acc, void* ws, const int* src_rows, int M, int H, hipStream_t st) {
-    return f32 ? vlr_rmsnorm_bwd_f32_src(dy, (const float*)x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st)
-               : vlr_rmsnorm_bwd_src(dy, x, w, rstd, dres, dx, dw, acc, ws, src_rows, M, H, st);
-}
+// vlr_decoder_layer_bwd after vlr_decoder_layer_fwd_compact_keep, call for call, in the same order and at M = batch * S rows
 extern "C" int vlr_decoder_layer_bwd_src(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
                                          const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, void* dgu, const int* src_rows,
                                          const void* x_in, const void* dx_out, void* dx_in, const int* pos, const int* key_mask,
                                          int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && g && a && ws && dgu && src_rows && x_in && dx_out && dx_in && pos, "vlr_decoder_layer_bwd_src: null argument");
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    // ---- MLP
-    CHECK(vlr_gemm_swiglu_bwd_src(dx_out, w->wdown, a->gu, src_rows, dgu, ws->dact, M, I, H, st));
-    CHECK(vlr_gemm_bf16_tn_pair(dgu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
-    CHECK(vlr_gemm_bf16(1, dgu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd_src(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g->ln2, accumulate, ws->norm_ws, src_rows, M, H, st));
-    // ---- attention (vlr_decoder_layer_bwd's calls on the dense q|k|v, attn, lse, xn1)
-    const bool pair_o = !accumulate && vlr_internal_tn_pair_saves(N, H, H, Nq) >= 0.25;
-    if (!pair_o) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, Nq, H, H, Nq, Nq, 0, 0, 0, 0, st));
-    CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
-                           key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
-                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    if (pair_o) CHECK(vlr_gemm_bf16_tn_pair(ws->dqkv, a->xn1, g->wqkv, N, H, N, H, H, ws->dx_mid, a->attn, g->wo, H, Nq, H, Nq, Nq, M, 0, st));
-    else CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
-    CHECK(norm_bwd_src(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g->ln1, accumulate, ws->norm_ws, src_rows, M, H, st));
-    return VLR_OK;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_bwd_src", cfg, batch, S, &L));
+    return layer_bwd(cfg, L, w, g, accumulate, a, ws, (const NoAdapter*)nullptr, RowLayout{src_rows, dgu, nullptr, nullptr}, x_in, dx_out, dx_in,
+                     pos, key_mask, batch, S, st);
+}
+// Backward of vlr_decoder_layer_fwd_compact_ex(keep_for_backward = 1)
+extern "C" int vlr_decoder_layer_bwd_compact(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g, int accumulate,
+                                             const vlr_layer_acts* a, const vlr_layer_bwd_ws* ws, const vlr_row_maps* m,
+                                             const vlr_dense_scratch* d, const void* x_in, const void* dx_out, void* dx_in,
+                                             const int* key_mask, int batch, int S, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && g && a && ws && m && d && x_in && dx_out && dx_in, "vlr_decoder_layer_bwd_compact: null argument");
+    VLR_REQUIRE(m->compact_rows && m->dense_src && m->dense_own && m->twin && m->pos_compact, "vlr_decoder_layer_bwd_compact: null row map");
+    VLR_REQUIRE(d->qkv && d->attn && d->dattn && d->dqkv, "vlr_decoder_layer_bwd_compact: null dense scratch");
+    VLR_REQUIRE(batch > 0 && S > 0 && m->Mc > 0 && m->Mc <= batch * S, "vlr_decoder_layer_bwd_compact: %d compact rows of %d x %d dense rows",
+                m->Mc, batch, S);
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_bwd_compact", cfg, batch, S, &L));
+    return layer_bwd(cfg, L, w, g, accumulate, a, ws, (const NoAdapter*)nullptr, RowLayout{nullptr, nullptr, m, d}, x_in, dx_out, dx_in,
+                     m->pos_compact, key_mask, batch, S, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -601,11 +612,24 @@ extern "C" int vlr_decoder_layer_bwd_src(const vlr_llama_cfg* cfg, const vlr_lay
 // u = dropout_t(x) A_t^T is kept for the backward ([M][7r] per layer: qkv | o | gate,up | down).
 // Dropout target t of a layer uses seed + t (t = 0..6 in q,k,v,o,gate,up,down order).
 // ---------------------------------------------------------------------------------------------------------------------
-// outs[t]: output features of sub-target t (they differ under grouped-query attention: q has heads*hd, k and v kv_heads*hd)
-// u_t = s * dropout_t(x) A_t^T for the n sub-targets of a group (the B half rides the K loop of the base GEMM: vlr_gemm_*_lora)
-// bits != NULL (vlr_lora_weights::mask_bits): the packed keep masks of the n targets are DRAWN here (target t at bits + t * M * in / 8) and
-// read by the staged-operand mask of the grouped launch - and again by the backward (lora_group_bwd)
-// ustride (0 = r): elements between the u blocks of consecutive sub-targets - the two-adapter layout [u_lora | u_plora] per sub-target
+// Group k of a layer (0: q|k|v, 1: o, 2: gate|up, 3: down): n sub-targets from target t0 on, reading `in` features - target t has the
+// u block at column t * rank, the dropout seed + t and the packed masks of target t; outs[t]: the output features of sub-target t
+struct LoraGroup { int n, in, t0, outs[3]; };
+// nq = 1: one adapter over the fused projection (Qwen c_attn); 3: q, k, v separately
+static LoraGroup lora_group(int k, int nq, const LayerDims& L) {
+    if (k == 0) return nq == 1 ? LoraGroup{1, L.H, 0, {L.N}} : LoraGroup{3, L.H, 0, {L.Nq, L.Nkv, L.Nkv}};
+    if (k == 1) return LoraGroup{1, L.H, 3, {L.H}};
+    if (k == 2) return LoraGroup{2, L.H, 4, {L.I, L.I}};
+    return LoraGroup{1, L.I, 6, {L.H}};
+}
+static long lora_rowmajor_bytes(int hidden, int inter, int M) { return (((long)M * hidden / 8) * 6 + (long)M * inter / 8 + 63) / 64 * 64; }
+// the packed keep masks of target t in lw->mask_bits (NULL without dropout): row-major, and K-tile-blocked transposed
+struct LoraMasks { unsigned char* bits; unsigned char* bits_kt; };
+static inline LoraMasks lora_masks(const vlr_lora_weights* lw, int t, int M, int H, int I) {
+    if (!lw->mask_bits || !(lw->dropout > 0.f)) return LoraMasks{nullptr, nullptr};
+    unsigned char* base = (unsigned char*)lw->mask_bits;
+    return LoraMasks{base + (size_t)t * ((size_t)M * H / 8), base + lora_rowmajor_bytes(H, I, M) + (size_t)t * (size_t)vlr_dropout_bits_kt_bytes(M, H)};
+}
 // per-stream device buffer for vlr_rows_tile_list (count + tile indices), grown on demand; NULL: no memory (the dense reductions run)
 static int* row_tiles_buf(hipStream_t st, int ints) {
     struct Slot { hipStream_t st; int* p; int cap; };
@@ -639,10 +663,13 @@ static const unsigned char* seg_skip_flags(hipStream_t st, const unsigned char* 
 bool vlr_lora_rows_try_launch(int mode, int n, const void* X, int ldx, const int* Ks, const void* W, int ldw, void* out, int ldo, int ostride,
                               int M, int r, float alpha, const void* bits, long gbits, int bits_ld, const unsigned char* rowmask, hipStream_t st, bool force = false);
 
+// u_t = s * dropout_t(x) A_t^T for the n sub-targets of a group (the B half rides the K loop of the base GEMM: vlr_gemm_*_lora)
+// bits != NULL (vlr_lora_weights::mask_bits): the packed keep masks of the n targets are DRAWN here (target t at bits + t * M * in / 8) and
+// read by the staged-operand mask of the grouped launch - and again by the backward (lora_group_bwd)
+// ustride (0 = r): elements between the u blocks of consecutive sub-targets - the two-adapter layout [u_lora | u_plora] per sub-target
 static int lora_group_a(int n, int r, int in, const void* x, int ldx, const void* A, void* u, int ldu, float scale, float p,
-                        uint64_t seed, void* ws_xd, int M, hipStream_t st, const unsigned char* rowmask = nullptr, unsigned char* bits = nullptr,
+                        uint64_t seed, int M, hipStream_t st, const unsigned char* rowmask = nullptr, unsigned char* bits = nullptr,
                         unsigned char* bits_kt = nullptr, int ustride = 0) {
-    (void)ws_xd;
     if (ustride == 0) ustride = r;
     struct MaskAfter {       // PLoRA: the adapter acts on the image rows only - zero the other rows of u on the way out
         void* u; int ldu, n, r, us, M; const unsigned char* rm; hipStream_t st;
@@ -686,12 +713,12 @@ static int lora_group_a(int n, int r, int in, const void* x, int ldx, const void
 }
 
 // dx [M][in] already holds dy W; adds the adapter path and writes the adapter gradients
+// outs[t]: output features of sub-target t (they differ under grouped-query attention: q has heads*hd, k and v kv_heads*hd)
 // dx_fresh = 1: dx is WRITTEN (= the adapter term alone; the caller adds dy W afterwards - the fused SwiGLU-backward GEMM of down_proj)
 static int lora_group_bwd(int n, int r, int in, const int* outs, const void* x, const void* dy, int lddy, const void* A, const void* B,
                           void* dA, void* dB, const void* u, int ldu, void* v, void* dx, float scale, float p, uint64_t seed,
-                          void* ws_xd, int accumulate, int M, hipStream_t st, int dx_fresh = 0, const unsigned char* rowmask = nullptr,
+                          int accumulate, int M, hipStream_t st, int dx_fresh = 0, const unsigned char* rowmask = nullptr,
                           const unsigned char* bits = nullptr, const unsigned char* bits_kt = nullptr, const int* ktl = nullptr) {
-    (void)ws_xd;
     const int nr = n * r;
     const long gstride = (long)M * in / 8;       // bytes between the packed keep masks of the group's targets (the forward drew them)
     size_t ofs[4] = {0, 0, 0, 0};
@@ -735,16 +762,69 @@ static int lora_group_bwd(int n, int r, int in, const int* outs, const void* x, 
     return VLR_OK;
 }
 
-static long lora_rowmajor_bytes(int hidden, int inter, int M) { return (((long)M * hidden / 8) * 6 + (long)M * inter / 8 + 63) / 64 * 64; }
 extern "C" long vlr_lora_mask_bytes(int hidden, int inter, int M) {
     return lora_rowmajor_bytes(hidden, inter, M) + 6 * vlr_dropout_bits_kt_bytes(M, hidden) + vlr_dropout_bits_kt_bytes(M, inter);
 }
-static int lora_check(const char* who, const vlr_lora_weights* lw, const void* ws_xd) {
+static int lora_check(const char* who, const vlr_lora_weights* lw) {
     VLR_REQUIRE(lw->r > 0 && lw->r % 8 == 0, "%s: LoRA rank must be a positive multiple of 8, got %d", who, lw->r);
     VLR_REQUIRE(lw->dropout >= 0.f && lw->dropout < 1.f, "%s: lora_dropout must be in [0,1), got %g", who, (double)lw->dropout);
-    (void)ws_xd;      // (ABI v3 kept drop(x) of the seven targets there; since v4 the mask is applied while the operand is staged)
     VLR_REQUIRE(lw->a_qkv && lw->b_qkv && lw->a_o && lw->b_o && lw->a_gu && lw->b_gu && (!lw->a_down == !lw->b_down), "%s: null adapter pointer", who);
     VLR_REQUIRE(lw->qkv_targets == 0 || lw->qkv_targets == 1 || lw->qkv_targets == 3, "%s: qkv_targets must be 1 or 3, got %d", who, lw->qkv_targets);
+    return VLR_OK;
+}
+
+// y = x W^T + u B^T + residual (NT; the adapter segment of rank R rides the K loop), on the bf16 or the fp32 stream
+static int proj_res_lora(int f32, const void* x, const void* W, void* y, const void* res, int M, int N, int K, const void* u, int ldu,
+                         const void* B, int R, hipStream_t st) {
+    return f32 ? vlr_gemm_lora_f32res(x, K, W, (float*)y, N, (const float*)res, N, M, N, K, u, ldu, B, R, st)
+               : vlr_gemm_lora(x, K, W, y, N, res, N, M, N, K, u, ldu, B, R, st);
+}
+// ---- the forward of one decoder layer under adapters: ONE sequence - vlr_decoder_layer_fwd_ex's, each of the four fused projections
+// with an adapter segment of rank R in its K loop.  The segment is made of one or two "sides" (adapters), each with its own rank, scale,
+// dropout, A matrices and packed masks (side.w), seed and row mask (NULL: every row): per sub-target the u block [M][R] holds the sides'
+// blocks in order, u is [M][7R].
+// B: the B operand [out][R] of each projection - one side: the adapter's own b_*; two: their row-wise concatenation (vlr_lora_bcomb)
+// skipf (seg_skip_flags; NULL: none): row tiles whose flag is set run only the first skip_col K elements of every sub-target's segment
+struct LoraSide { const vlr_lora_weights* w; uint64_t seed; const unsigned char* rowmask; };
+static int layer_fwd_lora(const vlr_llama_cfg* cfg, const LayerDims& L, const vlr_layer_weights* w, const LoraSide* sides, int nsides,
+                          const vlr_lora_bcomb& B, const unsigned char* skipf, int skip_col, const vlr_layer_acts* a, void* u,
+                          const void* x_in, const int* pos, const int* key_mask, int batch, int S, hipStream_t st) {
+    const int H = L.H, I = L.I, M = L.M, Nq = L.Nq, Nkv = L.Nkv, N = L.N, rf = L.rf;
+    int R = 0;
+    for (int s = 0; s < nsides; ++s) R += sides[s].w->r;
+    const int ldu = 7 * R;
+    const int nq = sides[0].w->qkv_targets == 1 ? 1 : 3;             // one adapter over the fused projection (Qwen c_attn) or q, k, v separately
+    // the segment of group k: every side's u = s * dropout(x) A^T, its block behind the previous side's; then the tile skip of the
+    // projection that follows
+    auto segment = [&](int k, const void* x) -> int {
+        const LoraGroup G = lora_group(k, nq, L);
+        size_t c = (size_t)G.t0 * R;
+        for (int s = 0; s < nsides; ++s) {
+            const vlr_lora_weights* lw = sides[s].w;
+            const void* const A[4] = {lw->a_qkv, lw->a_o, lw->a_gu, lw->a_down};
+            const LoraMasks mk = lora_masks(lw, G.t0, M, H, I);
+            CHECK(lora_group_a(G.n, lw->r, G.in, x, G.in, A[k], off(u, c), ldu, lw->scale, lw->dropout, sides[s].seed + G.t0, M, st, sides[s].rowmask,
+                               mk.bits, mk.bits_kt, R));
+            c += lw->r;
+        }
+        return vlr_gemm_seg_rowskip(skipf, skip_col);
+    };
+    CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, M, H, cfg->rms_eps, st));
+    CHECK(segment(0, a->xn1));
+    CHECK(vlr_gemm_qkv_rope_lora(a->xn1, w->wqkv, w->bqkv, a->qkv, pos, cfg->rope_cos, cfg->rope_sin, M, N, Nq + Nkv, H, H,
+                                 cfg->head_dim, cfg->max_pos, u, ldu, B.qkv, R, nq == 1 ? N : Nq, nq == 1 ? 0 : Nkv, st));
+    CHECK(attn_fwd(cfg, L, a->qkv, a->attn, a->lse, key_mask, batch, S, st));
+    CHECK(segment(1, a->attn));
+    CHECK(proj_res_lora(rf, a->attn, w->wo, a->x_mid, x_in, M, H, H, off(u, 3 * (size_t)R), ldu, B.o, R, st));
+    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
+    CHECK(segment(2, a->xn2));
+    CHECK(vlr_gemm_swiglu_lora(a->xn2, w->wgu, a->gu, a->act, M, I, H, H, off(u, 4 * (size_t)R), ldu, B.gu, R, st));
+    if (sides[0].w->a_down) {
+        CHECK(segment(3, a->act));
+        CHECK(proj_res_lora(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, off(u, 6 * (size_t)R), ldu, B.down, R, st));
+    } else {
+        CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
+    }
     return VLR_OK;
 }
 
@@ -755,49 +835,39 @@ extern "C" int vlr_decoder_layer_fwd_lora(const vlr_llama_cfg* cfg, const vlr_la
 }
 // rowmask [batch * S] bytes (NULL: every row): the adapters act on the rows whose byte is non-zero only - PLoRA of InternLM-XComposer2
 // (reference models/InternLMXC2/build_mlp.py:158-203: im_mask = the image rows)
+// (ws_xd is not read: ABI v3 kept drop(x) of the seven targets there; since v4 the mask is applied while the operand is staged)
 extern "C" int vlr_decoder_layer_fwd_lora_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lw,
                                              const vlr_layer_acts* a, void* u, void* ws_xd, uint64_t seed, const unsigned char* rowmask,
                                              const void* x_in, const int* pos, const int* key_mask, int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && lw && a && u && x_in && pos, "vlr_decoder_layer_fwd_lora: null argument");
-    CHECK(lora_check("vlr_decoder_layer_fwd_lora", lw, ws_xd));
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S, r = lw->r, ldu = 7 * r;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    VLR_REQUIRE(Nq == H, "vlr_decoder_layer_fwd_lora: heads*head_dim != hidden");
-    const float sc = lw->scale, p = lw->dropout;
-#define XD(seg) (ws_xd)      // ABI v4: one scratch [M][max(hidden, inter)] (the fallback path of vlr_gemm_dropout_acc), not per-target copies
-#define MB(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + (size_t)(t) * ((size_t)M * H / 8) : nullptr)      // packed keep mask of target t
-#define MT(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + lora_rowmajor_bytes(H, I, M) + (size_t)(t) * (size_t)vlr_dropout_bits_kt_bytes(M, H) : nullptr)   // ... K-tile-blocked transposed
-    const int rf = cfg->resid_f32;
+    CHECK(lora_check("vlr_decoder_layer_fwd_lora", lw));
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd_lora", cfg, batch, S, &L));
+    VLR_REQUIRE(L.Nq == L.H, "vlr_decoder_layer_fwd_lora: heads*head_dim != hidden");
     // a row-restricted adapter (PLoRA alone): row tiles without a marked row skip the WHOLE segment (u is zero there)
-    const unsigned char* skipf = (r % 64 == 0) ? seg_skip_flags(st, rowmask, M) : nullptr;
-    CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, M, H, cfg->rms_eps, st));
-    const int nq = lw->qkv_targets == 1 ? 1 : 3;             // one adapter over the fused projection (Qwen c_attn) or q, k, v separately
-    CHECK(lora_group_a(nq, r, H, a->xn1, H, lw->a_qkv, u, ldu, sc, p, seed + 0, ws_xd, M, st, rowmask, MB(0), MT(0)));
-    CHECK(vlr_gemm_seg_rowskip(skipf, 0));
-    CHECK(vlr_gemm_qkv_rope_lora(a->xn1, w->wqkv, w->bqkv, a->qkv, pos, cfg->rope_cos, cfg->rope_sin, M, N, Nq + Nkv, H, H,
-                                 cfg->head_dim, cfg->max_pos, u, ldu, lw->b_qkv, r, nq == 1 ? N : Nq, nq == 1 ? 0 : Nkv, st));
-    CHECK(vlr_attn_fwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, Nq, a->lse, key_mask, batch, S,
-                           cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(lora_group_a(1, r, H, a->attn, H, lw->a_o, off(u, 3 * (size_t)r), ldu, sc, p, seed + 3, XD(3), M, st, rowmask, MB(3), MT(3)));
-    CHECK(vlr_gemm_seg_rowskip(skipf, 0));
-    if (rf) CHECK(vlr_gemm_lora_f32res(a->attn, H, w->wo, (float*)a->x_mid, H, (const float*)x_in, H, M, H, H, off(u, 3 * (size_t)r), ldu, lw->b_o, r, st));
-    else CHECK(vlr_gemm_lora(a->attn, H, w->wo, a->x_mid, H, x_in, H, M, H, H, off(u, 3 * (size_t)r), ldu, lw->b_o, r, st));
-    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
-    CHECK(lora_group_a(2, r, H, a->xn2, H, lw->a_gu, off(u, 4 * (size_t)r), ldu, sc, p, seed + 4, XD(4), M, st, rowmask, MB(4), MT(4)));
-    CHECK(vlr_gemm_seg_rowskip(skipf, 0));
-    CHECK(vlr_gemm_swiglu_lora(a->xn2, w->wgu, a->gu, a->act, M, I, H, H, off(u, 4 * (size_t)r), ldu, lw->b_gu, r, st));
-    if (lw->a_down) {
-        CHECK(lora_group_a(1, r, I, a->act, I, lw->a_down, off(u, 6 * (size_t)r), ldu, sc, p, seed + 6, XD(6), M, st, rowmask, MB(6), MT(6)));
-        CHECK(vlr_gemm_seg_rowskip(skipf, 0));
-        if (rf) CHECK(vlr_gemm_lora_f32res(a->act, I, w->wdown, (float*)a->x_out, H, (const float*)a->x_mid, H, M, H, I, off(u, 6 * (size_t)r), ldu, lw->b_down, r, st));
-        else CHECK(vlr_gemm_lora(a->act, I, w->wdown, a->x_out, H, a->x_mid, H, M, H, I, off(u, 6 * (size_t)r), ldu, lw->b_down, r, st));
-    } else {
-        CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
-    }
-    return VLR_OK;
+    const unsigned char* skipf = (lw->r % 64 == 0) ? seg_skip_flags(st, rowmask, L.M) : nullptr;
+    const LoraSide side = {lw, seed, rowmask};
+    return layer_fwd_lora(cfg, L, w, &side, 1, vlr_lora_bcomb{lw->b_qkv, lw->b_o, lw->b_gu, lw->b_down}, skipf, 0, a, u, x_in, pos, key_mask, batch,
+                          S, st);
 }
 
+// the adapter terms of the backward (layer_bwd) under ONE adapter: lora_group_bwd on group k
+struct LoraBwd {
+    const vlr_lora_weights* lw; const vlr_lora_grads* lg; const void* u; void* v; uint64_t seed; const unsigned char* rowmask; const int* ktl;
+    int accumulate; LayerDims L; hipStream_t st;
+    bool down() const { return lw->a_down != nullptr; }
+    int add(int k, const void* x, const void* dy, int lddy, void* dx, int dx_fresh) const {
+        const int r = lw->r;
+        const LoraGroup G = lora_group(k, lw->qkv_targets == 1 ? 1 : 3, L);
+        const void* const A[4] = {lw->a_qkv, lw->a_o, lw->a_gu, lw->a_down};
+        const void* const B[4] = {lw->b_qkv, lw->b_o, lw->b_gu, lw->b_down};
+        void* const dA[4] = {lg->a_qkv, lg->a_o, lg->a_gu, lg->a_down};
+        void* const dB[4] = {lg->b_qkv, lg->b_o, lg->b_gu, lg->b_down};
+        const LoraMasks mk = lora_masks(lw, G.t0, L.M, L.H, L.I);
+        return lora_group_bwd(G.n, r, G.in, G.outs, x, dy, lddy, A[k], B[k], dA[k], dB[k], off(u, (size_t)G.t0 * r), 7 * r, v, dx, lw->scale,
+                              lw->dropout, seed + G.t0, accumulate, L.M, st, dx_fresh, rowmask, mk.bits, mk.bits_kt, ktl);
+    }
+};
 extern "C" int vlr_decoder_layer_bwd_lora(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lw,
                                           const vlr_lora_grads* lg, int accumulate, const vlr_layer_acts* a, const void* u,
                                           const vlr_layer_bwd_ws* ws, void* ws_v, void* ws_xd, uint64_t seed, const void* x_in,
@@ -807,61 +877,24 @@ extern "C" int vlr_decoder_layer_bwd_lora(const vlr_llama_cfg* cfg, const vlr_la
                                          key_mask, batch, S, st);
 }
 // g != NULL: the base weights are trainable too (their gradients as in vlr_decoder_layer_bwd) - the FULL fine-tune of a decoder whose
-// linears carry adapters as base-model weights (InternLM-XComposer2's PLoRA); rowmask as in vlr_decoder_layer_fwd_lora_ex
+// linears carry adapters as base-model weights (InternLM-XComposer2's PLoRA); rowmask and ws_xd as in vlr_decoder_layer_fwd_lora_ex
 extern "C" int vlr_decoder_layer_bwd_lora_ex(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_layer_grads* g,
                                              const vlr_lora_weights* lw, const vlr_lora_grads* lg, int accumulate, const vlr_layer_acts* a,
                                              const void* u, const vlr_layer_bwd_ws* ws, void* ws_v, void* ws_xd, uint64_t seed,
                                              const unsigned char* rowmask, const void* x_in, const void* dx_out, void* dx_in, const int* pos,
                                              const int* key_mask, int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && lw && lg && a && u && ws && ws_v && x_in && dx_out && dx_in && pos, "vlr_decoder_layer_bwd_lora: null argument");
-    CHECK(lora_check("vlr_decoder_layer_bwd_lora", lw, ws_xd));
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S, r = lw->r, ldu = 7 * r;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    VLR_REQUIRE(Nq == H, "vlr_decoder_layer_bwd_lora: heads*head_dim != hidden");
-    const int o_qkv[3] = {Nq, Nkv, Nkv}, o_h[1] = {H}, o_gu[2] = {I, I};
-    const float sc = lw->scale, p = lw->dropout;
+    CHECK(lora_check("vlr_decoder_layer_bwd_lora", lw));
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_bwd_lora", cfg, batch, S, &L));
+    VLR_REQUIRE(L.Nq == L.H, "vlr_decoder_layer_bwd_lora: heads*head_dim != hidden");
     const int* ktl = nullptr;         // PLoRA: the 64-row K tiles with an image row, for the adapter-gradient reductions over the token rows
-    if (rowmask && M % 64 == 0 && lg->a_qkv) {
-        int* buf = row_tiles_buf(st, M / 64 + 1);
-        if (buf) { CHECK(vlr_rows_tile_list(rowmask, M, buf, st)); ktl = buf; }
+    if (rowmask && L.M % 64 == 0 && lg->a_qkv) {
+        int* buf = row_tiles_buf(st, L.M / 64 + 1);
+        if (buf) { CHECK(vlr_rows_tile_list(rowmask, L.M, buf, st)); ktl = buf; }
     }
-#define XD(seg) (ws_xd)      // ABI v4: one scratch [M][max(hidden, inter)] (the fallback path of vlr_gemm_dropout_acc), not per-target copies
-#define MB(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + (size_t)(t) * ((size_t)M * H / 8) : nullptr)      // packed keep mask of target t
-#define MT(t) (lw->mask_bits && p > 0.f ? (unsigned char*)lw->mask_bits + lora_rowmajor_bytes(H, I, M) + (size_t)(t) * (size_t)vlr_dropout_bits_kt_bytes(M, H) : nullptr)   // ... K-tile-blocked transposed
-    // ---- MLP
-    if (lw->a_down) {      // adapter term of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue
-        // history: SLOWER than the three separate kernels in round 3 (38.8 ms against 25.5 + 7.7 per step: the addend is a third 16-byte
-        // load stream in an epilogue that already reads gate | up), equal in round 4 after the epilogue staging, 1.7 ms FASTER in round 5
-        // (482.3 against 484.1 ms, same box, twice each): the default now - no swiglu_bwd_kernel launch under LoRA
-        CHECK(lora_group_bwd(1, r, I, o_h, a->act, dx_out, H, lw->a_down, lw->b_down, lg->a_down, lg->b_down, off(u, 6 * (size_t)r), ldu, ws_v,
-                             ws->dact, sc, p, seed + 6, XD(6), accumulate, M, st, 1, rowmask, MB(6), MT(6), ktl));
-        CHECK(vlr_gemm_swiglu_bwd_add(dx_out, w->wdown, a->gu, ws->dact, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]
-    } else {
-        CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));
-    }
-    if (g) CHECK(vlr_gemm_bf16_tn_pair(a->gu, a->xn2, g->wgu, 2 * I, H, 2 * I, H, H, dx_out, a->act, g->wdown, H, I, H, I, I, M, accumulate, st));
-    CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    CHECK(lora_group_bwd(2, r, H, o_gu, a->xn2, a->gu, 2 * I, lw->a_gu, lw->b_gu, lg->a_gu, lg->b_gu, off(u, 4 * (size_t)r), ldu, ws_v,
-                         ws->dxn, sc, p, seed + 4, XD(4), accumulate, M, st, 0, rowmask, MB(4), MT(4), ktl));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, g ? g->ln2 : nullptr, g ? accumulate : 0, ws->norm_ws, M, H, st));
-    // ---- attention
-    if (g) CHECK(vlr_gemm_bf16(2, ws->dx_mid, a->attn, g->wo, nullptr, nullptr, H, Nq, M, H, Nq, Nq, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, H, H, H, H, H, 0, 0, 0, 0, st));
-    CHECK(lora_group_bwd(1, r, H, o_h, a->attn, ws->dx_mid, H, lw->a_o, lw->b_o, lg->a_o, lg->b_o, off(u, 3 * (size_t)r), ldu, ws_v,
-                         ws->dattn, sc, p, seed + 3, XD(3), accumulate, M, st, 0, rowmask, MB(3), MT(3), ktl));
-    CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
-                           key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
-                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    if (g) CHECK(vlr_gemm_bf16(2, ws->dqkv, a->xn1, g->wqkv, nullptr, nullptr, N, H, M, N, H, H, 0, 0, accumulate, 0, st));
-    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
-    const int o_all[1] = {N};
-    const int nq = lw->qkv_targets == 1 ? 1 : 3;
-    CHECK(lora_group_bwd(nq, r, H, nq == 1 ? o_all : o_qkv, a->xn1, ws->dqkv, N, lw->a_qkv, lw->b_qkv, lg->a_qkv, lg->b_qkv, u, ldu, ws_v, ws->dxn,
-                         sc, p, seed + 0, ws_xd, accumulate, M, st, 0, rowmask, MB(0), MT(0), ktl));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, g ? g->ln1 : nullptr, g ? accumulate : 0, ws->norm_ws, M, H, st));
-    return VLR_OK;
+    const LoraBwd ad = {lw, lg, u, ws_v, seed, rowmask, ktl, accumulate, L, st};
+    return layer_bwd(cfg, L, w, g, accumulate, a, ws, &ad, RowLayout{}, x_in, dx_out, dx_in, pos, key_mask, batch, S, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -949,15 +982,13 @@ static int lora2_group_bwd(int n, int in, const int* outs, const void* x, const 
 }
 
 static int lora2_check(const char* who, const vlr_lora_weights* lw, const vlr_lora_weights* pw, const vlr_lora_bcomb* bc) {
-    CHECK(lora_check(who, lw, nullptr));
-    CHECK(lora_check(who, pw, nullptr));
+    CHECK(lora_check(who, lw));
+    CHECK(lora_check(who, pw));
     VLR_REQUIRE(bc && bc->qkv && bc->o && bc->gu, "%s: null concatenated B", who);
     VLR_REQUIRE((lw->qkv_targets == 1) == (pw->qkv_targets == 1), "%s: the two adapters must split the qkv projection the same way", who);
     VLR_REQUIRE(!lw->a_down == !pw->a_down && (!lw->a_down || bc->down), "%s: down-projection adapters must be both present or both absent", who);
     return VLR_OK;
 }
-#define MB2(w_, t) ((w_)->mask_bits && (w_)->dropout > 0.f ? (unsigned char*)(w_)->mask_bits + (size_t)(t) * ((size_t)M * H / 8) : nullptr)
-#define MT2(w_, t) ((w_)->mask_bits && (w_)->dropout > 0.f ? (unsigned char*)(w_)->mask_bits + lora_rowmajor_bytes(H, I, M) + (size_t)(t) * (size_t)vlr_dropout_bits_kt_bytes(M, H) : nullptr)
 
 extern "C" int vlr_decoder_layer_fwd_lora2(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lw,
                                            const vlr_lora_weights* pw, const vlr_lora_bcomb* bc, const vlr_layer_acts* a, void* u,
@@ -965,47 +996,38 @@ extern "C" int vlr_decoder_layer_fwd_lora2(const vlr_llama_cfg* cfg, const vlr_l
                                            const int* key_mask, int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && lw && pw && a && u && x_in && pos, "vlr_decoder_layer_fwd_lora2: null argument");
     CHECK(lora2_check("vlr_decoder_layer_fwd_lora2", lw, pw, bc));
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S, rl = lw->r, rp = pw->r, R = rl + rp, ldu = 7 * R;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    VLR_REQUIRE(Nq == H, "vlr_decoder_layer_fwd_lora2: heads*head_dim != hidden");
-    const int rf = cfg->resid_f32;
-    const int nq = lw->qkv_targets == 1 ? 1 : 3;
-    // group g of the layer: u columns [c, c + n R); LoRA block first, PLoRA block behind it (row-masked)
-    auto both = [&](int n, int in, const void* x, const void* Al, const void* Ap, size_t c, int t0) -> int {
-        CHECK(lora_group_a(n, rl, in, x, in, Al, off(u, c), ldu, lw->scale, lw->dropout, seed_l + t0, nullptr, M, st, nullptr, MB2(lw, t0), MT2(lw, t0), R));
-        CHECK(lora_group_a(n, rp, in, x, in, Ap, off(u, c + rl), ldu, pw->scale, pw->dropout, seed_p + t0, nullptr, M, st, rowmask, MB2(pw, t0), MT2(pw, t0), R));
-        return VLR_OK;
-    };
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_fwd_lora2", cfg, batch, S, &L));
+    VLR_REQUIRE(L.Nq == L.H, "vlr_decoder_layer_fwd_lora2: heads*head_dim != hidden");
+    const int rl = lw->r, R = rl + pw->r;
     // row tiles without an image row run only the LoRA part (the first rl of every sub-target's R K elements) of the [B_lora | B_plora]
     // segment: the PLoRA block of u is zero there (45 % of the row tiles at 490 x 490 / max_length 1024)
-    const unsigned char* skipf = (rl % 64 == 0 && R % 64 == 0) ? seg_skip_flags(st, rowmask, M) : nullptr;
-    CHECK(norm_fwd(rf, x_in, w->ln1, a->xn1, a->rstd1, M, H, cfg->rms_eps, st));
-    CHECK(both(nq, H, a->xn1, lw->a_qkv, pw->a_qkv, 0, 0));
-    CHECK(vlr_gemm_seg_rowskip(skipf, rl));
-    CHECK(vlr_gemm_qkv_rope_lora(a->xn1, w->wqkv, w->bqkv, a->qkv, pos, cfg->rope_cos, cfg->rope_sin, M, N, Nq + Nkv, H, H,
-                                 cfg->head_dim, cfg->max_pos, u, ldu, bc->qkv, R, nq == 1 ? N : Nq, nq == 1 ? 0 : Nkv, st));
-    CHECK(vlr_attn_fwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, Nq, a->lse, key_mask, batch, S,
-                           cfg->heads, kvh, cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(both(1, H, a->attn, lw->a_o, pw->a_o, 3 * (size_t)R, 3));
-    CHECK(vlr_gemm_seg_rowskip(skipf, rl));
-    if (rf) CHECK(vlr_gemm_lora_f32res(a->attn, H, w->wo, (float*)a->x_mid, H, (const float*)x_in, H, M, H, H, off(u, 3 * (size_t)R), ldu, bc->o, R, st));
-    else CHECK(vlr_gemm_lora(a->attn, H, w->wo, a->x_mid, H, x_in, H, M, H, H, off(u, 3 * (size_t)R), ldu, bc->o, R, st));
-    CHECK(norm_fwd(rf, a->x_mid, w->ln2, a->xn2, a->rstd2, M, H, cfg->rms_eps, st));
-    CHECK(both(2, H, a->xn2, lw->a_gu, pw->a_gu, 4 * (size_t)R, 4));
-    CHECK(vlr_gemm_seg_rowskip(skipf, rl));
-    CHECK(vlr_gemm_swiglu_lora(a->xn2, w->wgu, a->gu, a->act, M, I, H, H, off(u, 4 * (size_t)R), ldu, bc->gu, R, st));
-    if (lw->a_down) {
-        CHECK(both(1, I, a->act, lw->a_down, pw->a_down, 6 * (size_t)R, 6));
-        CHECK(vlr_gemm_seg_rowskip(skipf, rl));
-        if (rf) CHECK(vlr_gemm_lora_f32res(a->act, I, w->wdown, (float*)a->x_out, H, (const float*)a->x_mid, H, M, H, I, off(u, 6 * (size_t)R), ldu, bc->down, R, st));
-        else CHECK(vlr_gemm_lora(a->act, I, w->wdown, a->x_out, H, a->x_mid, H, M, H, I, off(u, 6 * (size_t)R), ldu, bc->down, R, st));
-    } else {
-        CHECK(proj_res(rf, a->act, w->wdown, a->x_out, a->x_mid, M, H, I, st));
-    }
-    return VLR_OK;
+    const unsigned char* skipf = (rl % 64 == 0 && R % 64 == 0) ? seg_skip_flags(st, rowmask, L.M) : nullptr;
+    // LoRA block first, PLoRA block behind it (row-masked)
+    const LoraSide sides[2] = {{lw, seed_l, nullptr}, {pw, seed_p, rowmask}};
+    return layer_fwd_lora(cfg, L, w, sides, 2, *bc, skipf, rl, a, u, x_in, pos, key_mask, batch, S, st);
 }
 
+// the adapter terms of the backward (layer_bwd) under LoRA over PLoRA: lora2_group_bwd on group k - gradients for the LoRA pairs only
+struct Lora2Bwd {
+    const vlr_lora_weights* lw; const vlr_lora_grads* lg; const vlr_lora_weights* pw; const vlr_lora_bcomb* bc; const void* u; void* v;
+    uint64_t seed_l, seed_p; const unsigned char* rowmask; int accumulate; LayerDims L; hipStream_t st;
+    bool down() const { return lw->a_down != nullptr; }
+    int add(int k, const void* x, const void* dy, int lddy, void* dx, int dx_fresh) const {
+        const int R = lw->r + pw->r;
+        const LoraGroup G = lora_group(k, lw->qkv_targets == 1 ? 1 : 3, L);
+        const void* const Al[4] = {lw->a_qkv, lw->a_o, lw->a_gu, lw->a_down};
+        const void* const Ap[4] = {pw->a_qkv, pw->a_o, pw->a_gu, pw->a_down};
+        const void* const Bc[4] = {bc->qkv, bc->o, bc->gu, bc->down};
+        void* const dA[4] = {lg->a_qkv, lg->a_o, lg->a_gu, lg->a_down};
+        void* const dB[4] = {lg->b_qkv, lg->b_o, lg->b_gu, lg->b_down};
+        const LoraMasks ml = lora_masks(lw, G.t0, L.M, L.H, L.I), mp = lora_masks(pw, G.t0, L.M, L.H, L.I);
+        const Lora2Side Ls = {lw->r, lw->scale, lw->dropout, seed_l + (uint64_t)G.t0, Al[k], dA[k], dB[k], ml.bits, ml.bits_kt};
+        const Lora2Side Ps = {pw->r, pw->scale, pw->dropout, seed_p + (uint64_t)G.t0, Ap[k], nullptr, nullptr, mp.bits, mp.bits_kt};
+        return lora2_group_bwd(G.n, G.in, G.outs, x, dy, lddy, Ls, Ps, Bc[k], off(u, (size_t)G.t0 * R), 7 * R, v, dx, accumulate, L.M, rowmask, st,
+                               dx_fresh);
+    }
+};
 extern "C" int vlr_decoder_layer_bwd_lora2(const vlr_llama_cfg* cfg, const vlr_layer_weights* w, const vlr_lora_weights* lw,
                                            const vlr_lora_grads* lg, const vlr_lora_weights* pw, const vlr_lora_bcomb* bc, int accumulate,
                                            const vlr_layer_acts* a, const void* u, const vlr_layer_bwd_ws* ws, void* ws_v, uint64_t seed_l,
@@ -1013,43 +1035,11 @@ extern "C" int vlr_decoder_layer_bwd_lora2(const vlr_llama_cfg* cfg, const vlr_l
                                            const int* pos, const int* key_mask, int batch, int S, vlr_stream_t st) {
     VLR_REQUIRE(cfg && w && lw && lg && pw && a && u && ws && ws_v && x_in && dx_out && dx_in && pos, "vlr_decoder_layer_bwd_lora2: null argument");
     CHECK(lora2_check("vlr_decoder_layer_bwd_lora2", lw, pw, bc));
-    const int H = cfg->hidden, I = cfg->inter, M = batch * S, rl = lw->r, rp = pw->r, R = rl + rp, ldu = 7 * R;
-    const int kvh = cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads;
-    const int Nq = cfg->heads * cfg->head_dim, Nkv = kvh * cfg->head_dim, N = Nq + 2 * Nkv;
-    VLR_REQUIRE(Nq == H, "vlr_decoder_layer_bwd_lora2: heads*head_dim != hidden");
-    const int o_qkv[3] = {Nq, Nkv, Nkv}, o_h[1] = {H}, o_gu[2] = {I, I}, o_all[1] = {N};
-    const int nq = lw->qkv_targets == 1 ? 1 : 3;
-    auto side = [&](const vlr_lora_weights* x_, const void* A, void* dA, void* dB, uint64_t seed, int t0) {
-        return Lora2Side{x_->r, x_->scale, x_->dropout, seed + (uint64_t)t0, A, dA, dB, MB2(x_, t0), MT2(x_, t0)};
-    };
-    // ---- MLP
-    // (as vlr_decoder_layer_bwd_lora_ex: the adapter terms of down_proj first, then the dgrad GEMM with the SwiGLU backward in its epilogue and
-    // those terms as its addend - no separate pass over [M][2I])
-    if (lw->a_down) {
-        CHECK(lora2_group_bwd(1, I, o_h, a->act, dx_out, H, side(lw, lw->a_down, lg->a_down, lg->b_down, seed_l, 6),
-                              side(pw, pw->a_down, nullptr, nullptr, seed_p, 6), bc->down, off(u, 6 * (size_t)R), ldu, ws_v, ws->dact, accumulate, M,
-                              rowmask, st, 1));
-        CHECK(vlr_gemm_swiglu_bwd_add(dx_out, w->wdown, a->gu, ws->dact, ws->dact, M, I, H, st));   // gu now holds [dgate | dup]
-    } else {
-        CHECK(vlr_gemm_swiglu_bwd(dx_out, w->wdown, a->gu, ws->dact, M, I, H, st));
-    }
-    CHECK(vlr_gemm_bf16(1, a->gu, w->wgu, ws->dxn, nullptr, nullptr, M, H, 2 * I, 2 * I, H, H, 0, 0, 0, 0, st));
-    CHECK(lora2_group_bwd(2, H, o_gu, a->xn2, a->gu, 2 * I, side(lw, lw->a_gu, lg->a_gu, lg->b_gu, seed_l, 4), side(pw, pw->a_gu, nullptr, nullptr, seed_p, 4),
-                          bc->gu, off(u, 4 * (size_t)R), ldu, ws_v, ws->dxn, accumulate, M, rowmask, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, a->x_mid, w->ln2, a->rstd2, dx_out, ws->dx_mid, nullptr, 0, ws->norm_ws, M, H, st));
-    // ---- attention
-    CHECK(vlr_gemm_bf16(1, ws->dx_mid, w->wo, ws->dattn, nullptr, nullptr, M, H, H, H, H, H, 0, 0, 0, 0, st));
-    CHECK(lora2_group_bwd(1, H, o_h, a->attn, ws->dx_mid, H, side(lw, lw->a_o, lg->a_o, lg->b_o, seed_l, 3), side(pw, pw->a_o, nullptr, nullptr, seed_p, 3),
-                          bc->o, off(u, 3 * (size_t)R), ldu, ws_v, ws->dattn, accumulate, M, rowmask, st));
-    CHECK(vlr_attn_bwd_gqa(a->qkv, off(a->qkv, Nq), off(a->qkv, (size_t)Nq + Nkv), N, a->attn, ws->dattn, Nq, a->lse, ws->delta,
-                           key_mask, ws->dqkv, off(ws->dqkv, Nq), off(ws->dqkv, (size_t)Nq + Nkv), N, batch, S, cfg->heads, kvh,
-                           cfg->head_dim, 1, 1.0f / sqrtf((float)cfg->head_dim), st));
-    CHECK(vlr_rope_heads(ws->dqkv, pos, cfg->rope_cos, cfg->rope_sin, M, cfg->heads + kvh, cfg->head_dim, N, cfg->max_pos, 1, st));
-    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, H, N, N, H, H, 0, 0, 0, 0, st));
-    CHECK(lora2_group_bwd(nq, H, nq == 1 ? o_all : o_qkv, a->xn1, ws->dqkv, N, side(lw, lw->a_qkv, lg->a_qkv, lg->b_qkv, seed_l, 0),
-                          side(pw, pw->a_qkv, nullptr, nullptr, seed_p, 0), bc->qkv, u, ldu, ws_v, ws->dxn, accumulate, M, rowmask, st));
-    CHECK(norm_bwd(cfg->resid_f32, ws->dxn, x_in, w->ln1, a->rstd1, ws->dx_mid, dx_in, nullptr, 0, ws->norm_ws, M, H, st));
-    return VLR_OK;
+    LayerDims L;
+    CHECK(layer_dims("vlr_decoder_layer_bwd_lora2", cfg, batch, S, &L));
+    VLR_REQUIRE(L.Nq == L.H, "vlr_decoder_layer_bwd_lora2: heads*head_dim != hidden");
+    const Lora2Bwd ad = {lw, lg, pw, bc, u, ws_v, seed_l, seed_p, rowmask, accumulate, L, st};
+    return layer_bwd(cfg, L, w, nullptr, accumulate, a, ws, &ad, RowLayout{}, x_in, dx_out, dx_in, pos, key_mask, batch, S, st);
 }
 
 // CLIP encoder layer (transformers CLIPEncoderLayer, pre-LN, quick_gelu; call site Llava/__init__.py:178), in place on x
