@@ -274,6 +274,16 @@ int vlr_layernorm_bwd(const void* dy, const void* x, const void* w, float eps, v
                       void* workspace, int M, int D, vlr_stream_t stream);
 int vlr_vit_embed_ln(const void* patch_embeds, const void* cls, const void* pos, const void* w, const void* b, void* y,
                      int n_img, int T, int D, float eps, vlr_stream_t stream);
+/* backward of vlr_vit_embed_ln: dy [n_img*T][D] is the gradient of its output.  Recomputes cat(cls, patch_embeds) + pos and the
+ * LayerNorm statistics; writes d_patch_embeds [n_img*(T-1)][D] (overwritten) and d_cls [D], d_pos [T][D], d_w, d_b [D] (bf16;
+ * `accumulate`: +=).  The sums over images and rows run in a fixed order (no atomics); workspace = vlr_layernorm_bwd_workspace_bytes(D). */
+int vlr_vit_embed_ln_bwd(const void* dy, const void* patch_embeds, const void* cls, const void* pos, const void* w,
+                         void* d_patch_embeds, void* d_cls, void* d_pos, void* d_w, void* d_b, int accumulate, void* workspace,
+                         int n_img, int T, int D, float eps, vlr_stream_t stream);
+/* vlr_layernorm_bwd with the gradient of the residual branch around the norm: dx = dres + (LayerNorm backward), rounded once; dx may
+ * be dres.  dw and db are required. */
+int vlr_layernorm_bwd_res(const void* dy, const void* x, const void* w, float eps, const void* dres, void* dx, void* dw, void* db,
+                          int accumulate, void* workspace, int M, int D, vlr_stream_t stream);
 int vlr_im2col(const float* pixel_values, void* patches, int n_img, int image_size, int patch, int Kp, vlr_stream_t stream);
 int vlr_rope_table(float* cos_t, float* sin_t, int max_pos, int head_dim, float theta, vlr_stream_t stream);
 int vlr_rope(void* qkv, const int* pos, const float* cos_t, const float* sin_t, int M, int H, int head_dim, int ld,
@@ -288,6 +298,10 @@ int vlr_swiglu_bwd(void* gate_up_inout, const void* dact, int M, int I, vlr_stre
 int vlr_swiglu_bwd_src(const void* gu_src, const int* src_rows, void* dgu_out, const void* dact, int M, int I, vlr_stream_t stream);
 int vlr_gelu_fwd(const void* z, void* h, long n, vlr_stream_t stream);
 int vlr_gelu_bwd(const void* z, const void* dh, void* dz, long n, vlr_stream_t stream);
+/* the ViT MLP's activation as a row-wise pass (the layer backward recomputes z and needs h = act(z), dz = dh * act'(z)): act 1 quick-GELU
+ * z sigma(1.702 z), act 2 the erf GELU of vlr_gelu_*.  bf16 in / out, fp32 arithmetic, any n >= 1, 16-byte aligned; dz may be dh. */
+int vlr_act_fwd(const void* z, void* h, long n, int act, vlr_stream_t stream);
+int vlr_act_bwd(const void* z, const void* dh, void* dz, long n, int act, vlr_stream_t stream);
 int vlr_colsum_workspace_bytes(int C);
 int vlr_colsum(const void* X, int R, int C, int ld, void* out, int accumulate, void* workspace, vlr_stream_t stream);
 int vlr_colsum_f32(const void* X, int R, int C, int ld, float* out, void* workspace, vlr_stream_t stream);
@@ -831,6 +845,23 @@ typedef struct {  /* bf16; q|k|v fused [3D][D] + bias [3D] */
 typedef struct { void* xn; void* qkv; void* attn; void* h; } vlr_vit_ws;   /* [M][D], [M][3D], [M][D], [M][mlp] */
 int vlr_vit_layer_fwd(const vlr_vit_cfg* cfg, const vlr_vit_layer_weights* w, const vlr_vit_ws* ws, void* x_inout,
                       int n_img, int T, vlr_stream_t stream);
+/* Backward of one CLIP encoder layer for a trainable tower (--freeze_vision_tower False; replaces autograd through transformers
+ * CLIPEncoderLayer).  vlr_vit_layer_fwd keeps nothing, so the layer is first recomputed from its input x_in [n_img*T][hidden] into ws
+ * (fc1 without the fused activation, so that z exists; h = act(z)), then the chain runs backwards: NN / TN GEMMs, vlr_colsum for the four
+ * biases, vlr_layernorm_bwd_res twice, vlr_act_bwd, vlr_attn_bwd (full attention, head_dim 64 or 128).  dx_inout [n_img*T][hidden] holds
+ * dL/dx_out on entry and dL/dx_in on return.  grads mirrors the weights (bf16; `accumulate`: +=).  Fixed summation orders, no atomics.
+ * A padded head_dim (Qwen-VL's tower) is refused.  ws: xn1, attn, x_mid, xn2, dxn, dattn [M][hidden] (dxn and dattn may be one buffer);
+ * qkv, dqkv [M][3*hidden]; z, h, dh [M][mlp]; lse, delta fp32 [n_img][heads][ceil64(T)]; norm_ws vlr_vit_layer_bwd_workspace_bytes. */
+typedef struct {
+    void* ln1_w; void* ln1_b; void* wqkv; void* bqkv; void* wo; void* bo; void* ln2_w; void* ln2_b; void* w1; void* b1; void* w2; void* b2;
+} vlr_vit_layer_grads;
+typedef struct {
+    void* xn1; void* qkv; void* attn; float* lse; void* x_mid; void* xn2; void* z; void* h;
+    void* dh; void* dxn; void* dattn; void* dqkv; float* delta; void* norm_ws;
+} vlr_vit_bwd_ws;
+int vlr_vit_layer_bwd_workspace_bytes(int hidden, int mlp);
+int vlr_vit_layer_bwd(const vlr_vit_cfg* cfg, const vlr_vit_layer_weights* w, const vlr_vit_layer_grads* grads, int accumulate,
+                      const void* x_in, const vlr_vit_bwd_ws* ws, void* dx_inout, int n_img, int T, vlr_stream_t stream);
 
 /* ---- decoding with a KV cache (replaces transformers LlamaAttention / LlamaMLP with a DynamicCache during GenerationMixin.generate:
  *      one new token per sequence per step, the K / V of every earlier token kept per layer; reference call site

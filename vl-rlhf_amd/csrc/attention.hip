@@ -1,5 +1,5 @@
 // Fused attention for gfx950 (MI355X): forward (causal + key-padding mask for the LLaMA decoder, D=128; full
-// attention for the CLIP ViT, D=64) and backward (D=128).  No S x S matrix is ever written to HBM.
+// attention for the CLIP ViT, D=64) and backward (D=128; D=64 on the register-staged pair).  No S x S matrix is ever written to HBM.
 //
 // Tiling is built around v_mfma_f32_32x32x16_bf16 with the SWAPPED product S^T = K . Q^T so that a query's row of
 // scores lives in ONE lane pair (l, l^32): softmax statistics are lane-local + one cross-lane exchange, and the
@@ -613,8 +613,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const bf16_t* __restr
 #include "attn_fwd3.h"
 
 // ------------------------------------------------------------------------------------------------------------
-// delta[b][h][s] = sum_d dO[s][h*128+d] * O[s][h*128+d]   (D = 128)
+// delta[b][h][s] = sum_d dO[s][h*D+d] * O[s][h*D+d]   (D/8 lanes per head)
 // ------------------------------------------------------------------------------------------------------------
+template <int D>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ out,
                                                          int ldo, float* __restrict__ delta, int S, int Sp, int nh) {
     // one workgroup per PADDED row: rows [S, Sp) are written as zeros - the dK,dV kernel multiplies P (exactly 0 there: lse is
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
         return;
     }
     const size_t row = (size_t)b * S + s;   // token row
-    for (int c = threadIdx.x * 8; c < nh * 128; c += 256 * 8) {
+    for (int c = threadIdx.x * 8; c < nh * D; c += 256 * 8) {
         float a[8], d[8];
         unpack8(*reinterpret_cast<const u32x4*>(dout + row * ldo + c), a);
         unpack8(*reinterpret_cast<const u32x4*>(out + row * ldo + c), d);
@@ -633,23 +634,25 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
 #pragma unroll
         for (int e = 0; e < 8; ++e) sum += a[e] * d[e];
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        if ((threadIdx.x & 15) == 0) delta[((size_t)b * nh + c / 128) * Sp + s] = sum;
+        for (int o = D / 16; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        if ((threadIdx.x & (D / 8 - 1)) == 0) delta[((size_t)b * nh + c / D) * Sp + s] = sum;
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // Backward, dQ:  grid (ceil(S/128), heads, batch); wave owns 32 queries, loops over KV tiles.
 //   S^T = K Q^T, dP^T = V dO^T, dS^T = P^T o (dP^T - delta),  dQ^T += K^T dS^T * scale
+// D = 128: the decoder past ATTN_MAX_TILES key tiles or with VLR_ATTN_DMA=0; D = 64: the CLIP ViT of a trainable tower (D / 16 K-steps,
+// D / 32 accumulator blocks, two [64][D] LDS tiles).  Build report, full / causal: D = 64 142 / 146 VGPR + 64 AGPR, 16.5 KiB LDS;
+// D = 128 204 / 236 VGPR + 96 AGPR, 32.5 KiB LDS; no scratch.
 // ------------------------------------------------------------------------------------------------------------
-template <bool CAUSAL>
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                           const bf16_t* __restrict__ v, int ld,
                                                           const bf16_t* __restrict__ dout, int ldo,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           const int* __restrict__ kmask, bf16_t* __restrict__ dq, int lddq,
                                                           int S, int Sp, float scale) {
-    constexpr int D = 128;
     __shared__ __attribute__((aligned(16))) char smem[KV_TILE * D * 2 * 2 + KV_TILE * 4];
     char* k_lds = smem;
     char* v_lds = smem + KV_TILE * D * 2;
@@ -667,18 +670,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
     const int qrow = qi < S ? qi : S - 1;
     const float scale_log2 = scale * LOG2E;
 
-    bf16x8 qf[8], dof[8];
+    bf16x8 qf[D / 16], dof[D / 16];
 #pragma unroll
-    for (int st = 0; st < 8; ++st) {
+    for (int st = 0; st < D / 16; ++st) {
         qf[st] = *reinterpret_cast<const bf16x8*>(qh + (size_t)qrow * ld + 16 * st + 8 * g);
         dof[st] = *reinterpret_cast<const bf16x8*>(doh + (size_t)qrow * ldo + 16 * st + 8 * g);
     }
     const float L2 = qi < S ? lse[((size_t)b * nh + head) * Sp + qrow] : INFINITY;
     const float dl = delta[((size_t)b * nh + head) * Sp + qrow];
 
-    f32x16 acc[4];
+    f32x16 acc[D / 32];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
@@ -705,7 +708,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-            for (int st = 0; st < 8; ++st) {
+            for (int st = 0; st < D / 16; ++st) {
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(k_lds, kb * 32, 2 * st, lane), qf[st], s, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(v_lds, kb * 32, 2 * st, lane), dof[st], dp, 0, 0, 0);
             }
@@ -730,7 +733,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
                 const bf16x8 dsf = pack_frag(s, h);
                 const int ks = kb * 2 + h;
 #pragma unroll
-                for (int db = 0; db < 4; ++db)
+                for (int db = 0; db < D / 32; ++db)
                     acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(k_lds, db * 32, ks, lane), dsf, acc[db], 0, 0, 0);
             }
         }
@@ -741,15 +744,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16_t* __restri
 // ------------------------------------------------------------------------------------------------------------
 // Backward, dK and dV: grid (ceil(S/128), heads, batch); wave owns 32 keys, loops over 64-query tiles.
 //   S = Q K^T, dP = dO V^T (key lane-local),  dV^T += dO^T P,  dK^T += Q^T dS * scale
+// Build report, full / causal: D = 64 194 / 178 VGPR + 96 AGPR, 16 KiB LDS; D = 128 202 / 256 VGPR + 160 / 220 AGPR, 32 KiB LDS; no scratch.
 // ------------------------------------------------------------------------------------------------------------
-template <bool CAUSAL>
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                            const bf16_t* __restrict__ v, int ld,
                                                            const bf16_t* __restrict__ dout, int ldo,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            const int* __restrict__ kmask, bf16_t* __restrict__ dk,
                                                            bf16_t* __restrict__ dv, int lddkv, int S, int Sp, float scale) {
-    constexpr int D = 128;
     __shared__ __attribute__((aligned(16))) char smem[KV_TILE * D * 2 * 2];
     char* q_lds = smem;
     char* do_lds = smem + KV_TILE * D * 2;
@@ -769,15 +772,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
     const bool any_bad_key = __builtin_amdgcn_ballot_w64(!key_ok) != 0;
     const float scale_log2 = scale * LOG2E;
 
-    bf16x8 kf[8], vf[8];
+    bf16x8 kf[D / 16], vf[D / 16];
 #pragma unroll
-    for (int st = 0; st < 8; ++st) {
+    for (int st = 0; st < D / 16; ++st) {
         kf[st] = *reinterpret_cast<const bf16x8*>(kh + (size_t)krow * ld + 16 * st + 8 * g);
         vf[st] = *reinterpret_cast<const bf16x8*>(vh + (size_t)krow * ld + 16 * st + 8 * g);
     }
-    f32x16 adk[4], adv[4];
+    f32x16 adk[D / 32], adv[D / 32];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { adk[i][r] = 0.f; adv[i][r] = 0.f; }
 
@@ -802,7 +805,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-            for (int st = 0; st < 8; ++st) {
+            for (int st = 0; st < D / 16; ++st) {
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(q_lds, qb * 32, 2 * st, lane), kf[st], s, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<D>(do_lds, qb * 32, 2 * st, lane), vf[st], dp, 0, 0, 0);
             }
@@ -829,7 +832,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16_t* __restr
                 const bf16x8 dsf = pack_frag(s, h);
                 const int ks = qb * 2 + h;
 #pragma unroll
-                for (int db = 0; db < 4; ++db) {
+                for (int db = 0; db < D / 32; ++db) {
                     adv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(do_lds, db * 32, ks, lane), pf, adv[db], 0, 0, 0);
                     adk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(q_lds, db * 32, ks, lane), dsf, adk[db], 0, 0, 0);
                 }
@@ -1432,13 +1435,31 @@ extern "C" int vlr_attn_bwd_gqa(const void* q, const void* k, const void* v, int
                                 float scale, hipStream_t st) {
     VLR_REQUIRE(batch > 0 && S > 0 && heads > 0, "vlr_attn_bwd: bad shape");
     VLR_REQUIRE(kv_heads > 0 && heads % kv_heads == 0, "vlr_attn_bwd: heads %d is not a multiple of kv_heads %d", heads, kv_heads);
-    VLR_REQUIRE(head_dim == 128, "vlr_attn_bwd: head_dim must be 128 (the ViT is frozen), got %d", head_dim);
+    VLR_REQUIRE(head_dim == 128 || head_dim == 64, "vlr_attn_bwd: head_dim must be 64 or 128, got %d", head_dim);
     VLR_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && ldd % 8 == 0 && delta_ws && lse, "vlr_attn_bwd: strides / workspace");
+    if (head_dim == 64) {
+        // the CLIP ViT's width: the register-staged pair at D = 64 (any S; the LDS-DMA pair below is written for D = 128)
+        VLR_REQUIRE(heads == kv_heads, "vlr_attn_bwd: head_dim 64 has no grouped-query form (heads %d, kv_heads %d)", heads, kv_heads);
+        const int Sp64 = (S + 63) / 64 * 64;
+        const int pj = vlr_prof_begin(VLR_K_ATTN_BWD, 10.0 * S * S * heads * head_dim * batch * (causal ? 0.5 : 1.0), st);
+        hipLaunchKernelGGL(attn_delta_kernel<64>, dim3(batch * Sp64), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)o, ldo,
+                           delta_ws, S, Sp64, heads);
+        const dim3 grid64((S + 127) / 128, heads, batch);
+#define LAUNCH_BWD64(C)                                                                                                            \
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<64, C>), grid64, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,              \
+                           (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dq, ldd, S, Sp64, scale); \
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, C>), grid64, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,             \
+                           (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp64, scale)
+        if (causal) { LAUNCH_BWD64(true); } else { LAUNCH_BWD64(false); }
+#undef LAUNCH_BWD64
+        vlr_prof_end(pj, st);
+        return vlr_check_launch("vlr_attn_bwd");
+    }
     const bool dma = attn_dma_on() && S <= ATTN_MAX_TILES * KV_TILE;
     VLR_REQUIRE(dma || heads == kv_heads, "vlr_attn_bwd: grouped-query attention needs the LDS-DMA kernels (S <= %d, VLR_ATTN_DMA != 0)", ATTN_MAX_TILES * KV_TILE);
     const int Sp = (S + 63) / 64 * 64;   // lse and delta_ws are [batch][heads][Sp] floats
     const int pi = vlr_prof_begin(VLR_K_ATTN_BWD, 10.0 * S * S * heads * head_dim * batch * (causal ? 0.5 : 1.0), st);
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(batch * Sp), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)o, ldo,
+    hipLaunchKernelGGL(attn_delta_kernel<128>, dim3(batch * Sp), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)o, ldo,
                        delta_ws, S, Sp, heads);
     const dim3 grid((S + 127) / 128, heads, batch);
     constexpr int LDS_DQ = 4 * KV_TILE * 128 * 2 + ATTN_MAX_TILES * 8, LDS_DKV = 4 * KV_TILE * 128 * 2 + 1024;
@@ -1468,14 +1489,14 @@ extern "C" int vlr_attn_bwd_gqa(const void* q, const void* k, const void* v, int
                                (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale, ag);
         }
     } else if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<true>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<128, true>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
                            (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dq, ldd, S, Sp, scale);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, true>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
                            (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale);
     } else {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<false>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<128, false>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
                            (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dq, ldd, S, Sp, scale);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<false>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, false>), grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
                            (const bf16_t*)v, ld, (const bf16_t*)dout, ldo, lse, delta_ws, key_mask, (bf16_t*)dk, (bf16_t*)dv, ldd, S, Sp, scale);
     }
     vlr_prof_end(pi, st);

@@ -271,8 +271,8 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_t* __res
 // dw = sum_rows dy * xh, db = sum_rows dy -> per-block partials [G][D] | [G][D], reduced in a fixed order
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
-                                                            const bf16_t* __restrict__ w, float eps, bf16_t* __restrict__ dx,
-                                                            float* __restrict__ part, int M, int D) {
+                                                            const bf16_t* __restrict__ w, float eps, bf16_t* dx,
+                                                            const bf16_t* dres, float* __restrict__ part, int M, int D) {
     __shared__ float red[16];
     constexpr int MAXC = 2;  // D <= 4096
     float dwacc[MAXC][8], dbacc[MAXC][8];
@@ -336,6 +336,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
                     float o[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = rs * (gv[i][e] - sg - xv[i][e] * sgx);
+                    if (dres) {      // the gradient of the residual branch around the norm (may be dx itself: a thread reads its own 8 first)
+                        float r[8];
+                        unpack8(*reinterpret_cast<const u32x4*>(dres + off + c), r);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) o[e] += r[e];
+                    }
                     *reinterpret_cast<u32x4*>(dx + off + c) = pack8(o);
                 }
             }
@@ -354,7 +360,141 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// LayerNorm forward (CLIP ViT; frozen tower, no backward).  Optional fused "embedding assemble": when pe != null the
+// Backward of vlr_vit_embed_ln (CLIPVisionEmbeddings + pre_layrnorm with a trainable tower).  Row (b, t) of the forward is
+// v = (t == 0 ? cls : pe[b][t-1]) + pos[t], y = LayerNorm(v) * w + b.  Workgroup g owns the positions t = g, g + G, ...; for each it
+// walks the images b = 0, 1, ... in order, recomputes v and its statistics, forms dv (the LayerNorm backward of layernorm_bwd_kernel),
+// stores it as d pe[b][t-1] and sums it over the images in registers: d pos[t] (and d cls at t == 0) are written by their one owner,
+// in a fixed order.  d w / d b leave as per-workgroup partials [G][D] | [G][D] like layernorm_bwd_kernel's.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vit_embed_ln_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ pe,
+                                                               const bf16_t* __restrict__ cls, const bf16_t* __restrict__ pos,
+                                                               const bf16_t* __restrict__ w, float eps, bf16_t* __restrict__ dpe,
+                                                               bf16_t* __restrict__ dcls, bf16_t* __restrict__ dpos,
+                                                               float* __restrict__ part, int n_img, int T, int D, int accumulate) {
+    __shared__ float red[16];
+    constexpr int MAXC = 2;  // D <= 4096
+    float dwacc[MAXC][8], dbacc[MAXC][8];
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dwacc[i][e] = dbacc[i][e] = 0.f;
+    for (int t = blockIdx.x; t < T; t += gridDim.x) {
+        float pv[MAXC][8], wv[MAXC][8], dsum[MAXC][8];
+#pragma unroll
+        for (int i = 0; i < MAXC; ++i) {
+            const int c = (i * 256 + threadIdx.x) * 8;
+            if (c < D) {
+                unpack8(*reinterpret_cast<const u32x4*>(pos + (size_t)t * D + c), pv[i]);
+                unpack8(*reinterpret_cast<const u32x4*>(w + c), wv[i]);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dsum[i][e] = 0.f;
+        }
+        for (int b = 0; b < n_img; ++b) {
+            const size_t off = ((size_t)b * T + t) * D;
+            const bf16_t* src = t == 0 ? cls : pe + ((size_t)b * (T - 1) + t - 1) * D;
+            float xv[MAXC][8], gv[MAXC][8];
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i) {
+                const int c = (i * 256 + threadIdx.x) * 8;
+                if (c < D) {
+                    unpack8(*reinterpret_cast<const u32x4*>(src + c), xv[i]);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        xv[i][e] += pv[i][e];
+                        s += xv[i][e];
+                    }
+                }
+            }
+            const float mean = block_sum(s, red) / (float)D;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i) {
+                const int c = (i * 256 + threadIdx.x) * 8;
+                if (c < D) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        xv[i][e] -= mean;
+                        q += xv[i][e] * xv[i][e];
+                    }
+                }
+            }
+            const float rs = rsqrtf(block_sum(q, red) / (float)D + eps);
+            float sg = 0.f, sgx = 0.f;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i) {
+                const int c = (i * 256 + threadIdx.x) * 8;
+                if (c < D) {
+                    float dv[8];
+                    unpack8(*reinterpret_cast<const u32x4*>(dy + off + c), dv);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        xv[i][e] *= rs;                       // xh
+                        gv[i][e] = dv[e] * wv[i][e];
+                        sg += gv[i][e];
+                        sgx += gv[i][e] * xv[i][e];
+                        dwacc[i][e] += dv[e] * xv[i][e];
+                        dbacc[i][e] += dv[e];
+                    }
+                }
+            }
+            sg = block_sum(sg, red) / (float)D;
+            sgx = block_sum(sgx, red) / (float)D;
+#pragma unroll
+            for (int i = 0; i < MAXC; ++i) {
+                const int c = (i * 256 + threadIdx.x) * 8;
+                if (c < D) {
+                    float o[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        o[e] = rs * (gv[i][e] - sg - xv[i][e] * sgx);
+                        dsum[i][e] += o[e];
+                    }
+                    if (t > 0) *reinterpret_cast<u32x4*>(dpe + ((size_t)b * (T - 1) + t - 1) * D + c) = pack8(o);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < MAXC; ++i) {
+            const int c = (i * 256 + threadIdx.x) * 8;
+            if (c < D) {
+                float o[8], a[8];
+                if (accumulate) {
+                    unpack8(*reinterpret_cast<const u32x4*>(dpos + (size_t)t * D + c), a);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] = dsum[i][e] + a[e];
+                    *reinterpret_cast<u32x4*>(dpos + (size_t)t * D + c) = pack8(o);
+                } else {
+                    *reinterpret_cast<u32x4*>(dpos + (size_t)t * D + c) = pack8(dsum[i]);
+                }
+                if (t == 0) {
+                    if (accumulate) {
+                        unpack8(*reinterpret_cast<const u32x4*>(dcls + c), a);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) o[e] = dsum[i][e] + a[e];
+                        *reinterpret_cast<u32x4*>(dcls + c) = pack8(o);
+                    } else {
+                        *reinterpret_cast<u32x4*>(dcls + c) = pack8(dsum[i]);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+        const int c = (i * 256 + threadIdx.x) * 8;
+        if (c < D) {
+            float* d = part + (size_t)blockIdx.x * D + c;
+            float* b = part + (size_t)(gridDim.x + blockIdx.x) * D + c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { d[e] = dwacc[i][e]; b[e] = dbacc[i][e]; }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// LayerNorm forward (CLIP ViT; its backward: layernorm_bwd_kernel, vit_embed_ln_bwd_kernel).  Optional fused "embedding assemble": when pe != null the
 // input row (b, t) is (t == 0 ? cls : pe[b, t-1]) + pos[t]  (CLIPVisionEmbeddings + pre_layrnorm).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
@@ -550,6 +690,48 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict_
         }
         *reinterpret_cast<u32x4*>(dz + i * 8) = pack8(d);
     }
+}
+
+// MLP activation of the CLIP ViT layer when its backward recomputes the layer (vlr_vit_layer_bwd): act 1 quick-GELU z sigma(1.702 z)
+// (the arithmetic of the GEMM epilogue's apply_act), act 2 the erf GELU above.  Any n: 8 elements per thread, then a scalar tail.
+__device__ __forceinline__ float act_fwd1(float z, int act) {
+    if (act == 1) return z / (1.f + __expf(-1.702f * z));
+    return 0.5f * z * (1.f + erff(z * 0.70710678118654752f));
+}
+__device__ __forceinline__ float act_bwd1(float z, float dh, int act) {
+    if (act == 1) {
+        const float sg = 1.f / (1.f + __expf(-1.702f * z));
+        return dh * sg * (1.f + 1.702f * z * (1.f - sg));
+    }
+    const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752f));
+    const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
+    return dh * (cdf + z * pdf);
+}
+__global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__ z, bf16_t* __restrict__ h, long n, int act) {
+    const long n8 = n / 8;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        float v[8];
+        unpack8(*reinterpret_cast<const u32x4*>(z + i * 8), v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = act_fwd1(v[e], act);
+        *reinterpret_cast<u32x4*>(h + i * 8) = pack8(v);
+    }
+    const long j = n8 * 8 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 8 && j < n) h[j] = f32_to_bf16(act_fwd1(bf16_to_f32(z[j]), act));
+}
+// dz may be dh (each thread reads its own elements before it writes them)
+__global__ __launch_bounds__(256) void act_bwd_kernel(const bf16_t* __restrict__ z, const bf16_t* dh, bf16_t* dz, long n, int act) {
+    const long n8 = n / 8;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        float v[8], d[8];
+        unpack8(*reinterpret_cast<const u32x4*>(z + i * 8), v);
+        unpack8(*reinterpret_cast<const u32x4*>(dh + i * 8), d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] = act_bwd1(v[e], d[e], act);
+        *reinterpret_cast<u32x4*>(dz + i * 8) = pack8(d);
+    }
+    const long j = n8 * 8 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 8 && j < n) dz[j] = f32_to_bf16(act_bwd1(bf16_to_f32(z[j]), bf16_to_f32(dh[j]), act));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -979,11 +1161,23 @@ extern "C" int vlr_layernorm_bwd(const void* dy, const void* x, const void* w, f
     VLR_REQUIRE(M > 0 && D % 8 == 0 && D <= 4096 && workspace, "vlr_layernorm_bwd: bad shape M=%d D=%d", M, D);
     const int G = M < VLR_LN_BWD_BLOCKS ? M : VLR_LN_BWD_BLOCKS;
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, eps,
-                       (bf16_t*)dx, (float*)workspace, M, D);
+                       (bf16_t*)dx, (const bf16_t*)nullptr, (float*)workspace, M, D);
     if (dw) hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace, G, D, (bf16_t*)dw, accumulate);
     if (db) hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace + (size_t)G * D, G, D,
                                (bf16_t*)db, accumulate);
     return vlr_check_launch("vlr_layernorm_bwd");
+}
+// the same with the gradient of the residual branch around the norm: dx = dres + (LayerNorm backward), one rounding; dx may be dres
+extern "C" int vlr_layernorm_bwd_res(const void* dy, const void* x, const void* w, float eps, const void* dres, void* dx, void* dw,
+                                     void* db, int accumulate, void* workspace, int M, int D, hipStream_t st) {
+    VLR_REQUIRE(M > 0 && D % 8 == 0 && D <= 4096 && workspace && dres && dx && dw && db, "vlr_layernorm_bwd_res: bad shape M=%d D=%d", M, D);
+    const int G = M < VLR_LN_BWD_BLOCKS ? M : VLR_LN_BWD_BLOCKS;
+    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, eps,
+                       (bf16_t*)dx, (const bf16_t*)dres, (float*)workspace, M, D);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace, G, D, (bf16_t*)dw, accumulate);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace + (size_t)G * D, G, D,
+                       (bf16_t*)db, accumulate);
+    return vlr_check_launch("vlr_layernorm_bwd_res");
 }
 
 extern "C" int vlr_layernorm_fwd(const void* x, const void* w, const void* b, void* y, int M, int D, float eps,
@@ -1001,6 +1195,24 @@ extern "C" int vlr_vit_embed_ln(const void* patch_embeds, const void* cls, const
                        (const bf16_t*)b, (bf16_t*)y, D, eps, (const bf16_t*)patch_embeds, (const bf16_t*)cls,
                        (const bf16_t*)pos, T);
     return vlr_check_launch("vlr_vit_embed_ln");
+}
+
+// backward of vlr_vit_embed_ln: dy [n_img*T][D] -> d patch_embeds [n_img*(T-1)][D] (overwritten), d cls [D], d pos [T][D], d w, d b
+// [D] (bf16; `accumulate`: +=); workspace = vlr_layernorm_bwd_workspace_bytes(D)
+extern "C" int vlr_vit_embed_ln_bwd(const void* dy, const void* patch_embeds, const void* cls, const void* pos, const void* w,
+                                    void* d_patch_embeds, void* d_cls, void* d_pos, void* d_w, void* d_b, int accumulate,
+                                    void* workspace, int n_img, int T, int D, float eps, hipStream_t st) {
+    VLR_REQUIRE(dy && patch_embeds && cls && pos && w && d_patch_embeds && d_cls && d_pos && d_w && d_b && workspace,
+                "vlr_vit_embed_ln_bwd: null argument");
+    VLR_REQUIRE(n_img > 0 && T > 1 && D > 0 && D % 8 == 0 && D <= 4096, "vlr_vit_embed_ln_bwd: bad shape n_img=%d T=%d D=%d", n_img, T, D);
+    const int G = T < VLR_LN_BWD_BLOCKS ? T : VLR_LN_BWD_BLOCKS;
+    hipLaunchKernelGGL(vit_embed_ln_bwd_kernel, dim3(G), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)patch_embeds, (const bf16_t*)cls,
+                       (const bf16_t*)pos, (const bf16_t*)w, eps, (bf16_t*)d_patch_embeds, (bf16_t*)d_cls, (bf16_t*)d_pos, (float*)workspace,
+                       n_img, T, D, accumulate);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace, G, D, (bf16_t*)d_w, accumulate);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const float*)workspace + (size_t)G * D, G, D,
+                       (bf16_t*)d_b, accumulate);
+    return vlr_check_launch("vlr_vit_embed_ln_bwd");
 }
 
 extern "C" int vlr_rope_table(float* cos_t, float* sin_t, int max_pos, int head_dim, float theta, hipStream_t st) {
@@ -1055,6 +1267,19 @@ extern "C" int vlr_gelu_bwd(const void* z, const void* dh, void* dz, long n, hip
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)dh,
                        (bf16_t*)dz, n / 8);
     return vlr_check_launch("vlr_gelu_bwd");
+}
+extern "C" int vlr_act_fwd(const void* z, void* h, long n, int act, hipStream_t st) {
+    VLR_REQUIRE(z && h && n > 0 && (act == 1 || act == 2), "vlr_act_fwd: n %ld act %d (1 quick_gelu, 2 gelu)", n, act);
+    VLR_REQUIRE(!(((uintptr_t)z | (uintptr_t)h) & 15), "vlr_act_fwd: 16-byte aligned operands");
+    hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for((n + 7) / 8, 256)), dim3(256), 0, st, (const bf16_t*)z, (bf16_t*)h, n, act);
+    return vlr_check_launch("vlr_act_fwd");
+}
+extern "C" int vlr_act_bwd(const void* z, const void* dh, void* dz, long n, int act, hipStream_t st) {
+    VLR_REQUIRE(z && dh && dz && n > 0 && (act == 1 || act == 2), "vlr_act_bwd: n %ld act %d (1 quick_gelu, 2 gelu)", n, act);
+    VLR_REQUIRE(!(((uintptr_t)z | (uintptr_t)dh | (uintptr_t)dz) & 15), "vlr_act_bwd: 16-byte aligned operands");
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for((n + 7) / 8, 256)), dim3(256), 0, st, (const bf16_t*)z, (const bf16_t*)dh, (bf16_t*)dz,
+                       n, act);
+    return vlr_check_launch("vlr_act_bwd");
 }
 extern "C" int vlr_dropout(const void* x, void* out, long n, float p, uint64_t seed, float alpha, int add, hipStream_t st) {
     VLR_REQUIRE(n > 0 && n % 8 == 0 && p >= 0.f && p < 1.f, "vlr_dropout: n %% 8 == 0 and 0 <= p < 1 required (n=%ld p=%g)", n, (double)p);

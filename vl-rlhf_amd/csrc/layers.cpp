@@ -1062,3 +1062,61 @@ extern "C" int vlr_vit_layer_fwd(const vlr_vit_cfg* cfg, const vlr_vit_layer_wei
     CHECK(vlr_gemm_bf16(0, ws->h, w->w2, x, w->b2, x, M, D, F, F, F, D, D, 0, 0, 0, st));
     return VLR_OK;
 }
+
+// Backward of one CLIP encoder layer with a trainable tower.  The forward above keeps nothing: the layer is recomputed from its input
+// x_in into ws (LN1, q|k|v, attention with lse, out-projection + residual, LN2, fc1 WITHOUT the fused activation so that z exists,
+// h = act(z)), then the chain runs backwards on existing kernels.  dx holds dL/dx_out on entry and dL/dx_in on return; the residual
+// gradient is carried in it (vlr_layernorm_bwd_res adds the norm's branch in place).  Weight gradients by TN GEMMs, bias gradients by
+// vlr_colsum, everything in a fixed order: two calls on the same inputs give the same bits.
+extern "C" int vlr_vit_layer_bwd_workspace_bytes(int hidden, int mlp) {
+    const int c = 3 * hidden > mlp ? 3 * hidden : mlp;
+    const int a = vlr_layernorm_bwd_workspace_bytes(hidden), b = vlr_colsum_workspace_bytes(c);
+    return a > b ? a : b;
+}
+extern "C" int vlr_vit_layer_bwd(const vlr_vit_cfg* cfg, const vlr_vit_layer_weights* w, const vlr_vit_layer_grads* g, int accumulate,
+                                 const void* x_in, const vlr_vit_bwd_ws* ws, void* dx, int n_img, int T, vlr_stream_t st) {
+    VLR_REQUIRE(cfg && w && g && x_in && ws && dx, "vlr_vit_layer_bwd: null argument");
+    VLR_REQUIRE(ws->xn1 && ws->qkv && ws->attn && ws->lse && ws->x_mid && ws->xn2 && ws->z && ws->h && ws->dh && ws->dxn && ws->dattn &&
+                ws->dqkv && ws->delta && ws->norm_ws, "vlr_vit_layer_bwd: null workspace member");
+    VLR_REQUIRE(g->ln1_w && g->ln1_b && g->wqkv && g->bqkv && g->wo && g->bo && g->ln2_w && g->ln2_b && g->w1 && g->b1 && g->w2 && g->b2,
+                "vlr_vit_layer_bwd: null gradient member");
+    VLR_REQUIRE(n_img > 0 && T > 0, "vlr_vit_layer_bwd: bad shape n_img=%d T=%d", n_img, T);
+    const int D = cfg->hidden, F = cfg->mlp, M = n_img * T;
+    VLR_REQUIRE(cfg->heads * cfg->head_dim == D, "vlr_vit_layer_bwd: heads*head_dim != hidden");
+    VLR_REQUIRE(cfg->head_dim_pad <= cfg->head_dim, "vlr_vit_layer_bwd: a padded head_dim (%d -> %d) has no backward", cfg->head_dim,
+                cfg->head_dim_pad);
+    const float scale = cfg->attn_scale > 0.f ? cfg->attn_scale : 1.0f / sqrtf((float)cfg->head_dim);
+    const int act = cfg->act == 2 ? 2 /*gelu*/ : 1 /*quick_gelu*/;
+    const int acc = accumulate ? 1 : 0;
+    // ---- the layer again, from x_in
+    CHECK(vlr_layernorm_fwd(x_in, w->ln1_w, w->ln1_b, ws->xn1, M, D, cfg->ln_eps, st));
+    CHECK(vlr_gemm_bf16(0, ws->xn1, w->wqkv, ws->qkv, w->bqkv, nullptr, M, 3 * D, D, D, D, 3 * D, 0, 0, 0, 0, st));
+    CHECK(vlr_attn_fwd(ws->qkv, off(ws->qkv, D), off(ws->qkv, 2 * (size_t)D), 3 * D, ws->attn, D, ws->lse, nullptr, n_img, T, cfg->heads,
+                       cfg->head_dim, 0, scale, st));
+    CHECK(vlr_gemm_bf16(0, ws->attn, w->wo, ws->x_mid, w->bo, x_in, M, D, D, D, D, D, D, 0, 0, 0, st));
+    CHECK(vlr_layernorm_fwd(ws->x_mid, w->ln2_w, w->ln2_b, ws->xn2, M, D, cfg->ln_eps, st));
+    CHECK(vlr_gemm_bf16(0, ws->xn2, w->w1, ws->z, w->b1, nullptr, M, F, D, D, D, F, 0, 0, 0, 0, st));
+    CHECK(vlr_act_fwd(ws->z, ws->h, (long)M * F, act, st));
+    // ---- fc2: x_out = x_mid + h W2^T + b2
+    CHECK(vlr_gemm_bf16(2, dx, ws->h, g->w2, nullptr, nullptr, D, F, M, D, F, F, 0, 0, acc, 0, st));
+    CHECK(vlr_colsum(dx, M, D, D, g->b2, acc, ws->norm_ws, st));
+    CHECK(vlr_gemm_bf16(1, dx, w->w2, ws->dh, nullptr, nullptr, M, F, D, D, F, F, 0, 0, 0, 0, st));
+    CHECK(vlr_act_bwd(ws->z, ws->dh, ws->dh, (long)M * F, act, st));                                  // dh <- dz
+    // ---- fc1: z = xn2 W1^T + b1
+    CHECK(vlr_gemm_bf16(2, ws->dh, ws->xn2, g->w1, nullptr, nullptr, F, D, M, F, D, D, 0, 0, acc, 0, st));
+    CHECK(vlr_colsum(ws->dh, M, F, F, g->b1, acc, ws->norm_ws, st));
+    CHECK(vlr_gemm_bf16(1, ws->dh, w->w1, ws->dxn, nullptr, nullptr, M, D, F, F, D, D, 0, 0, 0, 0, st));
+    CHECK(vlr_layernorm_bwd_res(ws->dxn, ws->x_mid, w->ln2_w, cfg->ln_eps, dx, dx, g->ln2_w, g->ln2_b, acc, ws->norm_ws, M, D, st));   // dx <- d x_mid
+    // ---- out-projection: x_mid = x_in + attn Wo^T + bo
+    CHECK(vlr_gemm_bf16(2, dx, ws->attn, g->wo, nullptr, nullptr, D, D, M, D, D, D, 0, 0, acc, 0, st));
+    CHECK(vlr_colsum(dx, M, D, D, g->bo, acc, ws->norm_ws, st));
+    CHECK(vlr_gemm_bf16(1, dx, w->wo, ws->dattn, nullptr, nullptr, M, D, D, D, D, D, 0, 0, 0, 0, st));
+    CHECK(vlr_attn_bwd(ws->qkv, off(ws->qkv, D), off(ws->qkv, 2 * (size_t)D), 3 * D, ws->attn, ws->dattn, D, ws->lse, ws->delta, nullptr,
+                       ws->dqkv, off(ws->dqkv, D), off(ws->dqkv, 2 * (size_t)D), 3 * D, n_img, T, cfg->heads, cfg->head_dim, 0, scale, st));
+    // ---- q|k|v: qkv = xn1 Wqkv^T + bqkv
+    CHECK(vlr_gemm_bf16(2, ws->dqkv, ws->xn1, g->wqkv, nullptr, nullptr, 3 * D, D, M, 3 * D, D, D, 0, 0, acc, 0, st));
+    CHECK(vlr_colsum(ws->dqkv, M, 3 * D, 3 * D, g->bqkv, acc, ws->norm_ws, st));
+    CHECK(vlr_gemm_bf16(1, ws->dqkv, w->wqkv, ws->dxn, nullptr, nullptr, M, D, 3 * D, 3 * D, D, D, 0, 0, 0, 0, st));
+    CHECK(vlr_layernorm_bwd_res(ws->dxn, x_in, w->ln1_w, cfg->ln_eps, dx, dx, g->ln1_w, g->ln1_b, acc, ws->norm_ws, M, D, st));       // dx <- d x_in
+    return VLR_OK;
+}

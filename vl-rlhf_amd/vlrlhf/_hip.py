@@ -88,6 +88,14 @@ class VitWs(C.Structure):
     _fields_ = [(n, P) for n in ("xn", "qkv", "attn", "h")]
 
 
+class VitLayerGrads(C.Structure):      # vlr_vit_layer_grads: mirrors VitLayerWeights
+    _fields_ = [(n, P) for n in ("ln1_w", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")]
+
+
+class VitBwdWs(C.Structure):      # vlr_vit_bwd_ws: the recomputed layer and the gradient scratch of vlr_vit_layer_bwd
+    _fields_ = [(n, P) for n in ("xn1", "qkv", "attn", "lse", "x_mid", "xn2", "z", "h", "dh", "dxn", "dattn", "dqkv", "delta", "norm_ws")]
+
+
 # name -> argtypes (every function returns int status, except the *_bytes helpers and vlr_last_error)
 _SIGS = {
     "vlr_gemm_bf16": [I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
@@ -102,6 +110,10 @@ _SIGS = {
     "vlr_layernorm_fwd": [P, P, P, P, I, I, F, P],
     "vlr_layernorm_bwd": [P, P, P, F, P, P, P, I, P, I, I, P],
     "vlr_vit_embed_ln": [P, P, P, P, P, P, I, I, I, F, P],
+    "vlr_vit_embed_ln_bwd": [P, P, P, P, P, P, P, P, P, P, I, P, I, I, I, F, P],
+    "vlr_layernorm_bwd_res": [P, P, P, F, P, P, P, P, I, P, I, I, P],
+    "vlr_act_fwd": [P, P, L, I, P],
+    "vlr_act_bwd": [P, P, P, L, I, P],
     "vlr_im2col": [P, P, I, I, I, I, P],
     "vlr_rope_table": [P, P, I, I, F, P],
     "vlr_rope": [P, P, P, P, I, I, I, I, I, I, P],
@@ -203,6 +215,7 @@ _SIGS = {
     "vlr_gemm_qkv_rope_lora": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, I, P, I, I, I, P],
     "vlr_decoder_layer_bwd": [P, P, P, I, P, P, P, P, P, P, P, I, I, P],
     "vlr_vit_layer_fwd": [P, P, P, P, I, I, P],
+    "vlr_vit_layer_bwd": [P, P, P, I, P, P, P, I, I, P],
     "vlr_decoder_layer_fwd_lora": [P, P, P, P, P, P, U64, P, P, P, I, I, P],
     "vlr_decoder_layer_bwd_lora": [P, P, P, P, I, P, P, P, P, P, U64, P, P, P, P, P, I, I, P],
     "vlr_decoder_layer_fwd_lora_ex": [P, P, P, P, P, P, U64, P, P, P, P, I, I, P],
@@ -247,6 +260,7 @@ _INT_HELPERS = {
     "vlr_rmsnorm_bwd_workspace_bytes": [I],
     "vlr_layernorm_bwd_workspace_bytes": [I],
     "vlr_colsum_workspace_bytes": [I],
+    "vlr_vit_layer_bwd_workspace_bytes": [I, I],
     "vlr_grad_sqnorm_workspace_bytes": [],
     "vlr_abi_version": [],
     "vlr_gemm_peel_rows": [I, I],

@@ -48,7 +48,13 @@ class ParamLayout:
     """Flat layout of the TRAINABLE parameters (LLM + projector; the vision tower is frozen, auto_load.py:554-555).
 
     Weight-decay region first, in the order the backward finishes them (lm_head, layer L-1 .. 0, projector,
-    embed_tokens) so contiguous slices are the DDP buckets; then the no-decay region (norm weights, biases)."""
+    embed_tokens) so contiguous slices are the DDP buckets; then the no-decay region (norm weights, biases).
+
+    cfg["train_vision_tower"] (--freeze_vision_tower False, LLaVA-1.5 / LLaVA-Next): the CLIP tower's EVALUATED tensors join - the
+    embeddings, pre_layrnorm and encoder layers 0 .. vit_layers + vit_feature_layer (q|k|v fused as VisionWeights fuses them).  The
+    weight matrices, class_embedding and position_embedding.weight close the decay region (the backward finishes them last: they
+    ride the last DDP bucket), the LayerNorm weights and the biases the no-decay region - the split of HF's decay grouping.  The
+    never-evaluated last layer and post_layernorm get no gradient in the reference either: they stay in the frozen copy."""
 
     def __init__(self, cfg):
         H, I, V, D, L = cfg["hidden"], cfg["inter"], cfg["vocab"], cfg.get("vit_hidden", 8), cfg["layers"]
@@ -61,6 +67,11 @@ class ParamLayout:
         e = self.entries
         qwen = cfg.get("family") == "qwen_vl"
         ilm = cfg.get("family") == "internlm_xc2"
+        tower = bool(cfg.get("train_vision_tower"))
+        if tower and (qwen or ilm):
+            raise NotImplementedError(f"train_vision_tower: {'Qwen-VL' if qwen else 'InternLM-XComposer2'} has no vision-tower backward "
+                                      "(LLaVA-1.5 and LLaVA-Next only)")
+        self.col_pad = {}           # entry name -> checkpoint shape behind the rows: loaded flattened into the first prod(shape) columns
         self.row_perm = {}          # entry name -> row permutation applied when loading (engine row i = checkpoint row perm[i])
         if ilm:
             # InternLM-XComposer2 (reference models/InternLMXC2/modeling_internlm2.py): fused grouped-query wqkv with rows laid out per
@@ -112,6 +123,21 @@ class ParamLayout:
         if cfg.get("image_grid_pinpoints"):                   # LLaVA-Next: the row appended to every line of the un-padded tile grid
             e.append(("image_newline", (H,), [("image_newline", 0, H)]))
         e.append(("embed", (V, H), [(nm["embed"], 0, V)]))
+        if tower:
+            vp = "vision_tower.vision_model."
+            Fv, Pz = cfg["vit_mlp"], cfg["patch_size"]
+            self.vit_layers = cfg["vit_layers"] + 1 + int(cfg.get("vit_feature_layer", -2))      # the layers the forward evaluates
+            Tv = (cfg["image_size"] // Pz) ** 2 + 1
+            for i in range(self.vit_layers - 1, -1, -1):
+                p = f"{vp}encoder.layers.{i}."
+                e.append((f"vit.l{i}.w2", (D, Fv), [(p + "mlp.fc2.weight", 0, D)]))
+                e.append((f"vit.l{i}.w1", (Fv, D), [(p + "mlp.fc1.weight", 0, Fv)]))
+                e.append((f"vit.l{i}.wo", (D, D), [(p + "self_attn.out_proj.weight", 0, D)]))
+                e.append((f"vit.l{i}.wqkv", (3 * D, D), [(p + f"self_attn.{n_}_proj.weight", j * D, D) for j, n_ in enumerate("qkv")]))
+            e.append(("vit.pos", (Tv, D), [(vp + "embeddings.position_embedding.weight", 0, Tv)]))
+            e.append(("vit.cls", (D,), [(vp + "embeddings.class_embedding", 0, D)]))
+            e.append(("vit.patch_w", (D, _align(3 * Pz * Pz, 8)), [(vp + "embeddings.patch_embedding.weight", 0, D)]))      # K-padded like VisionWeights.patch_w
+            self.col_pad["vit.patch_w"] = (3, Pz, Pz)
         ap = "transformer.visual.attn_pool."
         if qwen and cfg.get("visual"):
             # the resampler of the Qwen-VL vision tower stays trainable in a full fine-tune (QwenVLForRL.freeze_vision_tower,
@@ -164,6 +190,15 @@ class ParamLayout:
         if not (qwen or ilm):
             e.append(("proj.b2", (H,), [("multi_modal_projector.linear_2.bias", 0, H)]))
             e.append(("proj.b1", (H,), [("multi_modal_projector.linear_1.bias", 0, H)]))
+        if tower:
+            for i in range(self.vit_layers - 1, -1, -1):
+                p = f"{vp}encoder.layers.{i}."
+                for k_, n_, w_ in (("b2", "mlp.fc2.bias", D), ("b1", "mlp.fc1.bias", Fv), ("ln2_w", "layer_norm2.weight", D), ("ln2_b", "layer_norm2.bias", D),
+                                   ("bo", "self_attn.out_proj.bias", D), ("ln1_w", "layer_norm1.weight", D), ("ln1_b", "layer_norm1.bias", D)):
+                    e.append((f"vit.l{i}.{k_}", (w_,), [(p + n_, 0, w_)]))
+                e.append((f"vit.l{i}.bqkv", (3 * D,), [(p + f"self_attn.{n_}_proj.bias", j * D, D) for j, n_ in enumerate("qkv")]))
+            e.append(("vit.pre_w", (D,), [(vp + "pre_layrnorm.weight", 0, D)]))
+            e.append(("vit.pre_b", (D,), [(vp + "pre_layrnorm.bias", 0, D)]))
         if rm_head:
             e.append(("rm_head.b", (1,), []))
         if v_head:
@@ -320,7 +355,9 @@ class WeightSet:
             perm = self.layout.row_perm.get(name)
             if perm is not None:
                 t = t[perm.to(t.device)]
-            if dst.dim() == 1:
+            if name in self.layout.col_pad:      # [rows, *shape] in the checkpoint, flattened into the leading columns (the rest stay zero)
+                dst[r0:r0 + rows, :int(math.prod(self.layout.col_pad[name]))].copy_(t.to(BF16).reshape(rows, -1))
+            elif dst.dim() == 1 and rows == dst.shape[0]:
                 dst.copy_(t.to(BF16))
             else:
                 dst[r0:r0 + rows].copy_(t.to(BF16))
@@ -335,7 +372,11 @@ class WeightSet:
             if perm is not None:                  # back to the checkpoint's row order (a copy, not a view)
                 out[hf] = v[invert_perm(perm).to(v.device)]
                 continue
-            out[hf] = v if v.dim() == 1 else v[r0:r0 + rows]
+            if name in self.layout.col_pad:      # back to the checkpoint's shape (splitting the column dimension: still a view)
+                shp = self.layout.col_pad[name]
+                out[hf] = v[r0:r0 + rows, :int(math.prod(shp))].reshape(rows, *shp)
+                continue
+            out[hf] = v if (v.dim() == 1 and rows == v.shape[0]) else v[r0:r0 + rows]
         return out
 
 
@@ -367,6 +408,21 @@ class VisionWeights:
             self._keep.append(t)
             self.layers.append(_hip.VitLayerWeights(*(t[k].data_ptr() for k in (
                 "ln1_w", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2"))))
+
+
+VIT_KEYS = ("ln1_w", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")
+
+
+class TowerViews:
+    """A CLIP tower whose tensors are the "vit.*" views of a flat buffer laid out by ParamLayout(train_vision_tower): the trainable
+    tower over the policy weights (struct = vlr_vit_layer_weights) or its gradients (vlr_vit_layer_grads).  Same attributes as
+    VisionWeights; the views alias the flat buffer, so an optimizer step or a reload moves the tower with it."""
+
+    def __init__(self, views, n_layers, struct):
+        self.patch_w, self.cls, self.pos = views["vit.patch_w"], views["vit.cls"], views["vit.pos"]
+        self.pre_w, self.pre_b = views["vit.pre_w"], views["vit.pre_b"]
+        self.Kp = self.patch_w.shape[1]
+        self.layers = [struct(*(views[f"vit.l{i}.{k}"].data_ptr() for k in VIT_KEYS)) for i in range(n_layers)]
 
 
 class KVCache:
@@ -538,6 +594,11 @@ class LlavaHipEngine:
         self.policy = WeightSet(self.layout, self.dev)
         self.grads = torch.zeros(self.layout.numel, dtype=BF16, device=self.dev)
         self.gv = self.layout.views(self.grads)
+        # --freeze_vision_tower False: the policy pass runs the tower of the trainable buffer, every other pass the initial one (self.vision)
+        self.train_vision = "vit.patch_w" in self.layout.offset
+        self.tower = TowerViews(self.policy.v, self.layout.vit_layers, _hip.VitLayerWeights) if self.train_vision else None
+        self.tower_grads = TowerViews(self.gv, self.layout.vit_layers, _hip.VitLayerGrads) if self.train_vision else None
+        self._vit_cache_policy = None            # _vit_cache of the trainable tower's no-grad passes; dropped at every optimizer step
         # GPTQ int4 base (q_lora): {layout entry: gptq.PackedLinear on the device} for the decoder projections, filled by load_state_dict;
         # the layer passes read a bf16 staging set that layer_weights() dequantises per call, decode_step reads the packed form itself
         self.packed = {} if c.get("gptq") else None
@@ -599,6 +660,7 @@ class LlavaHipEngine:
         # output directory reloads (reference trainer._save writes the whole model)
         self.vision_sd = {k: v.detach().to(device=self.dev, dtype=BF16) for k, v in sd.items() if k.startswith(self.vision_prefix)}
         self._vit_cache = None
+        self._vit_cache_policy = None
         self._weights_version += 1
         if self.master is not None:
             self.init_optimizer()
@@ -640,6 +702,11 @@ class LlavaHipEngine:
         trainable parameters (gradients, optimizer state, DDP bucket) are the adapters."""
         if r <= 0 or r % 8:
             raise ValueError(f"lora_r must be a positive multiple of 8 for the gfx950 GEMM tiles, got {r}")
+        if self.train_vision:
+            # peft freezes every base weight, the tower included: a model laid out to train it would keep the tower's activations and run
+            # its backward into gradients no optimizer reads
+            raise ValueError("enable_lora on a model built with train_vision_tower: under LoRA the vision tower is frozen; load the model "
+                             "without train_vision_tower")
         if self.packed is not None and not self.packed:
             raise ValueError("enable_lora on a packed (GPTQ) engine: load the checkpoint first")
         if self.Nq != self.H:
@@ -835,14 +902,22 @@ class LlavaHipEngine:
                       int(keep))
 
     # ------------------------------------------------------------------------------------------------ vision
-    def vision_features(self, pixel_values: torch.Tensor, key=None) -> torch.Tensor:
+    def vision_features(self, pixel_values: torch.Tensor, key=None, tower=None, keep=None) -> torch.Tensor:
         """CLIP ViT hidden_states[-2] without CLS -> [n*P, D] bf16 (frozen tower: cached per pixel_values tensor so the
         reference pass and the policy pass share one evaluation).  `pixel_values` may be a callable producing the [n,3,s,s]
-        tensor (LLaVA-Next selects the evaluated tiles of a padded 5-D batch) - it is only called on a cache miss."""
+        tensor (LLaVA-Next selects the evaluated tiles of a padded 5-D batch) - it is only called on a cache miss.
+        tower (the trainable tower, self.tower): the same launches on its weights, in buffers and a cache of their own
+        (_vit_cache_policy, keyed by the weights' version too).  keep (a dict, the training pass of a trainable tower): never cached;
+        the pass leaves in `keep` what _vision_backward reads - the im2col patches, the patch embeddings and every layer's INPUT xs[l]
+        (xs[l + 1] is layer l's output)."""
+        policy = tower is not None
         if key is None:
             key = (pixel_values.data_ptr(), tuple(pixel_values.shape), pixel_values._version)
-        if self._vit_cache is not None and self._vit_cache[0] == key:
-            return self._vit_cache[1]
+        if policy:
+            key = (key, self.policy.version, self._weights_version)      # (a reload of the weights moves the tower as a step does)
+        cache = self._vit_cache_policy if policy else self._vit_cache
+        if keep is None and cache is not None and cache[0] == key:
+            return cache[1]
         if callable(pixel_values):
             pixel_values = pixel_values()
         c = self.cfg
@@ -850,18 +925,24 @@ class LlavaHipEngine:
         g = c["image_size"] // c["patch_size"]
         T = g * g + 1
         D, F = self.D, c["vit_mlp"]
-        vw = self.vision
+        vw = tower if policy else self.vision
+        # scratch per kind of pass: the reference pass may run on the side stream while the policy's training pass runs on the main one
+        tag = "vit_train_" if keep is not None else ("vit_policy_" if policy else "vit_")
         pv = pixel_values.to(device=self.dev, dtype=torch.float32).contiguous()
-        patches = self._buf(("vit_patches", n), (n * g * g, vw.Kp))
+        patches = self._buf((tag + "patches", n), (n * g * g, vw.Kp))
         _hip.call("vlr_im2col", pv, patches, n, c["image_size"], c["patch_size"], vw.Kp)
-        pe = self._buf(("vit_pe", n), (n * g * g, D))
+        pe = self._buf((tag + "pe", n), (n * g * g, D))
         _hip.call("vlr_gemm_bf16", 0, patches, vw.patch_w, pe, None, None, n * g * g, D, vw.Kp, vw.Kp, vw.Kp, D, 0, 0, 0, 0)
-        x = self._buf(("vit_x", n), (n * T, D))
+        xs = self._buf((tag + "xs", n), (len(vw.layers) + 1, n * T, D)) if keep is not None else None
+        x = xs[0] if keep is not None else self._buf((tag + "x", n), (n * T, D))
         _hip.call("vlr_vit_embed_ln", pe, vw.cls, vw.pos, vw.pre_w, vw.pre_b, x, n, T, D, self.vit_cfg.ln_eps)
-        wsb = dict(xn=self._buf(("vit_xn", n), (n * T, D)), qkv=self._buf(("vit_qkv", n), (n * T, 3 * D)),
-                   attn=self._buf(("vit_attn", n), (n * T, D)), h=self._buf(("vit_h", n), (n * T, F)))
+        wsb = dict(xn=self._buf((tag + "xn", n), (n * T, D)), qkv=self._buf((tag + "qkv", n), (n * T, 3 * D)),
+                   attn=self._buf((tag + "attn", n), (n * T, D)), h=self._buf((tag + "h", n), (n * T, F)))
         ws = _hip.VitWs(*(wsb[k].data_ptr() for k in ("xn", "qkv", "attn", "h")))
-        for lw in vw.layers:
+        for l, lw in enumerate(vw.layers):
+            if keep is not None:          # the layer runs in place: on a copy of its input, which the backward recomputes it from
+                xs[l + 1].copy_(x)
+                x = xs[l + 1]
             _hip.call("vlr_vit_layer_fwd", self.vit_cfg, lw, ws, x, n, T)
         rows = self._ws.get(("vit_rows", n))
         if rows is None:
@@ -869,10 +950,54 @@ class LlavaHipEngine:
             self._ws[("vit_rows", n)] = rows
         feat = torch.empty(n * (T - 1), D, dtype=BF16, device=self.dev)
         _hip.call("vlr_gather_rows", x, rows, feat, n * (T - 1), D)
-        self._vit_cache = (key, feat, pixel_values)
+        if keep is not None:
+            keep.update(n=n, T=T, xs=xs, pe=pe, patches=patches, rows=rows, tower=vw)
+        elif policy:
+            self._vit_cache_policy = (key, feat, pixel_values)
+        else:
+            self._vit_cache = (key, feat, pixel_values)
         return feat
 
-    def anyres_vision_features(self, pixel_values, image_sizes, image_dup=1):
+    def copy_tower_from(self, vw: VisionWeights, ws: Optional[WeightSet] = None):
+        """the trainable tower's tensors in `ws` (default: the policy) <- the tower `vw` (synthetic initialisers: the policy's tower
+        starts as the initial one, as it does when both are loaded from one checkpoint)"""
+        v = (ws or self.policy).v
+        for k in ("patch_w", "cls", "pos", "pre_w", "pre_b"):
+            v["vit." + k].copy_(getattr(vw, k))
+        for i, t in enumerate(vw._keep):
+            for k in VIT_KEYS:
+                v[f"vit.l{i}.{k}"].copy_(t[k])
+        self._vit_cache_policy = None
+
+    def _vision_backward(self, ctx, vk, dz, acc):
+        """d z of the projector's first linear [n_rows][H] -> the gradients of the trainable tower: d vit_feat = dz W1, scattered to the
+        non-CLS rows of a zeroed [n*T][D] buffer (the inverse of the vit_rows gather), the layers top down (vlr_vit_layer_bwd recomputes
+        each from its kept input), the embeddings + pre_layrnorm, and the patch kernel's d W = d patch_embeds^T patches.  The pixels get
+        no gradient."""
+        n, T, D, F, H = vk["n"], vk["T"], self.D, self.cfg["vit_mlp"], self.H
+        M, R = n * T, n * (T - 1)
+        tw, tg = vk["tower"], self.tower_grads
+        dfeat = self._buf(("vit_bwd", "dfeat", n), (R, D))
+        _hip.call("vlr_gemm_bf16", 1, dz, ctx["ws"].v["proj.w1"], dfeat, None, None, R, D, H, H, D, D, 0, 0, 0, 0)
+        dx = self._buf(("vit_bwd", "dx", n), (M, D))
+        dx.zero_()
+        _hip.call("vlr_scatter_rows", dfeat, vk["rows"], dx, R, D)
+        Sp = _align(T, 64)
+        b = {k: self._buf(("vit_bwd", k, n), (M, w)) for k, w in (("xn1", D), ("qkv", 3 * D), ("attn", D), ("x_mid", D), ("xn2", D), ("z", F),
+                                                                    ("h", F), ("dh", F), ("dxn", D), ("dqkv", 3 * D))}
+        b["dattn"] = b["dxn"]
+        for k in ("lse", "delta"):
+            b[k] = self._buf(("vit_bwd", k, n), (n, self.vit_cfg.heads, Sp), torch.float32)
+        b["norm_ws"] = self._buf(("vit_bwd", "norm_ws"), (_hip.helper("vlr_vit_layer_bwd_workspace_bytes", D, F),), torch.uint8)
+        wsb = _hip.VitBwdWs(*(b[k].data_ptr() for k, _ in _hip.VitBwdWs._fields_))
+        for l in range(len(tw.layers) - 1, -1, -1):
+            _hip.call("vlr_vit_layer_bwd", self.vit_cfg, tw.layers[l], tg.layers[l], acc, vk["xs"][l], wsb, dx, n, T)
+        dpe = self._buf(("vit_bwd", "dpe", n), (R, D))
+        _hip.call("vlr_vit_embed_ln_bwd", dx, vk["pe"], tw.cls, tw.pos, tw.pre_w, dpe, tg.cls, tg.pos, tg.pre_w, tg.pre_b, acc, b["norm_ws"],
+                  n, T, D, self.vit_cfg.ln_eps)
+        _hip.call("vlr_gemm_bf16", 2, dpe, vk["patches"], tg.patch_w, None, None, D, tw.Kp, R, D, tw.Kp, tw.Kp, 0, 0, acc, 0)
+
+    def anyres_vision_features(self, pixel_values, image_sizes, image_dup=1, tower=None, keep=None):
         """LLaVA-Next: the first num_patches(image_size) tiles of every DISTINCT image through the frozen ViT (cached like
         vision_features).  -> (features [tiles*P, D], sizes of the distinct images, tiles per image)"""
         from .models.LlavaNext import anyres as AR
@@ -896,7 +1021,8 @@ class LlavaHipEngine:
             flat = lambda: uniq                                                              # noqa: E731
         else:
             raise ValueError(f"pixel_values of shape {tuple(pixel_values.shape)}, expect to be of 4 or 5 dimensions")
-        vit_feat = self.vision_features(flat, key=(pixel_values.data_ptr(), tuple(pixel_values.shape), pixel_values._version, tuple(usz)))
+        vit_feat = self.vision_features(flat, key=(pixel_values.data_ptr(), tuple(pixel_values.shape), pixel_values._version, tuple(usz)),
+                                        tower=tower, keep=keep)
         if vit_feat.shape[0] != sum(npatch) * self.P:
             raise ValueError(f"{vit_feat.shape[0] // self.P} image tiles given, image_sizes need {sum(npatch)}")
         return vit_feat, usz, npatch
@@ -914,11 +1040,15 @@ class LlavaHipEngine:
         return out, z, h
 
     # ------------------------------------------------------------------------------------------------ forward
-    def _embed_inputs(self, ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta):
+    def _embed_inputs(self, ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta, save=False):
         """vision tower -> projector -> merge index: everything in front of the decoder.  Returns the merged-sequence geometry
-        (S, src / inv maps, mask, positions, merged labels, image map) and the feature rows `feats` the merge gathers from."""
+        (S, src / inv maps, mask, positions, merged labels, image map) and the feature rows `feats` the merge gathers from.
+        With a trainable tower the policy weights run their own tower; a pass that will be back-propagated (`save`) keeps what the
+        tower's backward reads in e["vit_keep"]."""
         c = self.cfg
         Bn, T = ids.shape
+        tower = self.tower if (self.train_vision and ws is self.policy) else None
+        vit_keep = {} if (tower is not None and save) else None
         n_img = pixel_values.shape[0]
         if image_dup > 1:
             assert n_img % image_dup == 0
@@ -929,7 +1059,7 @@ class LlavaHipEngine:
         if self.anyres:
             # ---- LLaVA-Next (reference LlavaNext/__init__.py:205-265): tiles -> ViT -> projector -> anyres pack (row gather)
             from .models.LlavaNext import anyres as AR
-            vit_feat, usz, npatch = self.anyres_vision_features(pixel_values, image_sizes, image_dup)
+            vit_feat, usz, npatch = self.anyres_vision_features(pixel_values, image_sizes, image_dup, tower=tower, keep=vit_keep)
             n_rows = vit_feat.shape[0]
             ext, z, h = self.projector_fwd(ws, vit_feat, tag, extra_rows=1)
             ext[n_rows].copy_(ws.v["image_newline"])
@@ -954,7 +1084,7 @@ class LlavaHipEngine:
             mlabels = cached["labels"].clone()                 # handed out as `output.labels`: every pass gets its own tensor
             n_feat = F
         else:
-            vit_feat = self.vision_features(uniq)
+            vit_feat = self.vision_features(uniq, tower=tower, keep=vit_keep)
             feats, z, h = self.projector_fwd(ws, vit_feat, tag)
             n_rows = feats.shape[0]
             n_feat = n_rows
@@ -984,7 +1114,7 @@ class LlavaHipEngine:
                     f" the number of image given to the model is {n_img}. This prevents correct indexing and breaks batch"
                     " generation.")
         return dict(S=S, M=M, src=src, mask=mask, pos=pos, labels=mlabels, img_map=img_map, inv=inv, feats=feats, vit_feat=vit_feat,
-                    proj_z=z, proj_h=h, n_rows=n_rows, n_feat=n_feat, pack=pack)
+                    proj_z=z, proj_h=h, n_rows=n_rows, n_feat=n_feat, pack=pack, vit_keep=vit_keep)
 
     def _prefix_plan(self, e, ids, Bn, meta):
         """the row maps of a row-compact pass over this [chosen ; rejected] batch (prefix_dedup.py), or None when the shared prompt rows
@@ -1166,7 +1296,10 @@ class LlavaHipEngine:
         ids = input_ids.to(self.dev).contiguous()
         am = attention_mask.to(self.dev).contiguous()
         lab = labels.to(self.dev).contiguous() if labels is not None else None
-        e = self._embed_inputs(ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta)
+        if self.train_vision:
+            e = self._embed_inputs(ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta, save=bool(save))
+        else:
+            e = self._embed_inputs(ws, ids, am, lab, pixel_values, image_dup, tag, image_sizes, meta)
         e["tag"] = tag               # scratch buffers of layers composed in Python are keyed per pass (the reference pass runs on a side stream)
         e["grad_pass"] = bool(save)  # this pass will be back-propagated (training-mode dropout applies; a checkpointed forward included)
         S, M = e["S"], e["M"]
@@ -1250,6 +1383,7 @@ class LlavaHipEngine:
                     vit_feat=vit_feat, feats=feats, proj_z=z, proj_h=h, image_dup=image_dup, n_rows=n_rows, n_feat=n_feat,
                     pack=pack, tag=tag, lora_seed=lora_seed, neftune=nf, meta=meta, extra=e.get("extra"), ckpt=ckpt, use_lora=use_lora,
                     plan=pplan, x0_c=x0_c,     # a row-compact policy pass: acts, x_last, rstd_f and x0_c hold the plan's Mc kept rows; hidden is dense
+                    vit_keep=e.get("vit_keep"),   # a trainable tower's training pass: what _vision_backward reads
                     src_plan=src_plan,         # a dense backward that reads the kept rows in place (_forward_layers_compact_keep)
                     embed=dict(pos=e["pos"], mask=e["mask"], extra=e.get("extra"), tag=tag, img_map=e["img_map"], plora_seed=e.get("plora_seed"), grad_pass=bool(save)))
 
@@ -1843,6 +1977,8 @@ class LlavaHipEngine:
         _hip.call("vlr_gelu_bwd", ctx["proj_z"], dh, dz, dz.numel())
         _hip.call("vlr_colsum", dz, n_rows, H, H, self.gv["proj.b1"], acc, self._colsum_ws)
         _hip.call("vlr_gemm_bf16", 2, dz, ctx["vit_feat"], self.gv["proj.w1"], None, None, H, D, n_rows, H, D, D, 0, 0, acc, 0)
+        if ctx.get("vit_keep"):
+            self._vision_backward(ctx, ctx["vit_keep"], dz, acc)
 
     def make_reducer(self, group=None):
         """DDP gradient reducer over the trainable flat gradient buffer (full fine-tuning: one bucket per decoder layer in
@@ -1880,6 +2016,7 @@ class LlavaHipEngine:
         self.opt_step = int(opt_step)
         # the bf16 working copy is the rounding of the master weights
         (self.lora_flat if self.lora is not None else self.policy.flat).copy_(self.master)
+        self._vit_cache_policy = None
         self._weights_version += 1
 
     def zero_grad(self):
@@ -1934,5 +2071,6 @@ class LlavaHipEngine:
             _hip.call("vlr_adamw_step", self.master[lo:hi], self.m[lo:hi], self.v[lo:hi], self.grads[lo:hi],
                       self.policy.flat[lo:hi], hi - lo, float(lr), float(beta1), float(beta2), float(eps), float(wd),
                       self.opt_step, self.norm_out)
+        self._vit_cache_policy = None      # (the trainable tower moved)
         self.grad_fresh = True
         return self.norm_out

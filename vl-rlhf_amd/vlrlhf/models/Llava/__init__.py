@@ -341,7 +341,7 @@ class LlavaForRL(nn.Module):
                 self._params[f"p{i}"].grad = gsd[hf]
         self._anchor = nn.Parameter(torch.zeros(1, device=self.engine.dev), requires_grad=True)
         self._last_ctx = None
-        self._vision_frozen = True
+        self._vision_frozen = not self.engine.train_vision      # cfg["train_vision_tower"]: the tower's evaluated tensors are parameters
 
     # ---- construction ---------------------------------------------------------------------------------
     @classmethod
@@ -351,8 +351,10 @@ class LlavaForRL(nn.Module):
         return m
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, *args, torch_dtype=None, use_flash_attention_2=None, **kwargs):
-        """reads a transformers==4.41.0 LLaVA checkpoint directory (config.json + *.safetensors)."""
+    def from_pretrained(cls, pretrained_model_name_or_path, *args, torch_dtype=None, use_flash_attention_2=None, train_vision_tower=False,
+                        **kwargs):
+        """reads a transformers==4.41.0 LLaVA checkpoint directory (config.json + *.safetensors).  train_vision_tower
+        (--freeze_vision_tower False): the CLIP tower's evaluated tensors join the trainable parameters."""
         from safetensors.torch import load_file
         path = pretrained_model_name_or_path
         with open(os.path.join(path, "config.json")) as f:
@@ -363,6 +365,8 @@ class LlavaForRL(nn.Module):
         quant = gptq.parse_quantization_config(hf)
         if quant:
             cfg["gptq"] = quant
+        if train_vision_tower:
+            cfg["train_vision_tower"] = True
         m = cls(cfg)
         m.hf_config = hf
         sd = {}
@@ -388,7 +392,8 @@ class LlavaForRL(nn.Module):
         with open(os.path.join(output_dir, "config.json"), "w") as f:
             json.dump(hf, f, indent=1)
         sd = dict(state_dict if state_dict is not None else self.state_dict())
-        sd.update(self.engine.vision_sd)
+        for k, v in self.engine.vision_sd.items():      # the frozen copy; a trained tower's tensors are in the state dict already
+            sd.setdefault(k, v)
         shards, cur, size = [], {}, 0
         for k, v in sd.items():
             nb = v.numel() * v.element_size()
@@ -544,10 +549,15 @@ class LlavaForRL(nn.Module):
         return ["q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj"]
 
     def get_vision_tower(self):
-        return self.engine.vision
+        """the tower this model's forward runs: the trainable one on a policy built with train_vision_tower, else the frozen one"""
+        return self.engine.tower if (self.engine.train_vision and self.weights is self.engine.policy) else self.engine.vision
 
     def freeze_vision_tower(self):
-        self._vision_frozen = True          # the MI355X path keeps the tower frozen (reference default, auto_load.py:554)
+        """reference auto_load.py:554: called unless --freeze_vision_tower False.  Whether the tower trains is decided when the model is
+        built (cfg["train_vision_tower"] lays its tensors out in the trainable buffer): a model built to train it cannot be frozen here."""
+        if self.engine.train_vision:
+            raise ValueError("freeze_vision_tower(): this model was built with train_vision_tower; load it without to keep the tower frozen")
+        self._vision_frozen = True
 
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
         """transformers PreTrainedModel API (the HF Trainer calls it for --gradient_checkpointing True, reference dpo.py:99): the engine

@@ -158,8 +158,13 @@ class MyAutoGenerationConfig:
         return out.get("generation_config", gc)
 
 
+TOWER_FAMILIES = ["Llava", "LlavaNext"]      # --freeze_vision_tower False: the families whose CLIP tower has a backward (engine._vision_backward)
+
+
 def auto_load_rlmodel(script_args, training_args, lora_args):
-    """-> (model, ref_model=None, lora_config); vision tower frozen (reference :554-555; freeze_vision_tower=False raises).  With use_lora the LoraConfig of
+    """-> (model, ref_model=None, lora_config); vision tower frozen unless --freeze_vision_tower False (reference :554-555), which a full
+    fine-tune of LLaVA-1.5 / LLaVA-Next honours, LoRA accepts as the no-op it is in the reference, and the other families refuse by
+    name.  With use_lora the LoraConfig of
     reference :559-571 is returned as a plain dict (peft itself is not needed: the trainer hands it to
     LlavaForRL.apply_lora).
 
@@ -181,13 +186,22 @@ def auto_load_rlmodel(script_args, training_args, lora_args):
     if quant is not None and not use_lora:
         raise ValueError(f"{script_args.model_name_or_path} is a GPTQ checkpoint: packed int4 weights cannot be trained, "
                          "pass --use_lora True (with --q_lora True)")
-    if not getattr(script_args, "freeze_vision_tower", True):
-        # reference :554-555 would train the tower (dpo.py:54 --freeze_vision_tower False); the MI355X path has no ViT backward:
-        # refuse instead of silently training with a frozen tower
-        raise NotImplementedError("--freeze_vision_tower False: the MI355X DPO path has no vision-tower backward; the tower is frozen "
-                                  "in every shipped script of the reference (scripts/dpo_*.sh)")
-    model = MyAutoModel.from_pretrained(script_args.model_name_or_path)
-    model.freeze_vision_tower()
+    train_tower = not getattr(script_args, "freeze_vision_tower", True)
+    if train_tower and use_lora:
+        # reference :554-559: freeze_vision_tower() is simply not called, and peft then freezes every base weight - the flag is a no-op
+        print("[vlrlhf] --freeze_vision_tower False with --use_lora True: peft freezes every base weight, the vision tower stays frozen",
+              flush=True)
+        train_tower = False
+    if train_tower:
+        nick = MODEL_NICKNAME_MAP[_architecture(script_args.model_name_or_path)]
+        if nick not in TOWER_FAMILIES:
+            # refuse instead of silently training with a frozen tower
+            raise NotImplementedError(f"--freeze_vision_tower False: {nick} has no vision-tower backward on the MI355X path; the tower "
+                                      f"trains for {TOWER_FAMILIES} (LLaVA-1.5 and LLaVA-Next) only")
+        model = MyAutoModel.from_pretrained(script_args.model_name_or_path, train_vision_tower=True)
+    else:
+        model = MyAutoModel.from_pretrained(script_args.model_name_or_path)
+        model.freeze_vision_tower()
     model.config.label_pad_token_id = script_args.label_pad_token_id
     model.config.use_cache = False
     lora_config = None

@@ -86,6 +86,9 @@ def init_hashed_model(model, seed=0, std=0.02, policy_delta=1e-3, seed_delta=1, 
         sh[p + "mlp.fc2.weight"], sh[p + "mlp.fc2.bias"] = (D, F), (D,)
     eng.vision = VisionWeights(c, {k: draw(k, s_, 0.0) for k, s_ in sh.items()}, dev, prefix=vp)
     eng._vit_cache = None
+    if getattr(eng, "train_vision", False):
+        for ws in (ref.weights, eng.policy):
+            eng.copy_tower_from(eng.vision, ws)
     return ref
 
 
@@ -130,6 +133,8 @@ def init_random_model(model, seed=0, std=0.02, policy_delta=1e-3):
         if len(shape) == 1 and (name.endswith("ln1") or name.endswith("ln2") or name == "norm"):
             eng.policy.v[name].fill_(1.0)
     eng.vision = VisionWeights(eng.cfg, vision_state_dict(eng.cfg, eng.dev, seed + 1, std), eng.dev)
+    if getattr(eng, "train_vision", False):
+        eng.copy_tower_from(eng.vision)
     ref = model.create_reference_model()
     for a in range(0, flat.numel(), step):
         b = min(flat.numel(), a + step)
