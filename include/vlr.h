@@ -537,6 +537,29 @@ int vlr_grpo_loss_ent(const float* logp, const float* old_logp, const float* ref
                       const float* entropy, const unsigned char* keep, float entropy_coef, float* dlogp, float* dent, float* stats,
                       vlr_stream_t stream);
 
+/* ---- KTO (Kahneman-Tversky Optimization on UNPAIRED feedback: trl's KTOTrainer.kto_loss; additive entry point, vlr_abi_version() does
+ *      not move).  A main row is one prompt, one completion and one label (1 desirable, 0 undesirable); a KL row is a prompt with another
+ *      row's completion.  Every input is a SUMMED completion log-prob: pi / ref [n] fp32 of the policy and the reference on the main rows,
+ *      label [n] bytes, pi_kl / ref_kl [m] fp32 on the KL rows.
+ *      kl     = max(0, (1 / m) sum_j (pi_kl[j] - ref_kl[j]))      a constant: no gradient flows into it (trl detaches it)
+ *      r_i    = pi[i] - ref[i]
+ *      loss_i = w_desirable   (1 - sigmoid(beta (r_i - kl)))      label[i] != 0
+ *             = w_undesirable (1 - sigmoid(beta (kl - r_i)))      label[i] == 0
+ *      loss   = (1 / n) sum_i loss_i                              over ALL n rows, whichever labels occur
+ *      rewards[i] = beta r_i
+ *      dpi[i] = upstream d loss / d pi[i] = -(w_desirable beta / n) s (1 - s) upstream,   s = sigmoid(beta (r_i - kl))    label != 0
+ *                                         = +(w_undesirable beta / n) s (1 - s) upstream, s = sigmoid(beta (kl - r_i))    label == 0
+ *      The weight is formed on the host in fp32 as ((w beta) / n) upstream.  1 - sigmoid(z) is computed as 1 / (1 + expf(z)): a
+ *      saturated z gives loss_i = w or 0 and dpi[i] = 0 exactly, never NaN; z = 0 gives loss_i = w / 2 and s (1 - s) = 1 / 4 exactly.
+ *      losses, rewards, dpi [n] fp32, final on return.  stats[8] = {loss, kl, sum of rewards over label 1, over label 0, sum of pi over
+ *      label 1, over label 0, count of label 1, count of label 0}.
+ *      Refused before any launch: a null pointer, n or m outside 1 .. 2^20, beta, a weight or upstream that is not finite.  One
+ *      workgroup of 1024 threads whose lanes stride the rows; every sum is per-lane partials, six xor butterflies, then the 16 waves in
+ *      order: no atomics, two calls give the same bits; exp is expf; nothing allocates. */
+int vlr_kto_loss(const float* pi, const float* ref, const unsigned char* label, int n, const float* pi_kl, const float* ref_kl, int m,
+                 float beta, float w_desirable, float w_undesirable, float upstream, float* losses, float* rewards, float* dpi,
+                 float* stats, vlr_stream_t stream);
+
 /* ---- sampling: the next token of every row of a generate batch, chosen on the device (additive entry point, vlr_abi_version() does
  *      not move).  One launch per new token on the fp32 logits the lm-head left in HBM; nothing allocates, the logits are never written.
  * vlr_sample_tokens: logits [B][ld] fp32 (ld >= V, 1 <= V < 2^24).  Per row r with unfinished[r] != 0, in this order:

@@ -163,6 +163,8 @@ _SIGS = {
     "vlr_grpo_advantages": [P, I, I, I, P, P, P],
     "vlr_grpo_loss": [P, P, P, P, P, I, I, D, D, F, I, I, F, P, P, P],
     "vlr_grpo_loss_ent": [P, P, P, P, P, I, I, D, D, F, I, I, F, P, P, F, P, P, P, P],
+    # KTO (include/vlr.h "KTO"): the unpaired loss with its statistics and its gradient
+    "vlr_kto_loss": [P, P, P, I, P, P, I, F, F, F, F, P, P, P, P, P],
     "vlr_sample_tokens": [P, I, I, I, I, F, I, F, F, P, I, I, I, P, I, I, P, I, I, U64, U32, U32, P, P, P, P, I, P, P, P, P],
     "vlr_grad_sqnorm": [P, L, F, F, F, P, P, P],
     "vlr_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, P],

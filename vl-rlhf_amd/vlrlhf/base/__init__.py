@@ -1,3 +1,3 @@
-from .collator import VLDPODataCollatorWithPadding  # noqa: F401
+from .collator import VLDPODataCollatorWithPadding, VLKTODataCollatorWithPadding  # noqa: F401
 from .processor import VLChatTemplate, VLProcessor  # noqa: F401
-from .trainer import VLDPOTrainer  # noqa: F401
+from .trainer import KTOConfig, VLDPOTrainer, VLKTOTrainer  # noqa: F401

@@ -122,3 +122,59 @@ class VLPPODataCollator:
             batch[key] = [torch.as_tensor(f[key], dtype=torch.long) if key in ("input_ids", "attention_mask") else f[key] for f in features]
         return batch
 
+
+KTO_BATCH_OF_ONE = ("KTO needs per_device_train_batch_size > 1: the KL row of a batch row carries another row's completion, and with one row "
+                    "the KL term would be that row's own implied reward")
+
+
+@dataclass
+class VLKTODataCollatorWithPadding:
+    r"""KTO rows (`completion_input_ids / _attention_mask / _labels`, `label`, `img_path`) -> a `[chosen ; rejected]`-shaped batch of the
+    family's DPO collator: `chosen_*` holds the B main rows, `rejected_*` their KL rows, the image inputs are those of the B rows (the
+    pair contract: both halves share prompt and image), `kto_label` [B] uint8 is 1 where the row is desirable.
+
+    The KL row of batch row i is prompt i (and image i) with the completion of row (i - 1) mod B - trl's KTOTrainer shifts the completions
+    of a batch by one the same way.  A row's prompt is its leading columns labelled label_pad_token_id, its completion the rest.  The
+    prompt does not move: the KL row carries the main row's prompt columns as the tokeniser left them (so both halves of the batch hold
+    the same image tokens for the same images), and where prompt + completion exceed max_length the COMPLETION is cut as the tokeniser
+    cuts an answer - to max_length - max_prompt_length, or to what the kept prompt leaves of max_length where that is less (at least
+    one token).  Labels: label_pad_token_id on the prompt, the completion's own labels behind it."""
+
+    dpo_collator: Any
+    max_length: int = 512
+    max_prompt_length: int = 128
+    label_pad_token_id: int = -100
+
+    def _split(self, row):
+        labels = list(row["completion_labels"])
+        n = 0
+        while n < len(labels) and labels[n] == self.label_pad_token_id:
+            n += 1
+        return n
+
+    def kl_row(self, row, other) -> Dict[str, Any]:
+        """prompt of `row` + completion of `other`, the completion cut to fit, labelled as a tokenised row is"""
+        n, k = self._split(row), self._split(other)
+        prompt = {f: list(row[f"completion_{f}"][:n]) for f in ("input_ids", "attention_mask")}
+        answer = {f: list(other[f"completion_{f}"][k:]) for f in ("input_ids", "attention_mask", "labels")}
+        if n + len(answer["input_ids"]) > self.max_length:
+            keep = max(1, self.max_length - max(n, self.max_prompt_length))
+            answer = {f: v[:keep] for f, v in answer.items()}
+        return dict(input_ids=prompt["input_ids"] + answer["input_ids"], attention_mask=prompt["attention_mask"] + answer["attention_mask"],
+                    labels=[self.label_pad_token_id] * n + answer["labels"])
+
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        B = len(features)
+        if B < 2:
+            raise ValueError(KTO_BATCH_OF_ONE)
+        rows = []
+        for i, f in enumerate(features):
+            kl = self.kl_row(f, features[(i - 1) % B])
+            row = {f"chosen_{k}": list(f[f"completion_{k}"]) for k in ("input_ids", "attention_mask", "labels")}
+            row.update({f"rejected_{k}": v for k, v in kl.items()})
+            row["img_path"] = f["img_path"]
+            row["label"] = bool(f["label"])
+            rows.append(row)
+        out = self.dpo_collator(rows)
+        out["kto_label"] = torch.tensor([int(r["label"]) for r in rows], dtype=torch.uint8)
+        return out

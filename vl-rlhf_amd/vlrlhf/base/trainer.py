@@ -1228,6 +1228,301 @@ class VLRMTrainer(VLTrainerLoop):
         return state
 
 
+# ----------------------------------------------------------------------------------------------------------
+# KTO: Kahneman-Tversky Optimization on unpaired feedback (trl KTOTrainer; include/vlr.h "KTO")
+# ----------------------------------------------------------------------------------------------------------
+class _KtoLossFn(torch.autograd.Function):
+    """trl KTOTrainer.kto_loss forward, statistics and gradient in ONE launch of vlr_kto_loss -> (loss, losses [n], rewards [n],
+    stats [8], dpi [n] at upstream 1).  Only `pi` is differentiated: the reference and both KL inputs are constants (the KL baseline is detached in trl).  The
+    kernel's gradient is taken at upstream 1 and scaled by the incoming gradient of `loss` in backward - the shared loop applies
+    1 / gradient_accumulation_steps at the optimizer step, as it does for DPO and SFT."""
+
+    @staticmethod
+    def forward(ctx, pi, ref, label, pi_kl, ref_kl, beta, w_desirable, w_undesirable):
+        n, m, dev = pi.shape[0], pi_kl.shape[0], pi.device
+        a = [t.detach().float().contiguous() for t in (pi, ref, pi_kl, ref_kl)]
+        lab = label.to(device=dev, dtype=torch.uint8).contiguous()
+        losses, rewards, dpi = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        stats = torch.empty(8, dtype=torch.float32, device=dev)
+        _hip.call("vlr_kto_loss", a[0], a[1], lab, n, a[2], a[3], m, float(beta), float(w_desirable), float(w_undesirable), 1.0, losses,
+                  rewards, dpi, stats)
+        ctx.save_for_backward(dpi)
+        loss = stats[0].clone()
+        ctx.mark_non_differentiable(losses, rewards, stats, dpi)
+        return loss, losses, rewards, stats, dpi
+
+    @staticmethod
+    def backward(ctx, g_loss, g_losses, g_rewards, g_stats, g_dpi):
+        (dpi,) = ctx.saved_tensors
+        return dpi * g_loss, None, None, None, None, None, None, None
+
+
+@dataclasses.dataclass
+class KTOConfig:
+    """the fields of trl's KTOConfig that this path reads (same names, same defaults) on top of the training arguments the shared loop
+    reads (vlrlhf/dpo.py TrainingArguments: same names, same defaults)."""
+    beta: float = 0.1
+    desirable_weight: float = 1.0
+    undesirable_weight: float = 1.0
+    max_length: Optional[int] = 512
+    max_prompt_length: Optional[int] = 128
+    precompute_ref_log_probs: bool = False
+    output_dir: str = "output"
+    per_device_train_batch_size: int = 4
+    gradient_accumulation_steps: int = 1
+    learning_rate: float = 1e-6
+    weight_decay: float = 0.0
+    adam_beta1: float = 0.9
+    adam_beta2: float = 0.98
+    adam_epsilon: float = 1e-6
+    max_grad_norm: float = 1.0
+    warmup_ratio: float = 0.03
+    warmup_steps: int = 0
+    lr_scheduler_type: str = "cosine"
+    num_train_epochs: float = 1.0
+    max_steps: int = -1
+    logging_steps: int = 10
+    seed: int = 42
+    bf16: bool = True
+    tf32: bool = True
+    gradient_checkpointing: bool = False
+    use_lora: bool = False
+    use_flash_attention_2: bool = True
+    dataset_num_proc: Optional[int] = 16
+    project_name: Optional[str] = "VL-RLHF"
+    group_name: Optional[str] = "llava-1.5-7b-kto"
+    resume_from_checkpoint: Optional[bool] = None
+    report_to: str = "none"
+    run_name: str = "kto"
+    save_strategy: str = "no"
+    save_steps: int = 500
+    save_total_limit: int = 1
+    evaluation_strategy: str = "no"
+    eval_strategy: Optional[str] = None
+    eval_steps: int = 500
+    per_device_eval_batch_size: int = 4
+    dataloader_num_workers: int = 0
+    dataloader_drop_last: bool = False
+    dataloader_prefetch: int = 2
+    remove_unused_columns: bool = False
+    local_rank: int = 0
+    neftune_noise_alpha: Optional[float] = None
+
+    def __post_init__(self):
+        for name in ("beta", "desirable_weight", "undesirable_weight"):
+            v = getattr(self, name)
+            if v is None or not math.isfinite(float(v)):
+                raise ValueError(f"{name} ({v}) must be a finite number")
+        if self.eval_strategy:
+            self.evaluation_strategy = self.eval_strategy
+
+
+class VLKTOTrainer(VLTrainerLoop):
+    """KTO on unpaired rows {prompt, completion, label, img_path} - trl's KTOTrainer on the MI355X path.  A collated batch (base/collator.py
+    VLKTODataCollatorWithPadding) is shaped like a DPO batch: `chosen_*` the B main rows, `rejected_*` their KL rows (prompt i and image
+    i with the completion of row i - 1), so the reference side is VLDPOTrainer's own code: concatenated_forward / _reference_logps, the
+    adapter-off pass under LoRA, a frozen copy otherwise, the row-compact reference pass wherever DPO gets it.  The policy runs ONE
+    training pass over the B main rows and ONE no-grad pass over the B KL rows - never a 2B-row training pass whose backward would cost
+    twice what is needed.  The loss is vlr_kto_loss (_KtoLossFn).
+
+    Deliberate differences from trl: the no-grad KL pass runs in eval mode (no LoRA dropout on a pass nothing differentiates - the choice
+    GRPO made for its no-grad passes); `kl` is this process's mean, not an average across ranks - and more than one rank is refused."""
+
+    dpo_trainer_cls = None      # the family's DPO trainer: its tokenize_row tokenises prompt + one answer (set below / by the model packages)
+
+    def __init__(self, model=None, ref_model=None, args: Optional[KTOConfig] = None, train_dataset=None, eval_dataset=None, processor=None,
+                 data_collator: Any = None, peft_config: Optional[Dict] = None, label_pad_token_id: int = -100, padding_value: int = None,
+                 truncation_mode: str = "keep_end", precompute_ref_log_probs: bool = False, reference_free: bool = False,
+                 callbacks: Optional[List] = None, dataset_num_proc: Optional[int] = None):
+        if model is None:
+            raise ValueError("VLKTOTrainer needs a model")
+        if args is None:
+            args = KTOConfig()
+        # ---- refused by name, before anything is built or changed
+        if _world() > 1:
+            raise NotImplementedError("KTO on more than one GPU: trl averages kl across the ranks, and that has never been run on the "
+                                      "MI355X path")
+        if precompute_ref_log_probs or getattr(args, "precompute_ref_log_probs", False):
+            raise NotImplementedError("precompute_ref_log_probs: the KL rows change with the batch's composition, and the pre-pass that "
+                                      "would store them per batch is not built")
+        if reference_free:
+            raise NotImplementedError("reference_free: KTO's rewards and its KL baseline are log-ratios against a reference model")
+        if bool(getattr(model, "is_packed", False)):
+            raise NotImplementedError("q_lora: KTO over a packed GPTQ base has never been run on the MI355X path")
+        if bool(getattr(getattr(model, "engine", None), "train_vision", False)):
+            raise NotImplementedError("--freeze_vision_tower False: KTO's two policy passes would both need the tower's backward state; "
+                                      "the tower stays frozen on this path")
+        if hasattr(model, "v_head"):
+            raise ValueError("a model with a value head: KTO trains a plain family wrapper (LlavaForRL, QwenVLForRL), it has no value head")
+        if int(getattr(args, "per_device_train_batch_size", 4)) < 2:
+            from .collator import KTO_BATCH_OF_ONE
+            raise ValueError(KTO_BATCH_OF_ONE)
+        if peft_config is not None:
+            if not hasattr(model, "apply_lora"):
+                raise ValueError("peft_config given but the model wrapper has no apply_lora()")
+            model.apply_lora(peft_config)
+        self.is_peft_model = bool(getattr(model, "is_peft_model", False))
+        self._init_neftune(model, args)
+        self.processor = processor
+        self.tokenizer = processor.tokenizer if processor is not None else None
+        self.model = model
+        self.args = args
+        self.beta = float(args.beta)
+        self.desirable_weight = float(args.desirable_weight)
+        self.undesirable_weight = float(args.undesirable_weight)
+        self.loss_type = "kto"
+        self.label_pad_token_id = label_pad_token_id
+        self.padding_value = padding_value if padding_value is not None else (
+            self.tokenizer.pad_token_id if self.tokenizer is not None and self.tokenizer.pad_token_id is not None else 0)
+        self.truncation_mode = truncation_mode
+        self.max_length = args.max_length if getattr(args, "max_length", None) is not None else 512
+        self.max_prompt_length = args.max_prompt_length if getattr(args, "max_prompt_length", None) is not None else 128
+        self.max_target_length = None
+        self.is_encoder_decoder = False
+        self.dataset_num_proc = dataset_num_proc
+        self.callbacks = list(callbacks or [])
+        self._stored_metrics = defaultdict(lambda: defaultdict(list))
+        self.log_history: List[dict] = []
+        self.accelerator = _Accelerator(model)
+        if ref_model is None and not self.is_peft_model:      # trl: no ref_model and no peft -> a frozen deep copy of the policy
+            ref_model = model.create_reference_model() if hasattr(model, "create_reference_model") else None
+        self.ref_model = ref_model
+        self.data_collator = data_collator
+        self.train_dataset = self._tokenize_dataset(train_dataset)
+        self.eval_dataset = self._tokenize_dataset(eval_dataset)
+        self.state = _State()
+        self._warn_balance()
+
+    # the reference side and the log-probs are VLDPOTrainer's own code on the [chosen ; rejected]-shaped batch
+    build_tokenized_answer = VLDPOTrainer.build_tokenized_answer
+    _trl_tokenize_row = VLDPOTrainer._trl_tokenize_row
+    concatenated_inputs = VLDPOTrainer.concatenated_inputs
+    get_batch_logps = staticmethod(VLDPOTrainer.get_batch_logps)
+    concatenated_forward = VLDPOTrainer.concatenated_forward
+    _reference_logps = VLDPOTrainer._reference_logps
+    _reference_pass = staticmethod(VLDPOTrainer._reference_pass)
+    null_ref_context = VLDPOTrainer.null_ref_context
+
+    # ------------------------------------------------------------------------------------------ rows
+    def _tokenize_dataset(self, ds):
+        if ds is None:
+            return None
+        rows = list(ds)
+        if rows and "completion_input_ids" not in rows[0]:
+            rows = [self.tokenize_row(dict(r)) for r in rows]
+        return rows
+
+    def tokenize_row(self, feature, model=None) -> Dict:
+        """prompt + one answer exactly as the family's DPO trainer tokenises a pair's chosen side (its tokenize_row on chosen = rejected =
+        completion: the same template, split, truncation and labels, -100 on the prompt) -> completion_input_ids / _attention_mask /
+        _labels, label, img_path"""
+        cls = self.dpo_trainer_cls or VLDPOTrainer
+        pair = cls.tokenize_row(self, dict(prompt=feature["prompt"], chosen=feature["completion"], rejected=feature["completion"],
+                                           img_path=feature["img_path"]))
+        out = {f"completion_{k}": pair[f"chosen_{k}"] for k in ("input_ids", "attention_mask", "labels")}
+        out["label"] = bool(feature["label"])
+        out["img_path"] = feature["img_path"]
+        return out
+
+    def _warn_balance(self):
+        """trl's advice: desirable_weight n_desirable / (undesirable_weight n_undesirable) should lie in [1, 4/3]; one log line otherwise"""
+        rows = self.train_dataset or []
+        n_d = sum(1 for r in rows if r.get("label"))
+        n_u = len(rows) - n_d
+        self.balance_warning = None
+        if n_d == 0 or n_u == 0 or self.undesirable_weight == 0:
+            return
+        ratio = self.desirable_weight * n_d / (self.undesirable_weight * n_u)
+        if not 1.0 <= ratio <= 4.0 / 3.0:
+            self.balance_warning = (f"[vlrlhf.kto] WARNING: desirable_weight * n_desirable / (undesirable_weight * n_undesirable) = "
+                                    f"{self.desirable_weight:g} * {n_d} / ({self.undesirable_weight:g} * {n_u}) = {ratio:.3f} lies outside "
+                                    f"[1, 4/3]; set the weights so that it lies inside (the KTO paper's advice for imbalanced data)")
+            if _rank() == 0:
+                print(self.balance_warning, flush=True)
+
+    # a batch of one row has no KL row: a trailing batch of one is left out of the epoch (and of evaluate), and counted that way
+    def _train_row_batches(self, epoch: int):
+        for rows in super()._train_row_batches(epoch):
+            if len(rows) >= 2:
+                yield rows
+
+    def _batches_per_epoch(self) -> int:
+        n = super()._batches_per_epoch()
+        bs = int(getattr(self.args, "per_device_train_batch_size", 4))
+        per_rank = -(-len(self.train_dataset) // _world())
+        if not getattr(self.args, "dataloader_drop_last", False) and per_rank % bs == 1:
+            n -= 1      # (the batch left out is always the LAST of the epoch: a resumed run skips the same batches in front of it)
+        return n
+
+    def evaluate(self, eval_dataset=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
+        ds = list(eval_dataset if eval_dataset is not None else (self.eval_dataset or []))
+        bs = int(getattr(self.args, "per_device_eval_batch_size", None) or getattr(self.args, "per_device_train_batch_size", 4))
+        if bs < 2:
+            from .collator import KTO_BATCH_OF_ONE
+            raise ValueError(KTO_BATCH_OF_ONE.replace("per_device_train_batch_size", "per_device_eval_batch_size"))
+        if len(ds) % bs == 1:
+            if _rank() == 0:
+                print(f"[vlrlhf.kto] evaluate: {len(ds)} rows in batches of {bs} leave a last batch of one row, which has no KL row: it is left out",
+                      flush=True)
+            ds = ds[:-1]
+        return super().evaluate(ds, metric_key_prefix)
+
+    # ------------------------------------------------------------------------------------------ the passes of a step
+    def _half_logps(self, model, batch, half: str):
+        """summed completion log-probs [B] of one half of the batch (`chosen`: the main rows, `rejected`: the KL rows) on a plain forward
+        of those B rows with the batch's own images"""
+        dev = self.accelerator.device
+        labels = batch[f"{half}_labels"].to(dev)
+        img = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in (batch.get("img_input_dict") or {}).items()}
+        out = model(input_ids=batch[f"{half}_input_ids"].to(dev), attention_mask=batch[f"{half}_attention_mask"].to(dev), labels=labels,
+                    use_cache=False, **img)
+        final = out.labels if getattr(out, "labels", None) is not None else labels
+        return self.get_batch_logps(out.logits, final, average_log_prob=False, label_pad_token_id=self.label_pad_token_id)
+
+    def kto_loss(self, pi, ref, label, pi_kl, ref_kl):
+        """-> (loss, losses [B], rewards [B], stats [8], dpi [B] at upstream 1) of vlr_kto_loss"""
+        return _KtoLossFn.apply(pi, ref, label, pi_kl, ref_kl, self.beta, self.desirable_weight, self.undesirable_weight)
+
+    def get_batch_loss_metrics(self, model, batch, train_eval: Literal["train", "eval"] = "train"):
+        """reference log-probs of both halves (VLDPOTrainer._reference_logps), the policy's no-grad eval-mode pass over the KL rows, its
+        pass over the main rows (a training pass under training_step), the loss"""
+        if batch["chosen_input_ids"].shape[0] < 2:
+            from .collator import KTO_BATCH_OF_ONE
+            raise ValueError(KTO_BATCH_OF_ONE)
+        ref, ref_kl = self._reference_logps(batch)
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                pi_kl = self._half_logps(model, batch, "rejected")
+        finally:
+            model.train(was_training)
+        pi = self._half_logps(model, batch, "chosen")
+        loss, losses, rewards, stats, dpi = self.kto_loss(pi, ref, batch["kto_label"], pi_kl, ref_kl)
+        prefix = "eval_" if train_eval == "eval" else ""
+        names = ("rewards/chosen_sum", "rewards/rejected_sum", "logps/chosen_sum", "logps/rejected_sum", "count/chosen", "count/rejected")
+        metrics = {f"{prefix}{k}": stats[2 + i] for i, k in enumerate(names)}
+        metrics[f"{prefix}kl"] = stats[1]
+        if self.keep_last:
+            self.last = dict(pi=pi.detach(), ref=ref, pi_kl=pi_kl, ref_kl=ref_kl, losses=losses, rewards=rewards, stats=stats, dpi=dpi)
+        return loss, metrics
+
+    keep_last = False      # tests: keep the log-probs of the last batch in `self.last`
+
+    def compute_loss(self, model, inputs, return_outputs: bool = False):
+        loss, metrics = self.get_batch_loss_metrics(model, inputs, train_eval="train")
+        self.store_metrics(metrics, train_eval="train")
+        if return_outputs:
+            return loss, metrics
+        return loss
+
+    def prediction_step(self, model, inputs, prediction_loss_only: bool = True, ignore_keys=None):
+        with torch.no_grad():
+            loss, metrics = self.get_batch_loss_metrics(model, self._prepare_inputs(inputs), train_eval="eval")
+        self.store_metrics(metrics, train_eval="eval")
+        return loss.detach(), None, None
+
+
 @dataclasses.dataclass
 class PPOConfig:
     """the fields of trl==0.8.1 PPOConfig that the PPO step reads (same names, same defaults).  batch_size = the rows of one step(),

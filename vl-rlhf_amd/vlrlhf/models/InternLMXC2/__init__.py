@@ -11,12 +11,12 @@ import torch
 
 from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLKTOTrainer, VLSFTTrainer
 from ...engine_internlm import InternLMHipEngine
 from ...utils.common import flatten_list
 from ..Llava import LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
 from ..QwenVL import load_qwen_pixel_values
-from ..utils import ModelCoreMapper
+from ..utils import KTOCore, ModelCoreMapper
 
 INTERNLM_XC2_VL_7B = dict(family="internlm_xc2", hidden=4096, inter=14336, layers=32, heads=32, kv_heads=8, vocab=92544, rms_eps=1e-5,
                           rope_theta=1000000.0, vit_hidden=1024, vit_mlp=4096, vit_layers=24, vit_heads=16, image_size=490, patch_size=14,
@@ -284,6 +284,14 @@ class InternLMXC2SFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
 
 class InternLMXC2SFTTRainer(VLSFTTrainer):    # sic: the reference's spelling (:481)
     ...
+
+
+class InternLMXC2KTOTrainer(VLKTOTrainer):
+    dpo_trainer_cls = InternLMXC2DPOTrainer      # prompt + one answer are tokenised as this family's DPO trainer tokenises them
+
+
+# The KTO record: the rows are collated by the DPO collator (base/collator.py VLKTODataCollatorWithPadding wraps it).
+kto_core = KTOCore(dpo_collator=InternLMXC2DPODataCollatorWithPadding, trainer=InternLMXC2KTOTrainer)
 
 
 core_mapper = ModelCoreMapper(

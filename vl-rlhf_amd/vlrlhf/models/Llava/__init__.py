@@ -16,10 +16,10 @@ from ... import _hip, gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLKTOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine import BF16, LlavaHipEngine, WeightSet
 from ...utils.common import flatten_list
-from ..utils import GRPOCore, ModelCoreMapper, PPOCore
+from ..utils import GRPOCore, KTOCore, ModelCoreMapper, PPOCore
 
 
 @dataclass
@@ -1128,6 +1128,14 @@ class LlavaGRPOTrainer(VLGRPOTrainer):
 
 # The GRPO record: the policy is the plain wrapper, the queries are collated as PPO's are.
 grpo_core = GRPOCore(model=LlavaForRL, collator=LlavaPPODataCollator, trainer=LlavaGRPOTrainer)
+
+
+class LlavaKTOTrainer(VLKTOTrainer):
+    dpo_trainer_cls = LlavaDPOTrainer      # prompt + one answer are tokenised as this family's DPO trainer tokenises them
+
+
+# The KTO record: the rows are collated by the DPO collator (base/collator.py VLKTODataCollatorWithPadding wraps it).
+kto_core = KTOCore(dpo_collator=LlavaDPODataCollatorWithPadding, trainer=LlavaKTOTrainer)
 
 
 core_mapper = ModelCoreMapper(

@@ -20,10 +20,10 @@ import torch
 
 from ...base.collator import VLDPODataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.processor import VLChatTemplate
-from ...base.trainer import VLDPOTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLKTOTrainer, VLSFTTrainer
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LlavaForRL, LlavaProcessor, LlavaRLOutputWithPast
-from ..utils import ModelCoreMapper
+from ..utils import KTOCore, ModelCoreMapper
 from . import anyres
 
 LLAVA_NEXT_MISTRAL_7B = dict(
@@ -189,6 +189,14 @@ class LlavaNextSFTDataCollatorWithPadding(VLSFTDataCollatorWithPadding):
 
 class LlavaNextSFTTrainer(VLSFTTrainer):
     ...
+
+
+class LlavaNextKTOTrainer(VLKTOTrainer):
+    dpo_trainer_cls = LlavaNextDPOTrainer      # prompt + one answer are tokenised as this family's DPO trainer tokenises them
+
+
+# The KTO record: the rows are collated by the DPO collator (base/collator.py VLKTODataCollatorWithPadding wraps it).
+kto_core = KTOCore(dpo_collator=LlavaNextDPODataCollatorWithPadding, trainer=LlavaNextKTOTrainer)
 
 
 core_mapper = ModelCoreMapper(

@@ -18,11 +18,11 @@ from ... import gptq
 from ...base.collator import VLDPODataCollatorWithPadding, VLPPODataCollator, VLRMDataCollatorWithPadding, VLSFTDataCollatorWithPadding
 from ...base.model import VLModelWithValueHead, VLRewardModel
 from ...base.processor import VLChatTemplate, VLProcessor
-from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
+from ...base.trainer import VLDPOTrainer, VLGRPOTrainer, VLKTOTrainer, VLPPOTrainer, VLRMTrainer, VLSFTTrainer
 from ...engine_qwen import QwenVLHipEngine
 from ...utils.common import flatten_list
 from ..Llava import CLIP_MEAN, CLIP_STD, LazyLogits, LlavaForRL, LlavaRLOutputWithPast, _HiddenFn
-from ..utils import GRPOCore, ModelCoreMapper, PPOCore
+from ..utils import GRPOCore, KTOCore, ModelCoreMapper, PPOCore
 
 IGNORE_TOKEN_ID = -100           # transformers LabelSmoother.ignore_index
 
@@ -460,6 +460,14 @@ class QwenVLGRPOTrainer(VLGRPOTrainer):
 
 # The GRPO record: the policy is the plain wrapper, the queries are collated as PPO's are.
 grpo_core = GRPOCore(model=QwenVLForRL, collator=QwenVLPPODataCollator, trainer=QwenVLGRPOTrainer)
+
+
+class QwenVLKTOTrainer(VLKTOTrainer):
+    dpo_trainer_cls = QwenVLDPOTrainer      # prompt + one answer are tokenised as this family's DPO trainer tokenises them
+
+
+# The KTO record: the rows are collated by the DPO collator (base/collator.py VLKTODataCollatorWithPadding wraps it).
+kto_core = KTOCore(dpo_collator=QwenVLDPODataCollatorWithPadding, trainer=QwenVLKTOTrainer)
 
 
 core_mapper = ModelCoreMapper(

@@ -38,3 +38,11 @@ class GRPOCore:
     model: Any
     collator: Any = None
     trainer: Any = None
+
+
+@dataclass
+class KTOCore:
+    """KTO's record (`kto_core`, resolved by utils/auto_load.py MyAutoKTOTrainer / MyAutoKTOCollator), exported by every package that has
+    a DPO trainer: the rows are collated by the family's DPO collator behind base/collator.py VLKTODataCollatorWithPadding"""
+    dpo_collator: Any
+    trainer: Any

@@ -57,6 +57,24 @@ class MyAutoDPOTrainer:
         return auto_core_mapper(_architecture(model_name_or_path)).dpo_trainer(*args, **kwargs)
 
 
+class MyAutoKTOCollator:
+    def __new__(cls, model_name_or_path, pad_token_id=0, label_pad_token_id=-100, processor=None, max_length=512, max_prompt_length=128):
+        """the family's DPO collator behind the KTO collator: a KTO batch is a `[chosen ; rejected]`-shaped batch of main and KL rows"""
+        from ..base.collator import VLKTODataCollatorWithPadding
+        nick = MODEL_NICKNAME_MAP[_architecture(model_name_or_path)]
+        auto_core_mapper(_architecture(model_name_or_path))      # (refuses the families without an MI355X path)
+        dpo = import_module(f".{nick}", "vlrlhf.models").kto_core.dpo_collator(pad_token_id, label_pad_token_id, False, processor)
+        return VLKTODataCollatorWithPadding(dpo, max_length=max_length, max_prompt_length=max_prompt_length,
+                                            label_pad_token_id=label_pad_token_id)
+
+
+class MyAutoKTOTrainer:
+    def __new__(cls, model_name_or_path, *args, **kwargs):
+        nick = MODEL_NICKNAME_MAP[_architecture(model_name_or_path)]
+        auto_core_mapper(_architecture(model_name_or_path))
+        return import_module(f".{nick}", "vlrlhf.models").kto_core.trainer(*args, **kwargs)
+
+
 class MyAutoSFTCollator:
     def __new__(cls, model_name_or_path, pad_token_id=0, label_pad_token_id=-100, processor=None):
         return auto_core_mapper(_architecture(model_name_or_path)).sft_collator(pad_token_id, label_pad_token_id, processor)

@@ -141,7 +141,51 @@ def build_dataset_from_vlquery_json(script_args):
     return [dict(d, img_path=os.path.join(script_args.image_root or "", d["image"])) for d in raw]
 
 
+def unpair(rows):
+    """paired rows {prompt, chosen, rejected, img_path} -> KTO's unpaired rows {prompt, completion, label, img_path}: every pair gives
+    (prompt, chosen, True) then (prompt, rejected, False), both with the pair's prompt and img_path"""
+    out = []
+    for r in rows:
+        out.append(dict(prompt=r["prompt"], completion=r["chosen"], label=True, img_path=r["img_path"]))
+        out.append(dict(prompt=r["prompt"], completion=r["rejected"], label=False, img_path=r["img_path"]))
+    return out
+
+
+def make_kto_json_dataset(script_args):
+    """`--dataset_name kto_json`: a JSON list of {prompt, completion, label, image | img_path} - one prompt, one completion and one
+    thumbs-up (true) or thumbs-down (false) per row; img_path = image_root / image"""
+    with open(script_args.data_path) as f:
+        data = json.load(f)
+    rows = []
+    for d in data:
+        img = d["image"] if "image" in d else d["img_path"]
+        if getattr(script_args, "image_root", None):
+            img = os.path.join(script_args.image_root, img)
+        label = d["label"]
+        if isinstance(label, str):
+            label = label.strip().lower() in ("1", "true", "yes")
+        rows.append(dict(prompt=d["prompt"], completion=d["completion"], label=bool(label), img_path=img))
+    return rows
+
+
+def make_vlfeedback_unpaired_dataset(script_args):
+    return unpair(make_vlfeedback_paired_dataset(script_args))
+
+
+def make_rlhfv_unpaired_dataset(script_args):
+    return unpair(make_rlhfv_paired_dataset(script_args))
+
+
+def make_synthetic_unpaired_dataset(script_args):
+    """`--dataset_name synthetic_unpaired`: the synthetic pairs split in two (tests, benchmarks)"""
+    return unpair(make_synthetic_dataset(script_args))[: int(getattr(script_args, "synthetic_rows", 64))]
+
+
 DATASET_MAP = {
+    "kto_json": make_kto_json_dataset,
+    "vlfeedback_unpaired": make_vlfeedback_unpaired_dataset,
+    "rlhfv_unpaired": make_rlhfv_unpaired_dataset,
+    "synthetic_unpaired": make_synthetic_unpaired_dataset,
     "vlfeedback_paired": make_vlfeedback_paired_dataset,
     "rlhfv": make_rlhfv_paired_dataset,
     "vlquery_json": build_dataset_from_vlquery_json,
